@@ -4,10 +4,20 @@
 Counterpart of the reference's scripts/benchmark_video_speed.py:69-109.  Frames are the reference's synthetic frames,
 seeded as SURVEY 8(d) asks: frame i = RandomState(1234+i).randint(0,256,(256,256,3),uint8) BGR.  A "step" is one pass of
 the frame loop (BGR->gray, u8 -> /255 -> U-Net -> sigmoid -> >0.5 -> per-frame area) over this rank's frames, followed by
-the area-waveform all-gather (RCCL) when N > 1.  ONE JSON line:
+the area-waveform all-gather (RCCL) when N > 1.  ONE JSON line.  A plain run sets up, warms up, times --steps steps and prints
+the headline only:
 
   value           frames/s with the (gray) frames already RESIDENT IN HBM when the timed region starts and the int32 areas
-                  left on the device (the contract's headline).
+                  left on the device (the contract's headline); `ms_per_step` is the wall time of one timed step.
+
+--dump-outputs DIR writes what the timed path returned in its last step: DIR/areas.npy, the area of every frame (float64).
+--full adds every other leg (each can still be left out with its --no-* flag):
+
+  parity          Dice delta and flipped pixels against the reference's fixtures (tests/golden/unet_full128.npz, unet_trained_hard.npz).
+  latency_mode    one frame per kernel chain, and the reference's per-frame call.
+  split_precision the exploratory f16 hi/lo mode.
+  gated_c3, crop_c5_standin  the pipelines either side of the headline (pipeline_legs).
+  c4_strong       N > 1 without --total-frames: ONE 10 000-frame video sharded over the ranks.
   host_inclusive  the reference's timed region (benchmark_video_speed.py:83-109 / SURVEY 8(d)): pinned host BGR u8 frames
                   -> H2D -> BGR->gray on the device -> U-Net -> int32 areas back on the host, through the streaming engine
                   (og_unet_stream_u8); N = 1 only.
@@ -17,7 +27,8 @@ the area-waveform all-gather (RCCL) when N > 1.  ONE JSON line:
   direct_form     the same chain on the direct 3x3 kernels (option wino=0): frames/s, chain fraction and dominant-kernel roofline.
   cpu_baseline    the oracle's torch-CPU restatement of the same loop body on the host cores, 1 thread and all cores.
 
-  python bench.py                                   # 1 GPU, 512 frames per step
+  python bench.py                                   # 1 GPU, 512 frames per step, headline only
+  python bench.py --full                            # the same headline, then every leg above
   python bench.py --gpus 8                          # starts its own 8 ranks (one process per GPU, RCCL), relays rank 0's line
   python bench.py --gpus 8 --total-frames 10000     # config C4: ONE 10 000-frame video sharded over the ranks (strong scaling)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
@@ -319,7 +330,16 @@ def main() -> None:
                     help="CPU-only check of the N > 1 plumbing (self-launch, rendezvous, shard_range, ragged all-gather over gloo, "
                          "JSON relay, exit codes) with NO device work: the line it prints says so and is not a measurement")
     ap.add_argument("--plumbing-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg (parity, host_inclusive, latency_mode, roofline, direct_form, "
+                         "split_precision, pipelines, c4_strong, cpu_baseline) unless its --no-* flag leaves it out")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path returned in its last step to DIR/areas.npy (float64, one area per frame)")
     args = ap.parse_args()
+    if not args.full:   # a plain run does only what the headline needs
+        for leg in ("parity", "host_inclusive", "latency_mode", "roofline", "direct_form", "split_precision", "pipelines",
+                    "c4_strong", "cpu_baseline"):
+            setattr(args, "no_" + leg, True)
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(sys.argv[1:], args.gpus))   # one process per GPU; this parent has not touched the GPU
@@ -427,6 +447,10 @@ def main() -> None:
         per_rank = [[int(v[0].item()), float(v[1].item())] for v in allr]
     assert wave.numel() == n_total and int(wave.min()) >= 0
     wave = wave.clone()   # `area` is reused by the legs below
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the int32 area of every frame (all ranks' at N > 1)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "areas.npy"), wave.cpu().numpy().astype(np.float64))
 
     out = None
     if rank == 0:

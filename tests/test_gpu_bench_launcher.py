@@ -27,7 +27,7 @@ def _bench(extra):
 
 
 def test_bench_starts_its_own_two_ranks_weak_scaling():
-    out = _bench(["--gpus", "2", "--frames", "128"])
+    out = _bench(["--gpus", "2", "--frames", "128", "--full"])
     assert out["n_gpus"] == 2 and out["world"] == 2 and out["scaling"] == "weak" and out["unit"] == "frames/s"
     assert out["collective"]["ranks"] == 2 and out["collective"]["backend"] == "gloo"
     assert out["config"]["frames_per_step_all_gpus"] == 256 and out["per_rank_frames"] == [128, 128]
@@ -41,7 +41,24 @@ def test_bench_starts_its_own_two_ranks_weak_scaling():
 
 
 def test_bench_strong_scaling_ragged_video_on_two_ranks():
-    out = _bench(["--gpus", "2", "--total-frames", "301"])           # ceil(301 / 2) = 151 + 150
+    out = _bench(["--gpus", "2", "--total-frames", "301", "--full"])   # ceil(301 / 2) = 151 + 150
     assert out["world"] == 2 and out["scaling"] == "strong"
     assert out["config"]["frames_per_step_all_gpus"] == 301 and out["per_rank_frames"] == [151, 150]
     assert out["value"] > 1000
+
+
+def test_plain_run_is_the_headline_only_and_dumps_its_areas(tmp_path):
+    """A plain run (no --full) times the headline loop and nothing else; --dump-outputs writes the areas of its last timed step,
+    and the two-rank loop's gathered waveform holds the same integers for the same frames."""
+    import numpy as np
+
+    out = _bench(["--gpus", "1", "--frames", "128", "--dump-outputs", str(tmp_path / "one")])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["unit"] == "frames/s" and out["dtype"] == "f32" and out["higher_is_better"]
+    assert abs(out["ms_per_step"] - 1e3 * 128 / out["value"]) <= 0.01 * out["ms_per_step"]
+    legs = {"parity", "host_inclusive", "latency_mode", "roofline", "direct_form", "split_precision", "gated_c3", "crop_c5_standin",
+            "c4_strong", "cpu_baseline"}
+    assert not legs & set(out), legs & set(out)
+    areas = np.load(tmp_path / "one" / "areas.npy")
+    assert areas.dtype == np.float64 and areas.shape == (128,) and areas.min() >= 0 and np.array_equal(areas, np.round(areas))
+    _bench(["--gpus", "2", "--frames", "64", "--dump-outputs", str(tmp_path / "two")])
+    assert np.array_equal(np.load(tmp_path / "two" / "areas.npy"), areas)

@@ -13,11 +13,11 @@ export TMPDIR=/tmp
 O=gpurun_out/prof_r04
 mkdir -p $O
 COMMON="--lanes 1 --steps 4 --warmup 1 --no-cpu-baseline --no-latency-mode --no-host-inclusive --no-split-precision --no-parity --no-pipelines"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python3 bench.py $COMMON > $O/bench_under_rocprof_lanes1.json 2> $O/stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o bench -- python3 bench.py --full $COMMON > $O/bench_under_rocprof_lanes1.json 2> $O/stats.err
 echo "stats rc=$?"
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o bench -- python3 bench.py $COMMON --no-roofline --no-direct-form > /dev/null 2> $O/fetch.err
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o bench -- python3 bench.py --full $COMMON --no-roofline --no-direct-form > /dev/null 2> $O/fetch.err
 echo "fetch rc=$?"
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -o bench -- python3 bench.py $COMMON --no-roofline --no-direct-form > /dev/null 2> $O/write.err
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -o bench -- python3 bench.py --full $COMMON --no-roofline --no-direct-form > /dev/null 2> $O/write.err
 echo "write rc=$?"
 F=$(find $O/fetch -name "*counter_collection.csv" | head -1); W=$(find $O/write -name "*counter_collection.csv" | head -1)
 python3 tools/pmc_traffic.py "$F" "$W" $O/pmc_traffic_chunk64.json > $O/pmc_traffic_chunk64.txt; echo "pmc rc=$?"
@@ -39,11 +39,11 @@ tools/ubench/wino1_two_waves_per_simd > $O/ubench_wino1_two_waves_per_simd.txt 2
 tools/ubench/gather_policy > $O/ubench_gather_policy.txt 2>&1
 tools/ubench/mfma_16x16x4_order > $O/ubench_mfma_16x16x4_order.txt 2>&1
 python3 tools/soak_w.py 8 2>&1 | grep -v amdgpu > $O/soak_wave_split_determinism.txt; echo "soak rc=$?"
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
-python3 bench.py --total-frames 10000 --no-split-precision --no-direct-form --no-pipelines > $O/bench_c4_total_frames_10000_n1.json 2> /dev/null; echo "c4 rc=$?"
-OG_BENCH_BACKEND=gloo python3 bench.py --gpus 2 --steps 5 --no-cpu-baseline > $O/bench_selflaunch_gloo_shared_gpu_n2.json 2> $O/bench_selflaunch_gloo_shared_gpu_n2.err; echo "n2 rc=$?"
-OG_BENCH_BACKEND=gloo python3 bench.py --gpus 3 --steps 3 --no-cpu-baseline > $O/bench_selflaunch_gloo_shared_gpu_n3.json 2> /dev/null; echo "n3 rc=$?"
-OG_BENCH_FORCE_DIST=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --steps 5 --no-cpu-baseline --no-split-precision --no-direct-form --no-pipelines > $O/bench_rccl_world1_forced_dist.json 2> $O/bench_rccl_world1_forced_dist.err; echo "rccl rc=$?"
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"
+python3 bench.py --full --total-frames 10000 --no-split-precision --no-direct-form --no-pipelines > $O/bench_c4_total_frames_10000_n1.json 2> /dev/null; echo "c4 rc=$?"
+OG_BENCH_BACKEND=gloo python3 bench.py --full --gpus 2 --steps 5 --no-cpu-baseline > $O/bench_selflaunch_gloo_shared_gpu_n2.json 2> $O/bench_selflaunch_gloo_shared_gpu_n2.err; echo "n2 rc=$?"
+OG_BENCH_BACKEND=gloo python3 bench.py --full --gpus 3 --steps 3 --no-cpu-baseline > $O/bench_selflaunch_gloo_shared_gpu_n3.json 2> /dev/null; echo "n3 rc=$?"
+OG_BENCH_FORCE_DIST=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 1 --steps 5 --no-cpu-baseline --no-split-precision --no-direct-form --no-pipelines > $O/bench_rccl_world1_forced_dist.json 2> $O/bench_rccl_world1_forced_dist.err; echo "rccl rc=$?"
 python3 scripts/benchmark_video_speed.py --frames 502 --json 2>&1 | grep -v amdgpu > $O/benchmark_video_speed_unet_only.txt
 python3 scripts/benchmark_video_speed.py --frames 502 --json --yolo-weights weights/none.npz 2>&1 | grep -v amdgpu > $O/benchmark_video_speed_gated.txt
 python3 tools/bench_detect_latency.py 2>&1 | grep -v amdgpu > $O/detector_and_unet_call_latency.txt

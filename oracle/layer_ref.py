@@ -1,0 +1,498 @@
+"""Float64 single-op references of the U-Net's layers and a per-element error bound.  TEST INFRASTRUCTURE.
+
+Only ``tests/`` imports this module; nothing under ``openglottal_amd/`` does.
+
+Every reference here is computed from the GPU's OWN input tensor of the op (``UNet.activation``), so one launch is judged in
+isolation from all upstream error.  The ops are those of ``unet_oracle`` (the reference's arithmetic), in float64:
+
+* ``conv3``  3x3 conv (pad 1, no bias) + eval BatchNorm (eps ``unet_oracle.BN_EPS``) + ReLU;
+* ``first``  the same op on u8 frames scaled by 1/255 (utils.py:235);
+* ``pool``   2x2 max-pool (exact: compared bit for bit);
+* ``convt``  ConvTranspose 2x2 stride 2 + bias;
+* ``head``   the 1x1 head + bias (the logits).
+
+The bound of an output element is ``kappa_form * 2^-24 * M + FLOOR`` where ``M`` is a magnitude pass of the same op in float64:
+``M = |s| * conv(|x|, |w|) + |s * mu| + |beta|`` with ``s`` the folded BN scale (for ``convt`` / ``head``: ``conv(|x|, |w|) + |b|``).
+ReLU is 1-Lipschitz, so the bound of the pre-activation holds after it.  Where a launch fuses two ops and the boundary between
+them is not stored, the next stored tensor is checked against the composed reference with the bound
+``own + |s| * conv(bound_in, |w|)`` (the fused first layer at ``keep_taps`` 0, the fused head without the ``ups.N.b`` tap).
+
+kappa per form (fixed BEFORE any GPU run; ``tests/test_layer_ref.py`` re-derives the two emulated figures on the CPU and checks
+that every mutant of a kernel's arithmetic still exceeds the bound):
+
+* ``direct`` = 16.  Direct f32 MFMA (``k_conv_mfma*``, ``k_convt_w``, ``k_conv_first``, the heads): the MFMA result is a k-ordered
+  f32 fma chain; the guide's measured error against float64 is 0.75-1.5e-7 * sum|a*b| at K <= 1024 (kappa 1.3-2.5) and 3.5e-7 at
+  K = 4096 (kappa 5.9); the largest K here is 512 channels x 9 taps = 4608.  The folded scale / shift (rounded once from
+  float64) and the epilogue's fma add two roundings of at most |s * acc| and |shift|, both inside M.  16 = 2.7x the K = 4096 figure.
+* ``wino`` = 24.  Winograd F(2x2,3x3) (``k_conv_wino*``): the transforms re-associate the sums, so the error is measured against
+  the direct magnitude M, not derived.  ``wino_f32`` below emulates the kernel's arithmetic in numpy f32 (B^T d B adds in f32,
+  U = G g G^T in float64 rounded once, a k-ordered f32 sum over the channels with one rounding per product and per add, A^T M A
+  adds in f32, the epilogue); on the matrix's nets (random weights; random / all-0 / all-255 / 0-255 checkerboard / one-pixel
+  stripe frames and their quadrant mosaic; every 3x3 layer; the seed-3 nets and the five-level net of the GPU matrix with its own
+  weights and frames) the worst |err| / (2^-24 M) it reaches is 8.6 (``WINO_EMULATED_MAX``: downs.0.b of that five-level net, whose
+  3-channel input from the special frames is the hardest case).  24 = 2.8x that; the weakest mutant of ``tests/test_layer_ref.py``
+  (BN eps x10) is still ~20x over.  On the GPU the same layer, weights and frames reach 10.6 (0.44 of the bound): the kernel's
+  packed sign-fma transforms round ~1.25x worse than the emulation's plain adds there; every other Winograd layer stays <= 3.5.
+* ``split`` = 16.  Split precision (``k_conv_mfma_h``, precision 1): v = hi + lo * 2^-11 with f16 hi / lo, three exact f16
+  products hi*hi + (hi*lo + lo*hi) * 2^-11 in f32 accumulation, the lo*lo term dropped, and every stored activation rounded to a
+  hi / lo pair again.  ``split_f32`` emulates it; the worst emulated ratio is 3.9 (``SPLIT_EMULATED_MAX``).  16 = 4x that; the
+  dropped a_lo * b_hi product (the mutant closest to the arithmetic's own error) is ~100x over.
+
+``FLOOR`` (1e-30) only keeps exact zeros and subnormal references from dividing by zero; it is far below every M of these nets.
+"""
+
+from __future__ import annotations
+
+import numpy as np
+
+from .unet_oracle import BN_EPS, n_levels
+
+U = 2.0 ** -24
+FLOOR = 1e-30
+KAPPA = {"direct": 16.0, "wino": 24.0, "split": 16.0}
+WINO_EMULATED_MAX = 8.6      # recorded by tests/test_layer_ref.py::test_winograd_emulation_passes_at_its_kappa (asserts <= 2x this)
+SPLIT_EMULATED_MAX = 3.9     # recorded by tests/test_layer_ref.py::test_split_precision_emulation_passes_at_its_kappa
+
+
+# ───────────────────────────── float64 ops ─────────────────────────────
+
+
+def _t(x):
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
+
+
+def conv3_raw(x: np.ndarray, w: np.ndarray) -> np.ndarray:
+    """x [B,Ci,H,W], w [Co,Ci,3,3] -> [B,Co,H,W] float64 (pad 1, cross-correlation, no bias)."""
+    import torch.nn.functional as F
+
+    return F.conv2d(_t(x), _t(w), None, 1, 1).numpy()
+
+
+def fold_bn(sd: dict, bn: str, eps: float = BN_EPS):
+    """Eval BatchNorm as y = s * conv + shift, float64; also the magnitude of the affine part |s * mu| + |beta|."""
+    g, b = sd[bn + ".weight"].astype(np.float64), sd[bn + ".bias"].astype(np.float64)
+    mu, var = sd[bn + ".running_mean"].astype(np.float64), sd[bn + ".running_var"].astype(np.float64)
+    s = g / np.sqrt(var + eps)
+    return s, b - mu * s, np.abs(s * mu) + np.abs(b)
+
+
+def conv3_bn_relu(sd: dict, w_key: str, bn: str, x: np.ndarray, eps: float = BN_EPS):
+    """(ref, pre-activation, M) of conv3x3 + BN + ReLU on x (float64)."""
+    w = sd[w_key]
+    s, shift, aff = fold_bn(sd, bn, eps)
+    pre = s[None, :, None, None] * conv3_raw(x, w) + shift[None, :, None, None]
+    M = np.abs(s)[None, :, None, None] * conv3_raw(np.abs(x), np.abs(w)) + aff[None, :, None, None]
+    return np.maximum(pre, 0.0), pre, M
+
+
+def first_input(gray: np.ndarray) -> np.ndarray:
+    """u8 frames [B,H,W] -> the first layer's input [B,1,H,W] (utils.py:235), float64."""
+    return (np.asarray(gray, dtype=np.float64) / 255.0)[:, None]
+
+
+def maxpool2(x: np.ndarray) -> np.ndarray:
+    B, C, H, W = x.shape
+    return x.reshape(B, C, H // 2, 2, W // 2, 2).max(axis=(3, 5))
+
+
+def convt_raw(x: np.ndarray, w: np.ndarray) -> np.ndarray:
+    import torch.nn.functional as F
+
+    return F.conv_transpose2d(_t(x), _t(w), None, 2).numpy()
+
+
+def convt(sd: dict, key: str, x: np.ndarray):
+    """(ref, M) of ConvTranspose2d(k=2, s=2) + bias."""
+    w, b = sd[key + ".weight"], sd[key + ".bias"].astype(np.float64)
+    ref = convt_raw(x, w) + b[None, :, None, None]
+    M = convt_raw(np.abs(x), np.abs(w)) + np.abs(b)[None, :, None, None]
+    return ref, M
+
+
+def head(sd: dict, x: np.ndarray):
+    """(ref, M) of the 1x1 head: logits [B,1,H,W]."""
+    w, b = sd["head.weight"][:, :, 0, 0].astype(np.float64), sd["head.bias"].astype(np.float64)
+    ref = np.einsum("oc,bchw->bohw", w, x.astype(np.float64)) + b[None, :, None, None]
+    M = np.einsum("oc,bchw->bohw", np.abs(w), np.abs(x.astype(np.float64))) + np.abs(b)[None, :, None, None]
+    return ref, M
+
+
+# ───────────────────────────── the check ─────────────────────────────
+
+
+class LayerMismatch(AssertionError):
+    pass
+
+
+def check(name: str, got: np.ndarray, ref: np.ndarray, bound: np.ndarray, frames=None, tile=(16, 16)) -> float:
+    """|got - ref| <= bound elementwise ([B,C,H,W]); returns the worst |err| / bound.  On failure the message names the layer, the
+    frame, the channel, (y, x), the ``tile``-sized grid cell (y, x) falls in (16 x 16: the output tile of k_conv_wino<1> / <2>, two
+    8 x 16 tiles of the direct kernels), the Winograd 2 x 2 output window and its position, and the worst ratio."""
+    got = np.asarray(got, dtype=np.float64)
+    assert got.shape == ref.shape == bound.shape, (name, got.shape, ref.shape, bound.shape)
+    if not np.all(np.isfinite(got)):
+        b, c, y, x = (int(v) for v in np.argwhere(~np.isfinite(got))[0])
+        raise LayerMismatch(f"{name}: non-finite value {got[b, c, y, x]} at frame {_frame(frames, b)} ch {c} (y,x)=({y},{x})")
+    ratio = np.abs(got - ref) / bound
+    worst = float(ratio.max()) if ratio.size else 0.0
+    if worst > 1.0:
+        b, c, y, x = (int(v) for v in np.unravel_index(int(np.argmax(ratio)), ratio.shape))
+        n_bad = int((ratio > 1.0).sum())
+        raise LayerMismatch(
+            f"{name}: |err|/bound = {worst:.3g} at frame {_frame(frames, b)} ch {c} (y,x)=({y},{x}) in {tile[0]}x{tile[1]} grid cell "
+            f"({y // tile[0]},{x // tile[1]}) at ({y % tile[0]},{x % tile[1]}) inside it, Winograd 2x2 window ({y // 2},{x // 2}) pos ({y % 2},{x % 2}); got {got[b, c, y, x]!r} ref {ref[b, c, y, x]!r} "
+            f"bound {bound[b, c, y, x]:.3g}; {n_bad} element(s) over the bound")
+    return worst
+
+
+def check_exact(name: str, got: np.ndarray, ref: np.ndarray, frames=None) -> None:
+    got, ref = np.asarray(got), np.asarray(ref)
+    assert got.shape == ref.shape, (name, got.shape, ref.shape)
+    bad = np.argwhere(got != ref)
+    if len(bad):
+        b, c, y, x = (int(v) for v in bad[0])
+        raise LayerMismatch(f"{name}: not bit-identical at frame {_frame(frames, b)} ch {c} (y,x)=({y},{x}): got {got[b, c, y, x]!r} "
+                            f"ref {ref[b, c, y, x]!r}; {len(bad)} element(s) differ")
+
+
+def _frame(frames, b):
+    return b if frames is None else frames[b]
+
+
+def bound_of(M: np.ndarray, kappa: float) -> np.ndarray:
+    return kappa * U * M + FLOOR
+
+
+# ───────────────────────────── the whole net, layer by layer ─────────────────────────────
+
+
+def layer_names(L: int):
+    """Tap names in chain order (the names of ``og_unet_get_activation``)."""
+    out = []
+    for i in range(L):
+        out += [f"downs.{i}.a", f"downs.{i}.b", f"pool{i}"]
+    out += ["bottleneck.a", "bottleneck.b"]
+    for j in range(L):
+        out += [f"ups.{2 * j}", f"ups.{2 * j + 1}.a", f"ups.{2 * j + 1}.b"]
+    return out
+
+
+def check_net(sd: dict, gray: np.ndarray, get, logits: np.ndarray, kappa: dict, frames=None, mask=None, area=None,
+              threshold: float = 0.5, fused_first: bool = False, fused_head: bool = False, tile=(16, 16)) -> dict:
+    """Every layer tensor of one forward against its float64 reference computed from the GPU's own input.
+
+    ``get(name)`` returns the GPU's tap ``[B,C,H,W]`` (the frames of ``gray``); ``logits`` ``[B,H,W]``; ``kappa`` maps the op kind
+    (``first``, ``conv3``, ``convt``, ``head``) to the form's kappa.  ``fused_first``: ``downs.0.a`` was never stored, ``downs.0.b``
+    is checked against the composed reference.  ``fused_head``: ``ups.N.b`` was never stored, the logits are checked against the
+    composed reference.  ``mask`` / ``area``: checked exactly against the GPU's own logits.  Returns {layer: worst |err| / bound}.
+    """
+    L = n_levels(sd)
+    worst = {}
+    cache = {}
+
+    def tap(n):
+        if n not in cache:
+            cache[n] = np.asarray(get(n), dtype=np.float64)
+        return cache[n]
+
+    def dc(prefix, x_in, idx):
+        return conv3_bn_relu(sd, f"{prefix}.net.{idx}.weight", f"{prefix}.net.{idx + 1}", x_in)
+
+    x0 = first_input(gray)
+    for i in range(L):
+        p = f"downs.{i}"
+        if i == 0:
+            ref_a, _, M_a = dc(p, x0, 0)
+            b_a = bound_of(M_a, kappa["first"])
+            if fused_first:   # downs.0.b from the frames: own bound + |s| conv(bound_a, |w|)
+                ref_b, _, M_b = dc(p, ref_a, 3)
+                s, _, _ = fold_bn(sd, p + ".net.4")
+                bnd = bound_of(M_b, kappa["conv3"]) + np.abs(s)[None, :, None, None] * conv3_raw(b_a, np.abs(sd[p + ".net.3.weight"]))
+                worst[p + ".b (fused first)"] = check(p + ".b (fused with the first layer)", tap(p + ".b"), ref_b, bnd, frames, tile)
+            else:
+                worst[p + ".a"] = check(p + ".a", tap(p + ".a"), ref_a, b_a, frames, tile)
+        else:
+            ref_a, _, M_a = dc(p, tap(f"pool{i - 1}"), 0)
+            worst[p + ".a"] = check(p + ".a", tap(p + ".a"), ref_a, bound_of(M_a, kappa["conv3"]), frames, tile)
+        if not (i == 0 and fused_first):
+            ref_b, _, M_b = dc(p, tap(p + ".a"), 3)
+            worst[p + ".b"] = check(p + ".b", tap(p + ".b"), ref_b, bound_of(M_b, kappa["conv3"]), frames, tile)
+        check_exact(f"pool{i}", tap(f"pool{i}"), maxpool2(tap(p + ".b")), frames)
+        worst[f"pool{i}"] = 0.0
+    ref, _, M = dc("bottleneck", tap(f"pool{L - 1}"), 0)
+    worst["bottleneck.a"] = check("bottleneck.a", tap("bottleneck.a"), ref, bound_of(M, kappa["conv3"]), frames, tile)
+    ref, _, M = dc("bottleneck", tap("bottleneck.a"), 3)
+    worst["bottleneck.b"] = check("bottleneck.b", tap("bottleneck.b"), ref, bound_of(M, kappa["conv3"]), frames, tile)
+    for j in range(L):
+        i = L - 1 - j
+        src = "bottleneck.b" if j == 0 else f"ups.{2 * j - 1}.b"
+        ref, M = convt(sd, f"ups.{2 * j}", tap(src))
+        n = f"ups.{2 * j}"
+        worst[n] = check(n, tap(n), ref, bound_of(M, kappa["convt"]), frames, tile)
+        p = f"ups.{2 * j + 1}"
+        cat = np.concatenate([tap(f"downs.{i}.b"), tap(n)], axis=1)      # skip first (unet.py:86)
+        ref, _, M = dc(p, cat, 0)
+        worst[p + ".a"] = check(p + ".a", tap(p + ".a"), ref, bound_of(M, kappa["conv3"]), frames, tile)
+        ref_b, _, M_b = dc(p, tap(p + ".a"), 3)
+        if j == L - 1 and fused_head:   # logits from ups.N.a: own bound + |w_head| . bound_b
+            b_b = bound_of(M_b, kappa["conv3"])
+            ref_h, M_h = head(sd, ref_b)
+            bnd = bound_of(M_h, kappa["head"]) + head_abs(sd, b_b)
+            worst["head (fused)"] = check("head (fused with the last conv)", logits[:, None], ref_h, bnd, frames, tile)
+        else:
+            worst[p + ".b"] = check(p + ".b", tap(p + ".b"), ref_b, bound_of(M_b, kappa["conv3"]), frames, tile)
+    if not fused_head:
+        ref_h, M_h = head(sd, tap(f"ups.{2 * L - 1}.b"))
+        worst["head"] = check("head", logits[:, None], ref_h, bound_of(M_h, kappa["head"]), frames, tile)
+    if mask is not None:
+        check_mask(logits, mask, threshold, frames)
+    if area is not None:
+        assert mask is not None
+        exp = (np.asarray(mask) > 0).reshape(len(mask), -1).sum(1)
+        assert np.array_equal(np.asarray(area), exp), ("area is not the popcount of the mask", area, exp)
+    return worst
+
+
+def head_abs(sd: dict, x: np.ndarray) -> np.ndarray:
+    w = np.abs(sd["head.weight"][:, :, 0, 0].astype(np.float64))
+    return np.einsum("oc,bchw->bohw", w, x)
+
+
+def check_mask(logits: np.ndarray, mask: np.ndarray, threshold: float, frames=None, band: float = 2.0 ** -22) -> int:
+    """mask > 0 must equal logit > logit(threshold) -- on the GPU's own logits, bit for bit -- except within ``band`` of the
+    threshold logit, where the kernels' f32 sigmoid (1 / (1 + expf(-v)) > thr, the reference's rule) rounds to thr itself
+    (at thr 0.5: any 0 < v < 2^-25 gives exactly 0.5).  Returns the number of pixels inside the band."""
+    lg = np.asarray(logits, dtype=np.float64)
+    t = float(np.log(threshold / (1.0 - threshold)))
+    want = lg > t
+    near = np.abs(lg - t) <= band * max(1.0, abs(t))
+    bad = np.argwhere(((np.asarray(mask) > 0) != want) & ~near)
+    if len(bad):
+        b, y, x = (int(v) for v in bad[0])
+        raise LayerMismatch(f"mask: frame {_frame(frames, b)} (y,x)=({y},{x}) mask {int(mask[b, y, x])} logit {lg[b, y, x]!r} "
+                            f"threshold logit {t!r}; {len(bad)} pixel(s) differ")
+    return int(near.sum())
+
+
+# ───────────────────────────── f32 emulations of the kernel forms (κ derivation) ─────────────────────────────
+
+_BT = np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], dtype=np.float64)
+_G = np.array([[1, 0, 0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0, 0, 1]], dtype=np.float64)
+_AT = np.array([[1, 1, 1, 0], [0, 1, -1, -1]], dtype=np.float64)
+
+
+def _f32(v):
+    return np.asarray(v, dtype=np.float32)
+
+
+def _bt_axis(d, axis):
+    """B^T along one axis of a [..4..] f32 array, one f32 rounding per add / subtract (the kernels' x[ia] +- x[ib])."""
+    t = np.moveaxis(d, axis, 0)
+    out = np.stack([t[0] - t[2], t[1] + t[2], t[2] - t[1], t[1] - t[3]])
+    return np.moveaxis(out.astype(np.float32), 0, axis)
+
+
+def _at_axis(m, axis):
+    t = np.moveaxis(m, axis, 0)
+    out = np.stack([(t[0] + t[1]) + t[2], (t[1] - t[2]) - t[3]])
+    return np.moveaxis(out.astype(np.float32), 0, axis)
+
+
+def wino_transform_weights(w: np.ndarray) -> np.ndarray:
+    """U = G g G^T per (co, ci), float64, rounded once to f32 (as the host packs it): [Co,Ci,4,4]."""
+    return _f32(np.einsum("ij,ocjk,lk->ocil", _G, w.astype(np.float64), _G))
+
+
+def wino_f32(x: np.ndarray, w: np.ndarray, s: np.ndarray, shift: np.ndarray, relu: bool = True, U_w=None) -> np.ndarray:
+    """numpy f32 emulation of a k_conv_wino* launch: conv3x3 (pad 1) via F(2x2,3x3) + the fma epilogue (+ ReLU).
+    x [B,Ci,H,W] f32, w [Co,Ci,3,3]."""
+    B, Ci, H, W = x.shape
+    Co = w.shape[0]
+    th, tw = (H + 1) // 2, (W + 1) // 2                               # odd maps: the last window row / column reads padding
+    xp = np.zeros((B, Ci, 2 * th + 2, 2 * tw + 2), np.float32)
+    xp[:, :, 1:H + 1, 1:W + 1] = x
+    d = np.empty((B, Ci, th, tw, 4, 4), np.float32)
+    for i in range(4):
+        for j in range(4):
+            d[..., i, j] = xp[:, :, i:i + 2 * th:2, j:j + 2 * tw:2]
+    V = _bt_axis(_bt_axis(d, 4), 5)                                   # [B,Ci,th,tw,4,4]
+    Uw = wino_transform_weights(w) if U_w is None else U_w            # [Co,Ci,4,4]
+    acc = np.zeros((B, Co, th, tw, 4, 4), np.float32)
+    for c in range(Ci):                                               # k-ordered f32 sum over the channels
+        prod = (Uw[None, :, c, None, None] * V[:, c, None]).astype(np.float32)
+        acc = (acc + prod).astype(np.float32)
+    Y = _at_axis(_at_axis(acc, 4), 5)                                 # [B,Co,th,tw,2,2]
+    y = Y.transpose(0, 1, 2, 4, 3, 5).reshape(B, Co, 2 * th, 2 * tw)[:, :, :H, :W]
+    out = (y * _f32(s)[None, :, None, None] + _f32(shift)[None, :, None, None]).astype(np.float32)
+    return np.maximum(out, 0).astype(np.float32) if relu else out
+
+
+def split_hilo(v: np.ndarray):
+    """v -> (hi, lo) f16 with v ~ hi + lo * 2^-11 (the kernels' split)."""
+    v = _f32(v)
+    hi = v.astype(np.float16)
+    lo = ((v - hi.astype(np.float32)) * np.float32(2048.0)).astype(np.float16)
+    return hi, lo
+
+
+def join_hilo(hi, lo) -> np.ndarray:
+    return (hi.astype(np.float32) + lo.astype(np.float32) * np.float32(1.0 / 2048.0)).astype(np.float32)
+
+
+def split_f32(x: np.ndarray, w: np.ndarray, s: np.ndarray, shift: np.ndarray, relu: bool = True, drop: str = "") -> np.ndarray:
+    """numpy emulation of a k_conv_mfma_h launch: x (a decoded hi / lo activation) and w split into f16 hi / lo, three products
+    (hi*hi, hi*lo, lo*hi; lo*lo dropped) summed in f32 per tap, the two correction products scaled by 2^-11 at the end, the fma
+    epilogue and the store as a hi / lo pair.  ``drop="a_lo_b_hi"`` omits the x_lo * w_hi product (a mutant)."""
+    B, Ci, H, W = x.shape
+    Co = w.shape[0]
+    xh, xl = split_hilo(x)
+    wh, wl = split_hilo(w)
+    xp_h = np.zeros((B, Ci, H + 2, W + 2), np.float32)
+    xp_l = np.zeros_like(xp_h)
+    xp_h[:, :, 1:-1, 1:-1] = xh.astype(np.float32)
+    xp_l[:, :, 1:-1, 1:-1] = xl.astype(np.float32)
+    acc = np.zeros((B, Co, H, W), np.float32)
+    cor = np.zeros((B, Co, H, W), np.float32)
+    whf, wlf = wh.astype(np.float32), wl.astype(np.float32)
+    for dy in range(3):
+        for dx in range(3):
+            ah = xp_h[:, :, dy:dy + H, dx:dx + W]
+            al = xp_l[:, :, dy:dy + H, dx:dx + W]
+            # f16 x f16 products are exact in f32; the sum over the channels in f32
+            acc = (acc + np.einsum("oc,bchw->bohw", whf[:, :, dy, dx], ah, dtype=np.float32)).astype(np.float32)
+            c = np.einsum("oc,bchw->bohw", wlf[:, :, dy, dx], ah, dtype=np.float32)
+            if drop != "a_lo_b_hi":
+                c = (c + np.einsum("oc,bchw->bohw", whf[:, :, dy, dx], al, dtype=np.float32)).astype(np.float32)
+            cor = (cor + c).astype(np.float32)
+    acc = (acc + cor * np.float32(1.0 / 2048.0)).astype(np.float32)
+    out = (acc * _f32(s)[None, :, None, None] + _f32(shift)[None, :, None, None]).astype(np.float32)
+    if relu:
+        out = np.maximum(out, 0).astype(np.float32)
+    return join_hilo(*split_hilo(out))
+
+
+# ───────────────────────────── special frames ─────────────────────────────
+
+
+def special_frames(H: int, W: int, seed: int = 0) -> dict:
+    """The frames every GPU case reads back: a quadrant mosaic of the four patterns (and their seams), random noise, all-0, all-255,
+    the 0/255 checkerboard (the worst case for the Winograd transforms' cancellation) and one-pixel stripes."""
+    yy, xx = np.mgrid[0:H, 0:W]
+    checker = (((yy + xx) & 1) * 255).astype(np.uint8)
+    stripes = ((xx & 1) * 255).astype(np.uint8)
+    zeros = np.zeros((H, W), np.uint8)
+    full = np.full((H, W), 255, np.uint8)
+    mosaic = zeros.copy()
+    h2, w2 = H // 2, W // 2
+    mosaic[:h2, w2:] = 255
+    mosaic[h2:, :w2] = checker[h2:, :w2]
+    mosaic[h2:, w2:] = ((yy[h2:, w2:] & 1) * 255).astype(np.uint8)     # horizontal stripes in the last quadrant
+    rnd = np.random.RandomState(seed).randint(0, 256, (H, W), dtype=np.uint8)
+    return {"mosaic": mosaic, "random": rnd, "zeros": zeros, "full": full, "checker": checker, "stripes": stripes}
+
+
+# ───────────────────────────── the GPU matrix (tests/test_gpu_layer_parity.py; its coverage is checked on the CPU) ─────────────────────────────
+
+FULL = (32, 64, 128, 256)
+
+
+def _case(cid, feats, H, W, B, options=None, families=(), form="wino", nread=2, fused_first=False, fused_head=False, prof=()):
+    opts = {"keep_taps": 1}
+    opts.update(options or {})
+    if not prof:   # every kernel family of the plan check is asserted through UNet.profile as well
+        prof = [f for f in families if f.startswith("k_") and f not in ("k_splitk_epilogue", "k_sum_counts")]
+    return dict(id=cid, feats=tuple(feats), H=H, W=W, B=B, options=opts, families=tuple(families), form=form, nread=min(nread, B),
+                fused_first=fused_first, fused_head=fused_head, prof=tuple(prof))
+
+
+# families: what og_unet_plan must list for the case (``plan_families``); prof: what UNet.profile must list (``profile_families``)
+GPU_CASES = [
+    _case("default-64", FULL, 256, 256, 64, {}, ["k_conv_wino", "k_conv_mfma_o"], prof=["k_conv_wino", "k_conv_mfma_o"]),
+    _case("default-1", FULL, 256, 256, 1, {}, ["k_conv_wino_w", "k_conv_wino_wp", "k_convt_w"], nread=1,
+          prof=["k_conv_wino_w", "k_conv_wino_wp", "k_convt_w"]),
+    _case("position-split-1", FULL, 256, 256, 1, {"wino_w": 0}, ["k_conv_wino_ps"], nread=1, prof=["k_conv_wino_ps"]),
+    _case("direct-64", FULL, 256, 256, 64, {"wino": 0}, ["k_conv_mfma_o"], form="direct", prof=["k_conv_mfma_o"]),
+    _case("direct-impl0-2", FULL, 256, 256, 2, {"wino": 0, "conv_impl": 0}, ["k_conv_mfma", "k_head"], form="direct",
+          prof=["k_conv_mfma", "k_head"]),
+    _case("direct-impl1-2", FULL, 256, 256, 2, {"wino": 0, "conv_impl": 1}, ["k_conv_mfma_p"], form="direct", prof=["k_conv_mfma_p"]),
+    _case("splitk-fused-1", FULL, 256, 256, 1, {"wino": 0, "splitk": 1}, ["k_conv_mfma_o", "splitk-parts", "splitk-fused-reduce"], form="direct", nread=1,
+          prof=["splitK"]),
+    _case("splitk-fused-2", FULL, 256, 256, 2, {"wino": 0, "splitk": 1}, ["k_conv_mfma_o", "splitk-parts", "splitk-fused-reduce"], form="direct",
+          prof=["splitK"]),
+    _case("splitk-epilogue-2", FULL, 256, 256, 2, {"wino": 0, "splitk": 1, "splitk_fused": 0}, ["splitk-parts", "k_splitk_epilogue"], form="direct",
+          prof=["splitK"]),
+    _case("splitk-nt1-0-steps9-1", FULL, 256, 256, 1, {"wino": 0, "splitk": 1, "splitk_nt1": 0, "splitk_min_steps": 9},
+          ["splitk-parts", "splitk-fused-reduce"], form="direct", nread=1, prof=["splitK"]),
+    _case("split-precision-64", FULL, 256, 256, 64, {"precision": 1}, ["k_conv_mfma_h"], form="split", prof=["k_conv_mfma_h"]),
+    _case("split-precision-1", FULL, 256, 256, 1, {"precision": 1}, ["k_conv_mfma_h"], form="split", nread=1, prof=["k_conv_mfma_h"]),
+    _case("split-precision-splitk-1", FULL, 256, 256, 1, {"precision": 1, "splitk": 1}, ["k_conv_mfma_h", "splitk-parts"],
+          form="split", nread=1, prof=["k_conv_mfma_h"]),
+    _case("fused-first-and-head-64", FULL, 256, 256, 64, {"wino": 0, "keep_taps": 0}, ["first-fused", "k_sum_counts"], form="direct",
+          fused_first=True, fused_head=True, prof=["first-fused"]),
+    _case("fused-head-wino-64", FULL, 256, 256, 64, {"keep_taps": 0}, ["k_conv_wino", "k_sum_counts"], fused_head=True,
+          prof=["k_conv_wino"]),
+    _case("unfused-head-2", FULL, 256, 256, 2, {"fuse_head": 0}, ["k_head"], prof=["k_head"]),
+    _case("tiles-128x256", (32, 64), 128, 256, 64, {}, ["k_conv_wino"], prof=["k_conv_wino"]),
+    _case("tiles-96x160", (32, 64), 96, 160, 16, {}, ["k_conv_wino"], nread=4, prof=["k_conv_wino"]),
+    _case("tiles-96x160-direct", (32, 64), 96, 160, 16, {"wino": 0}, ["k_conv_mfma_o"], form="direct", nread=4),
+    _case("padded-40x80-64x64", (40, 80), 64, 64, 8, {}, ["k_conv_wino_w", "k_head"], nread=6),
+    _case("padded-33x66-32x64", (33, 66), 32, 64, 4, {}, ["k_conv_wino_w", "k_conv_mfma_p", "k_head"], nread=4),
+    _case("padded-33x66-32x64-direct", (33, 66), 32, 64, 4, {"wino": 0}, ["k_conv_mfma_p"], form="direct", nread=4),
+    _case("bottleneck-1x1-16x16", (4, 8, 16, 32), 16, 16, 4, {}, ["k_conv_mfma_p", "k_convt_w"], nread=4),
+    _case("maps-1x16-16x256", (4, 8, 16, 32), 16, 256, 2, {}, ["k_conv_mfma_p"], nread=2),
+    _case("five-levels-64x96", (3, 6, 12, 24, 48), 64, 96, 4, {}, ["k_conv_wino_w", "k_conv_wino_wp", "k_conv_mfma_p"], nread=4),
+    _case("large-512x512", (32, 64), 512, 512, 8, {}, ["k_conv_wino"], nread=1),
+]
+
+
+def kappa_of(form: str) -> dict:
+    """kappa per op kind for a chain of the given form (the first layer, the transposed convs and the heads are direct in every
+    f32 chain; split precision runs every op through the hi / lo arithmetic)."""
+    k, d = KAPPA[form], KAPPA["direct"]
+    if form == "split":
+        return {"first": k, "conv3": k, "convt": k, "head": k}
+    return {"first": d, "conv3": k, "convt": d, "head": d}
+
+
+def option_string(options: dict) -> str:
+    return ",".join(f"{k}={v}" for k, v in options.items())
+
+
+def plan_families(recs, B: int) -> set:
+    """Kernel families of an og_unet_plan record list (``[{kernel, grid, ws, cnt, ...}]``) of a B-frame chain.  Pseudo-families:
+    ``first-fused`` (downs.0 with the first layer inside), ``splitk-parts`` (a conv launch with more grid.z slices than frames:
+    its K split over workgroups), ``splitk-fused-reduce`` (split parts with a workspace and arrival counters)."""
+    import re
+
+    out = set()
+    for r in recs:
+        k = r["kernel"]
+        m = re.match(r"\(?\s*(k_\w+)", k)
+        if m:
+            out.add(m.group(1))
+        if re.search(r"k_conv_mfma_[oh]<1, 0, 8, 3, true>", k):
+            out.add("first-fused")
+        if "k_conv_mfma" in k and r["grid"][2] > B:
+            out.add("splitk-parts")
+        if r["ws"] > 0 and r["cnt"] > 0 and "k_conv_mfma" in k:
+            out.add("splitk-fused-reduce")
+    return out
+
+
+def profile_families(prof) -> set:
+    """Kernel families of a ``UNet.profile`` list (its kernel names are the launch sites' labels)."""
+    import re
+
+    out = set()
+    for p in prof:
+        k = p["kernel"]
+        m = re.match(r"(k_\w+)", k)
+        if m:
+            out.add(m.group(1))
+        if "FIRST" in k:
+            out.add("first-fused")
+        if "+splitK" in k:
+            out.add("splitK")
+    return out

@@ -1,0 +1,62 @@
+"""GPU (-m gpu): every layer tensor of every kernel form against a float64 reference of that one op, computed from the GPU's OWN
+input tensor (oracle/layer_ref.py), at the precision the form's arithmetic reaches (kappa * 2^-24 * M per element).
+
+The matrix (``layer_ref.GPU_CASES``) covers the canonical Winograd kernels at full and one-frame occupancy, the position-split
+and wave-split forms, the direct kernels (occupancy, persistent, padded-channel), split K with the fused reduce and with the
+separate epilogue, split precision, the fused first layer and fused head (checked by composition) and the unfused head, at frame
+shapes where the tiles have edges.  Entry point: the u8 product path (``segment``).  The first ``nread`` frames of the (single)
+chunk are read back: the special frames of ``layer_ref.special_frames`` (a mosaic of all-0 / all-255 / checkerboard / stripes
+first, then random, all-0, all-255, checkerboard, stripes), the rest of the batch random.  The one-frame cases (nread 1) see
+the mosaic only: its quadrants keep the four patterns pure in the shallow layers, but the deep layers of the 256 x 256 chains mix
+them; the pure special frames are checked by the cases that read 3 or more frames (the 96 x 160, padded, 16 x 16 and five-level
+nets).  Which kernels ran is asserted through
+``UNet.profile`` here, and through ``og_unet_plan`` on the CPU (tests/test_layer_ref.py).
+"""
+import numpy as np
+import pytest
+
+import openglottal_amd as og
+from openglottal_amd import synth
+from oracle import layer_ref as R
+
+pytestmark = pytest.mark.gpu
+
+ORDER = ["mosaic", "random", "zeros", "full", "checker", "stripes"]
+
+
+def batch(H, W, B, seed=5):
+    sp = R.special_frames(H, W, seed=seed)
+    head = np.stack([sp[k] for k in ORDER])[:B]
+    if B <= len(head):
+        return np.ascontiguousarray(head)
+    return np.concatenate([head, synth.random_gray_frames(B - len(head), H, W, seed=seed + 1)])
+
+
+@pytest.mark.parametrize("case", R.GPU_CASES, ids=[c["id"] for c in R.GPU_CASES])
+def test_every_layer_against_float64(case):
+    import torch
+
+    feats, H, W, B, n = case["feats"], case["H"], case["W"], case["B"], case["nread"]
+    sd = synth.make_unet_state_dict(feats, seed=11, head_scale=3.0, head_bias=-0.5)
+    m = og.UNet(1, 1, feats)
+    m.load_state_dict(sd)
+    m.to("cuda:0").eval()
+    for k, v in case["options"].items():
+        m.set_option(k, v)
+    m.set_chunk(B)                    # one chunk: the activations read back are this batch's
+    gray = batch(H, W, B)
+    masks, areas, logits = m.segment(gray, want_logits=True)
+    taps = {}
+
+    def get(name):
+        if name not in taps:
+            taps[name] = m.activation(name, n)
+        return taps[name]
+
+    worst = R.check_net(sd, gray[:n], get, logits[:n], R.kappa_of(case["form"]), frames=[ORDER[i] if i < len(ORDER) else i for i in range(n)],
+                        mask=masks[:n], area=areas[:n], fused_first=case["fused_first"], fused_head=case["fused_head"])
+    assert np.array_equal(areas, (masks > 0).reshape(B, -1).sum(1))
+    fams = R.profile_families(m.profile(torch.from_numpy(gray).cuda(), B, H, W, reps=1))
+    assert set(case["prof"]) <= fams, (case["id"], sorted(set(case["prof"]) - fams), sorted(fams))
+    print(f"{case['id']} [{case['form']} kappa {R.KAPPA[case['form']]:g}] worst |err|/bound per layer: "
+          + " ".join(f"{k}={v:.3f}" for k, v in worst.items() if not k.startswith("pool")) + f"  (max {max(worst.values()):.3f})")

@@ -16,13 +16,16 @@ import pytest
 
 import openglottal_amd as og
 from openglottal_amd import synth
-from openglottal_amd.features import area_waveform, extract_features_unet
+from openglottal_amd.features import _kinematic_features, area_waveform, extract_features_unet
 
 pytestmark = pytest.mark.gpu
 
 import oracle
 
 TOL = oracle.reference_band()   # the reference's own run-to-run logit difference (tests/golden/unet_full128_self_noise.npz: 3.475e-5)
+# Split-K latency mode against the unsplit path and the fixture: the ABSOLUTE bound these checks held (and the GPU passed) before
+# commit 7a08550 re-scaled them to 2 * TOL * max(1, |logit|max) -- tens of times looser with logits of several units.
+SPLITK_ABS = 5e-5
 
 
 def unpack(bits, h=256, w=256):
@@ -121,7 +124,9 @@ def test_full_width_8_frames_masks_areas_logits(full):
     assert np.abs(samp - g["logits_samples"]).max() <= TOL
     assert np.abs(logits[[0, 4]] - g["logits_full"]).max() <= TOL
     ref_masks = np.stack([unpack(b) for b in g["masks_packed"]])
-    flips = check_masks(masks, lambda i, y, x: logits[i, y, x], ref_masks, g["areas"], areas)
+    from oracle import unet_oracle as O
+    _, ref_logits = O.segment_frames(sd, frames, backend="torch")     # the flip rule judges a pixel by the REFERENCE's logit
+    flips = check_masks(masks, lambda i, y, x: ref_logits[i, y, x], ref_masks, g["areas"], areas)
     print("full-width flipped pixels:", flips, "of", 8 * 65536, "areas", areas.tolist())
     for i in range(4):
         assert abs(og.dice(masks[4 + i], gt[i]) - float(g["dice_vs_gt"][i])) <= 1e-3
@@ -209,8 +214,7 @@ def test_split_k_latency_mode(trained, full):
     m.set_option("splitk", 0)
     m.set_option("wino", 1)
     assert not np.array_equal(l0, l1)                                                 # the split path really ran
-    scale = max(1.0, float(np.abs(l0).max()))
-    assert np.abs(l0 - l1).max() <= 2 * TOL * scale      # two of OUR summation orders against each other: each within the band of the reference
+    assert np.abs(l0 - l1).max() <= SPLITK_ABS, float(np.abs(l0 - l1).max())     # two of OUR summation orders against each other
     # fused reduce (last-arriving K part sums all parts in split order) == separate reduce kernel, bit for bit, every time
     mf.set_chunk(1)
     mf.set_option("splitk_fused", 0)
@@ -228,13 +232,15 @@ def test_split_k_latency_mode(trained, full):
         _, a_v, l_v = mf.segment(framesf, want_mask=False, want_logits=True)
         _, a_v2, l_v2 = mf.segment(framesf, want_mask=False, want_logits=True)
         assert np.array_equal(l_v, l_v2) and np.array_equal(a_v, a_v2)
-        assert np.abs(l_v - l0).max() <= 2 * TOL * scale, (nt1, steps)
+        assert np.abs(l_v - l0).max() <= SPLITK_ABS, (nt1, steps, float(np.abs(l_v - l0).max()))
     mf.set_option("splitk_nt1", 1)
     mf.set_option("splitk_min_steps", 3)
     mf.set_chunk(32)
     mf.set_option("splitk", 0)
     mf.set_option("wino", 1)
-    assert np.abs(l1.reshape(8, -1)[:, gf["sample_idx"]] - gf["logits_samples"]).max() <= TOL * max(1.0, float(np.abs(gf["logits_samples"]).max()))
+    err = float(np.abs(l1.reshape(8, -1)[:, gf["sample_idx"]] - gf["logits_samples"]).max())
+    print(f"split-K latency mode: max|l1 - fixture| = {err:.3g} (bound {SPLITK_ABS})")
+    assert err <= SPLITK_ABS, err
     assert np.all(np.abs(a0.astype(int) - a1.astype(int)) <= ((l0 > 0) != (l1 > 0)).reshape(8, -1).sum(1))
 
 
@@ -309,7 +315,18 @@ def test_extract_features_unet_matches_reference_kinematics(trained, golden_dir)
     for k, v in ref.items():
         assert (feats[k] is None) if v is None else abs(float(feats[k]) - v) <= 1e-12 * max(1, abs(v)), k
     assert extract_features_unet(np.zeros((0, 256, 256, 3), np.uint8), None, m) is None
-    assert extract_features_unet(np.full((5, 256, 256, 3), 255, np.uint8), None, m) in (None,) or True
+    white = np.full((5, 256, 256, 3), 255, np.uint8)
+    wave = np.asarray(area_waveform(white, None, m), dtype=np.float64)
+    assert wave.shape == (5,) and np.all(wave == wave[0]), wave                  # five identical frames, five identical areas
+    got, want = extract_features_unet(white, None, m), _kinematic_features([float(v) for v in wave])
+    assert (got is None) == (want is None), (got, want)
+    if want is not None:
+        assert set(got) == set(want)
+        for k, v in want.items():
+            if isinstance(v, np.ndarray):
+                assert np.array_equal(got[k], v), k
+            else:
+                assert (got[k] is None and v is None) or got[k] == v or (np.isnan(got[k]) and np.isnan(v)), (k, got[k], v)
 
 
 def test_oracle_random_shapes_and_odd_widths():

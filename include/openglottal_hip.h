@@ -108,6 +108,28 @@ int og_unet_stream_u8(og_unet* h, const uint8_t* frames, int B, int H, int W, in
  * no stacked copy of the video is ever made (a Python np.stack of 502 frames costs more than a fifth of the whole pass). */
 int og_unet_stream_frames_u8(og_unet* h, const uint8_t* const* frame_ptrs, int B, int H, int W, int channels, float threshold,
                              const int32_t* boxes, uint8_t* mask, int32_t* area);
+/* = unet_segment_frame (utils.py:218-241) for frames of ANY size H x W (1..8192 per side), streamed like og_unet_stream_u8:
+ * cv2.resize(u8 -> net_w x net_h, INTER_LINEAR) -> U-Net -> sigmoid -> cv2.resize(f32 -> W x H, INTER_LINEAR) -> > threshold, with
+ * BGR2GRAY (features.py:235) per tap for channels = 3, all on the device.  OpenCV's arithmetic as restated in
+ * openglottal_amd/geometry.py (parity against a real cv2 unpinned).  mask [B,H,W] u8 {0,255} and area [B] int32 at SOURCE size,
+ * boxes [B,4] in SOURCE coordinates (x1 < 0: no detection, area 0).  A frame already at net_h x net_w takes og_unet_stream_u8's
+ * chain unchanged (same bits).  net_h / net_w: multiples of 2^n_levels.  Source frames per micro-batch are capped at 64 MiB
+ * (the handle's chunk is lowered for large frames; results are per frame, so no bit changes); no zero copy.  Synchronous. */
+int og_unet_stream_resized_u8(og_unet* h, const uint8_t* frames, int B, int H, int W, int channels, int net_h, int net_w,
+                              float threshold, const int32_t* boxes, uint8_t* mask, int32_t* area);
+/* The list-of-frames twin (og_unet_stream_frames_u8): frame_ptrs[i] -> [H,W] gray or [H,W,3] BGR u8, contiguous. */
+int og_unet_stream_frames_resized_u8(og_unet* h, const uint8_t* const* frame_ptrs, int B, int H, int W, int channels, int net_h,
+                                     int net_w, float threshold, const int32_t* boxes, uint8_t* mask, int32_t* area);
+/* DEVICE pointers, asynchronous, one lane.  src [B,H,W,channels] u8; boxes / mask / area as above or NULL; the last three are
+ * optional debug outputs (NULL = not written): net_logits [B,net_h,net_w] f32, net_prob [B,net_h,net_w] f32 (sigmoid),
+ * prob [B,H,W] f32 (the resized probability the mask thresholds). */
+int og_unet_segment_resized_u8_dev(og_unet* h, const uint8_t* src_dev, int B, int H, int W, int channels, int net_h, int net_w,
+                                   float threshold, const int32_t* boxes_dev, uint8_t* mask_dev, int32_t* area_dev,
+                                   float* net_logits_dev, float* net_prob_dev, float* prob_dev);
+/* Host only: the INTER_LINEAR tap rule of both resize kernels for dst_len outputs from src_len inputs (geometry._linear_taps):
+ * i0 / i1 [dst_len] int32, frac [dst_len] f32, a1 [dst_len] int32 = the u8 path's 11-bit coefficient rint(frac * 2048). */
+int og_linear_taps_host(int src_len, int dst_len, int32_t* i0, int32_t* i1, float* frac_f32, int32_t* a1_i32);
+
 /* Same as og_unet_segment_u8, DEVICE pointers, asynchronous on the handle's stream. */
 int og_unet_segment_u8_dev(og_unet* h, const uint8_t* gray_dev, int B, int H, int W, float threshold,
                            const int32_t* boxes_dev, uint8_t* mask_dev, int32_t* area_dev, float* logits_dev);
@@ -243,6 +265,12 @@ double og_unet_flops_per_frame(og_unet* h, int H, int W);
  * machine without a GPU (tests/test_launch_plan.py), instead of being found by a faulting kernel. */
 int og_unet_plan(const int* features, int n_levels, int B, int H, int W, int lanes, const char* options, char* out, size_t cap,
                  long long* arena_bytes);
+/* og_unet_plan for og_unet_segment_resized_u8_dev over B frames of H x W x channels (every micro-batch, with k_resize_in and
+ * k_resize_out, every debug output asked for).  Each line carries a ninth field: the caller-owned buffers the launch writes and
+ * where its writes end, in bytes from the buffer's base ("mask=N;area=N;net_logits=N;net_prob=N;prob=N", "-" for none), so
+ * that the extents can be checked against B x H x W, 4 B, ... without a device (tests/test_resize_host.py). */
+int og_unet_plan_resized(const int* features, int n_levels, int B, int H, int W, int channels, int net_h, int net_w, int lanes,
+                         const char* options, char* out, size_t cap, long long* arena_bytes);
 /* which: 0 split-K / position-split workspace bytes per lane, 1 arrival counters per lane, 2 largest grid.y / grid.z, 3 LDS bytes per workgroup */
 long long og_workspace_limit(int which);
 

@@ -45,6 +45,13 @@ PROTOTYPES = {
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "og_unet_stream_frames_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "og_unet_stream_resized_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "og_unet_stream_frames_resized_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                   C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "og_unet_segment_resized_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "og_linear_taps_host": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "og_unet_segment_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "og_unet_segment_crops_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
@@ -74,6 +81,8 @@ PROTOTYPES = {
                                       C.POINTER(C.c_int)]),
     "og_unet_clock_probe_raw": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "og_unet_flops_per_frame": (C.c_double, [C.c_void_p, C.c_int, C.c_int]),
+    "og_unet_plan_resized": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
     "og_unet_plan": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_size_t,
                                C.POINTER(C.c_longlong)]),
     "og_workspace_limit": (C.c_longlong, [C.c_int]),

@@ -71,10 +71,12 @@ struct PlanRec {
     unsigned gx, gy, gz, block, lds;
     long long partial_bytes;
     long long counters;
+    std::string writes;   // og_unet_plan_resized: "buffer=end" per caller-owned buffer the launch writes (end = bytes from its base)
 };
 struct Plan {
     std::vector<PlanRec> recs;
     long long need_partial = 0, need_counters = 0;
+    std::map<std::string, const void*> bases;   // og_unet_plan_resized: placeholder base of each caller-owned buffer
 };
 thread_local Plan* g_plan = nullptr;
 inline void plan_need(long long partial_bytes, long long counters) {
@@ -84,8 +86,17 @@ inline void plan_need(long long partial_bytes, long long counters) {
     }
 }
 inline void plan_record(const char* kernel, dim3 grid, dim3 block, size_t lds) {
-    g_plan->recs.push_back({kernel, grid.x, grid.y, grid.z, block.x, (unsigned)lds, g_plan->need_partial, g_plan->need_counters});
+    g_plan->recs.push_back({kernel, grid.x, grid.y, grid.z, block.x, (unsigned)lds, g_plan->need_partial, g_plan->need_counters, ""});
     g_plan->need_partial = g_plan->need_counters = 0;
+}
+// the last recorded launch writes `bytes` into caller-owned buffer `name` starting at `p`: note where that ends, from the buffer's base
+inline void plan_write(const char* name, const void* p, long long bytes) {
+    if (!g_plan || !p || g_plan->recs.empty()) return;
+    auto it = g_plan->bases.find(name);
+    if (it == g_plan->bases.end()) return;
+    const long long end = (long long)((const char*)p - (const char*)it->second) + bytes;
+    std::string& w = g_plan->recs.back().writes;
+    w += (w.empty() ? "" : ";") + std::string(name) + "=" + std::to_string(end);
 }
 // every launch of the chain goes through here: a failed launch is reported as OG_EHIP by THIS call (not by a later one)
 #define OG_LAUNCH(kern, grid, block, lds, stream, ...)                                                    \
@@ -249,12 +260,14 @@ struct og_unet {
         uint8_t *d_in = nullptr, *d_gray = nullptr, *d_mask = nullptr, *h_in = nullptr, *h_mask = nullptr;
         int32_t *d_area = nullptr, *d_boxes = nullptr, *h_area = nullptr, *h_boxes = nullptr;
         float *d_logits = nullptr, *h_logits = nullptr;
+        float* d_net = nullptr;   // resized calls: the chain's logits at network size (d_gray is then at network size too)
         hipEvent_t ev_h2d = nullptr, ev_done = nullptr, ev_out = nullptr;
         int b0 = -1, nb = 0;   // micro-batch occupying the slot (-1: free)
     };
     struct Ring {
         std::vector<Slot> slots;
         int cap = 0, H = 0, W = 0, ch = 0;
+        int Hn = 0, Wn = 0;   // network size of resized calls (0: the chain runs at H x W)
         bool mask = false, logits = false;
         hipStream_t s_h2d = nullptr, s_d2h = nullptr;
     } ring;
@@ -1376,7 +1389,7 @@ int run_chunk(og_unet* h, int kind, const void* in, int B, int H, int W, float t
     // One short chain at a time (the per-frame call; one-frame chains on one lane): the host enqueues a launch in ~4 us and a kernel
     // runs ~13 us, so plain launches keep the GPU fed and a graph launch only adds its own latency (measured: 299.7 vs 305.5 us per
     // one-frame chain, unet_segment_frame 0.331 vs 0.342 ms).  Several lanes in flight need the graph: one host thread feeds them all.
-    const bool eager = !h->use_graphs || (h->active_lanes <= 1 && B <= 4);
+    const bool eager = g_plan || !h->use_graphs || (h->active_lanes <= 1 && B <= 4);   // (a dry run captures nothing)
     if (eager) {
         if ((rc = enqueue_body(h, B, fuse, ff))) return rc;
     } else {
@@ -1468,7 +1481,7 @@ void free_ring(og_unet* h) {
     if (r.s_h2d) (void)hipStreamSynchronize(r.s_h2d);
     if (r.s_d2h) (void)hipStreamSynchronize(r.s_d2h);
     for (auto& s : r.slots) {
-        for (void* p : {(void*)s.d_in, (void*)s.d_gray, (void*)s.d_mask, (void*)s.d_area, (void*)s.d_boxes, (void*)s.d_logits})
+        for (void* p : {(void*)s.d_in, (void*)s.d_gray, (void*)s.d_mask, (void*)s.d_area, (void*)s.d_boxes, (void*)s.d_logits, (void*)s.d_net})
             if (p) (void)hipFree(p);
         for (void* p : {(void*)s.h_in, (void*)s.h_mask, (void*)s.h_area, (void*)s.h_boxes, (void*)s.h_logits})
             if (p) (void)hipHostFree(p);
@@ -1482,12 +1495,14 @@ void free_ring(og_unet* h) {
     r.s_h2d = r.s_d2h = nullptr;
 }
 
-int ensure_ring(og_unet* h, int n_slots, int cap, int H, int W, int ch, bool mask, bool logits) {
+int ensure_ring(og_unet* h, int n_slots, int cap, int H, int W, int ch, bool mask, bool logits, int Hn = 0, int Wn = 0) {
     auto& r = h->ring;
-    if ((int)r.slots.size() >= n_slots && r.cap >= cap && r.H == H && r.W == W && r.ch >= ch && (r.mask || !mask) && (r.logits || !logits))
+    if ((int)r.slots.size() >= n_slots && r.cap >= cap && r.H == H && r.W == W && r.Hn == Hn && r.Wn == Wn && r.ch >= ch &&
+        (r.mask || !mask) && (r.logits || !logits))
         return OG_OK;
+    const bool same = r.H == H && r.W == W && r.Hn == Hn && r.Wn == Wn;
     const bool km = r.mask || mask, kl = r.logits || logits;   // keep what an earlier call needed
-    const int kch = r.ch > ch ? r.ch : ch, kcap = (r.H == H && r.W == W && r.cap > cap) ? r.cap : cap;
+    const int kch = r.ch > ch ? r.ch : ch, kcap = (same && r.cap > cap) ? r.cap : cap;
     const int ks = (int)r.slots.size() > n_slots ? (int)r.slots.size() : n_slots;
     for (og_unet* t = h; t; t = t->twin)
         if (t->stream) HIPCHK(hipStreamSynchronize(t->stream));
@@ -1499,7 +1514,12 @@ int ensure_ring(og_unet* h, int n_slots, int cap, int H, int W, int ch, bool mas
     for (auto& s : r.slots) {
         HIPCHK(hipMalloc((void**)&s.d_in, kcap * HW * kch));
         HIPCHK(hipHostMalloc((void**)&s.h_in, kcap * HW * kch, hipHostMallocDefault));
-        if (kch == 3) HIPCHK(hipMalloc((void**)&s.d_gray, kcap * HW));
+        if (Hn) {   // resized: gray and logits at network size, inputs and masks at source size
+            HIPCHK(hipMalloc((void**)&s.d_gray, kcap * (size_t)Hn * Wn));
+            HIPCHK(hipMalloc((void**)&s.d_net, kcap * (size_t)Hn * Wn * 4));
+        } else if (kch == 3) {
+            HIPCHK(hipMalloc((void**)&s.d_gray, kcap * HW));
+        }
         HIPCHK(hipMalloc((void**)&s.d_area, (size_t)kcap * 4));
         HIPCHK(hipHostMalloc((void**)&s.h_area, (size_t)kcap * 4, hipHostMallocDefault));
         HIPCHK(hipMalloc((void**)&s.d_boxes, (size_t)kcap * 16));
@@ -1520,6 +1540,8 @@ int ensure_ring(og_unet* h, int n_slots, int cap, int H, int W, int ch, bool mas
     r.H = H;
     r.W = W;
     r.ch = kch;
+    r.Hn = Hn;
+    r.Wn = Wn;
     r.mask = km;
     r.logits = kl;
     return OG_OK;
@@ -1535,6 +1557,93 @@ bool is_pinned_host(const void* p) {   // hipHostMalloc'd / hipHostRegister'ed (
 }
 
 inline size_t al256(size_t x) { return (x + 255) / 256 * 256; }
+
+// ---- frames of any size (og_unet_stream_resized_u8 / og_unet_segment_resized_u8_dev) ----
+// Bytes of SOURCE frames per micro-batch of a resized call: a ring slot holds cb x H x W x C input bytes (pinned and device) and
+// cb x H x W mask bytes, so large frames lower the frames per micro-batch instead of growing the ring (1080 x 1920 BGR: 10
+// frames).  A frame is never split: a single frame above the cap is a micro-batch of one (at most 8192^2 x 3 = 192 MiB).
+constexpr size_t kResizeSlotBytes = 64u << 20;
+constexpr int kResizeMaxSide = 8192;   // largest source (and network) side a resized call accepts
+
+int check_resized(og_unet* h, int B, int H, int W, int ch, int Hn, int Wn) {
+    if (!h) return fail(OG_EINVAL, "null handle");
+    if (!h->finalized) return fail(OG_ESTATE, "og_unet_finalize() has not been called");
+    if (B < 0 || H <= 0 || W <= 0) return fail(OG_EINVAL, "bad B/H/W");
+    if (Hn <= 0 || Wn <= 0) return fail(OG_EINVAL, "net_h and net_w must be positive");
+    if (H > kResizeMaxSide || W > kResizeMaxSide || Hn > kResizeMaxSide || Wn > kResizeMaxSide)
+        return fail(OG_EINVAL, "frame or network side above " + std::to_string(kResizeMaxSide));
+    if (ch != 1 && ch != 3) return fail(OG_EINVAL, "channels must be 1 (gray) or 3 (BGR)");
+    return check_shape(h, B, Hn, Wn);   // the network size must be a multiple of 2^n_levels
+}
+
+// frames per micro-batch of a resized call: the handle's chunk, lowered to the byte cap of a slot's source frames
+int resized_chunk(const og_unet* h, int H, int W, int ch) {
+    const int chunk = effective_chunk(h);
+    const long long per = (long long)H * W * ch, fit = (long long)(kResizeSlotBytes / (size_t)per);
+    return fit < 1 ? 1 : (fit < chunk ? (int)fit : chunk);
+}
+
+// source u8 [nb,H,W,ch] -> gray u8 [nb,Hn,Wn] (the input k_conv_first<u8> reads)
+int enqueue_resize_in(hipStream_t st, int ch, const uint8_t* src, int nb, int H, int W, int Hn, int Wn, uint8_t* gray) {
+    const dim3 grid((unsigned)((Hn * Wn + 255) / 256), (unsigned)nb);
+    if (ch == 3)
+        OG_LAUNCH(k_resize_in<3>, grid, dim3(256), 0, st, src, H, W, Hn, Wn, gray);
+    else
+        OG_LAUNCH(k_resize_in<1>, grid, dim3(256), 0, st, src, H, W, Hn, Wn, gray);
+    return OG_OK;
+}
+
+// net logits f32 [nb,Hn,Wn] -> mask / area (inside boxes) / net_prob / prob at source size; area must be zero on entry
+int enqueue_resize_out(hipStream_t st, const float* logits, int nb, int Hn, int Wn, int H, int W, float thr, const int32_t* boxes,
+                       uint8_t* mask, int32_t* area, float* net_prob, float* prob) {
+    const int n = H * W > Hn * Wn ? H * W : Hn * Wn;
+    const dim3 grid((unsigned)((n + 255) / 256), (unsigned)nb);
+    OG_LAUNCH(k_resize_out, grid, dim3(256), 0, st, logits, Hn, Wn, H, W, thr, boxes, mask, area, net_prob, prob);
+    if (g_plan) {   // extents from the launch's own geometry: grid.y frames from each pointer
+        plan_write("mask", mask, (long long)grid.y * H * W);
+        plan_write("area", area, (long long)grid.y * 4);
+        plan_write("net_prob", net_prob, (long long)grid.y * Hn * Wn * 4);
+        plan_write("prob", prob, (long long)grid.y * H * W * 4);
+    }
+    return OG_OK;
+}
+
+// og_unet_segment_resized_u8_dev after its argument checks, on the handle's own lane (also walked by og_unet_plan_resized, where
+// `scratch` is a placeholder).  scratch: cb x Hn x Wn gray bytes (al256), then cb x Hn x Wn f32 logits when net_logits is null.
+int resized_dev_run(og_unet* h, const uint8_t* src, int B, int H, int W, int ch, int Hn, int Wn, float thr, const int32_t* boxes,
+                    uint8_t* mask, int32_t* area, float* net_logits, float* net_prob, float* prob, int chunk, char* scratch) {
+    const bool ident = H == Hn && W == Wn;   // the existing chain, head included: its bits (k_resize_in is then a copy / BGR2GRAY)
+    const size_t HW = (size_t)H * W, HWn = (size_t)Hn * Wn;
+    uint8_t* s_gray = (uint8_t*)scratch;
+    float* s_logits = (float*)(scratch + al256((size_t)chunk * HWn));
+    int rc = OG_OK;
+    for (int b0 = 0; b0 < B && !rc; b0 += chunk) {
+        const int nb = (B - b0 < chunk) ? B - b0 : chunk;
+        const uint8_t* in = src + (size_t)b0 * HW * ch;
+        const uint8_t* gray = in;
+        if (!(ident && ch == 1)) {
+            if ((rc = enqueue_resize_in(h->stream, ch, in, nb, H, W, Hn, Wn, s_gray))) break;
+            gray = s_gray;
+        }
+        float* lg = net_logits ? net_logits + (size_t)b0 * HWn : s_logits;
+        const int32_t* bx = boxes ? boxes + 4 * (size_t)b0 : nullptr;
+        uint8_t* mk = mask ? mask + (size_t)b0 * HW : nullptr;
+        int32_t* ar = area ? area + b0 : nullptr;
+        float* np_ = net_prob ? net_prob + (size_t)b0 * HWn : nullptr;
+        float* pr = prob ? prob + (size_t)b0 * HW : nullptr;
+        if ((rc = ident ? run_chunk(h, KIND_U8, gray, nb, Hn, Wn, thr, bx, mk, ar, lg)
+                        : run_chunk(h, KIND_U8, gray, nb, Hn, Wn, thr, nullptr, nullptr, nullptr, lg)))
+            break;
+        if (g_plan && ident) {   // the chain's head writes the caller's outputs of these nb frames
+            plan_write("mask", mk, (long long)nb * HW);
+            plan_write("area", ar, (long long)nb * 4);
+        }
+        if (g_plan) plan_write("net_logits", net_logits ? lg : nullptr, (long long)nb * HWn * 4);
+        if (!ident) rc = enqueue_resize_out(h->stream, lg, nb, Hn, Wn, H, W, thr, bx, mk, ar, np_, pr);
+        else if (np_ || pr) rc = enqueue_resize_out(h->stream, lg, nb, Hn, Wn, H, W, thr, nullptr, nullptr, nullptr, np_, pr);
+    }
+    return rc;
+}
 
 }  // namespace
 
@@ -1989,10 +2098,15 @@ int og_unet_segment_u8_dev(og_unet* h, const uint8_t* gray, int B, int H, int W,
 }
 
 // The frame loop with the video on the HOST (features.py:226,234-245), streamed: see og_unet::Ring.
+// Hn > 0 (resized call, frames of H x W != Hn x Wn): per micro-batch the source frames go up into the slot, k_resize_in writes the
+// network-size gray frames (it replaces k_bgr2gray), the chain runs at Hn x Wn with its logits in the slot, and k_resize_out writes
+// mask and area at source size; the micro-batch is lowered to kResizeSlotBytes of source frames.  Zero copy stays off for these calls
+// (the chain does not read the caller's frames: k_resize_in does, and the resize pair is not written for host-mapped buffers).
 static int stream_impl(og_unet* h, const uint8_t* frames, const uint8_t* const* frame_ptrs, int B, int H, int W, int ch, float thr,
-                       const int32_t* boxes, uint8_t* mask, int32_t* area, float* logits) {
+                       const int32_t* boxes, uint8_t* mask, int32_t* area, float* logits, int Hn = 0, int Wn = 0) {
     OG_SCOPE(h);
-    int rc = check_shape(h, B, H, W);
+    const bool rs = Hn > 0;
+    int rc = rs ? check_resized(h, B, H, W, ch, Hn, Wn) : check_shape(h, B, H, W);
     if (rc) return rc;
     if (ch != 1 && ch != 3) return fail(OG_EINVAL, "channels must be 1 (gray) or 3 (BGR)");
     if (B == 0) return OG_OK;
@@ -2000,7 +2114,9 @@ static int stream_impl(og_unet* h, const uint8_t* frames, const uint8_t* const* 
     if (frame_ptrs)
         for (int i = 0; i < B; ++i)
             if (!frame_ptrs[i]) return fail(OG_EINVAL, "frame_ptrs[" + std::to_string(i) + "] is null");
-    const int chunk = effective_chunk(h);
+    if (rs) logits = nullptr;
+    const int cH = rs ? Hn : H, cW = rs ? Wn : W;   // the chain's frame size
+    const int chunk = rs ? resized_chunk(h, H, W, ch) : effective_chunk(h);
     const int cb = chunk < B ? chunk : B;
     const int n_chunks = (B + chunk - 1) / chunk;
     og_unet* lanes[kMaxLanes] = {h};
@@ -2009,10 +2125,10 @@ static int stream_impl(og_unet* h, const uint8_t* frames, const uint8_t* const* 
     if (h->dual)
         for (og_unet* t = h->twin; t && n_lanes < want && n_lanes < n_chunks; t = t->twin) lanes[n_lanes++] = t;
     for (int l = 0; l < n_lanes; ++l)
-        if ((rc = ensure_arena(lanes[l], cb, H, W))) return rc;
+        if ((rc = ensure_arena(lanes[l], cb, cH, cW))) return rc;
     for (int l = 0; l < n_lanes; ++l) lanes[l]->active_lanes = n_lanes;
     const int n_slots = (n_chunks < n_lanes + 2) ? n_chunks : n_lanes + 2;   // one being filled, one per lane computing, one draining
-    if ((rc = ensure_ring(h, n_slots, cb, H, W, ch, mask != nullptr, logits != nullptr))) return rc;
+    if ((rc = ensure_ring(h, n_slots, cb, H, W, ch, mask != nullptr, logits != nullptr, rs ? Hn : 0, rs ? Wn : 0))) return rc;
     auto& R = h->ring;
     const size_t HW = (size_t)H * W, fb = HW * ch;
     const bool pinned = frames != nullptr && is_pinned_host(frames);
@@ -2044,7 +2160,7 @@ static int stream_impl(og_unet* h, const uint8_t* frames, const uint8_t* const* 
         // one stream there is, more than moving 64 KB costs.  So the kernels read the frame from, and write the mask / area to, the
         // slot's PINNED host buffers directly (mapped into the device's address space; the writes are visible to the host once the
         // completion event has fired): no H2D, no D2H, no memset command.
-        bool zc = single && nb <= 4 && h->zero_copy && !logits && (src == s.h_in || pinned);
+        bool zc = !rs && single && nb <= 4 && h->zero_copy && !logits && (src == s.h_in || pinned);
         uint8_t* z_in = nullptr;
         uint8_t* z_mask = nullptr;
         int32_t* z_area = nullptr;
@@ -2070,17 +2186,26 @@ static int stream_impl(og_unet* h, const uint8_t* frames, const uint8_t* const* 
             HIPCHK(hipStreamWaitEvent(lane->stream, s.ev_h2d, 0));
         }
         const uint8_t* gray = zc ? z_in : s.d_in;
-        if (ch == 3) {   // cv2.cvtColor(frm_bgr, COLOR_BGR2GRAY) of features.py:235, on the device, in front of the chain
+        if (rs) {
+            if (area) HIPCHK(hipMemsetAsync(s.d_area, 0, (size_t)nb * 4, lane->stream));
+            int rc2 = enqueue_resize_in(lane->stream, ch, s.d_in, nb, H, W, Hn, Wn, s.d_gray);
+            if (!rc2) rc2 = run_chunk(lane, KIND_U8, s.d_gray, nb, Hn, Wn, thr, nullptr, nullptr, nullptr, s.d_net);
+            if (!rc2) rc2 = enqueue_resize_out(lane->stream, s.d_net, nb, Hn, Wn, H, W, thr, boxes ? s.d_boxes : nullptr,
+                                               mask ? s.d_mask : nullptr, area ? s.d_area : nullptr, nullptr, nullptr);
+            if (rc2) return rc2;
+        } else if (ch == 3) {   // cv2.cvtColor(frm_bgr, COLOR_BGR2GRAY) of features.py:235, on the device, in front of the chain
             const long long n = (long long)nb * H * W;
             hipLaunchKernelGGL(k_bgr2gray, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lane->stream, gray, s.d_gray, n);
             HIPCHK(hipGetLastError());
             gray = s.d_gray;
         }
-        if (area && !zc) HIPCHK(hipMemsetAsync(s.d_area, 0, (size_t)nb * 4, lane->stream));
-        int rc2 = zc ? run_chunk(lane, KIND_U8, gray, nb, H, W, thr, z_boxes, z_mask, z_area, nullptr)
-                     : run_chunk(lane, KIND_U8, gray, nb, H, W, thr, boxes ? s.d_boxes : nullptr, mask ? s.d_mask : nullptr,
-                                 area ? s.d_area : nullptr, logits ? s.d_logits : nullptr);
-        if (rc2) return rc2;
+        if (!rs) {
+            if (area && !zc) HIPCHK(hipMemsetAsync(s.d_area, 0, (size_t)nb * 4, lane->stream));
+            int rc2 = zc ? run_chunk(lane, KIND_U8, gray, nb, H, W, thr, z_boxes, z_mask, z_area, nullptr)
+                         : run_chunk(lane, KIND_U8, gray, nb, H, W, thr, boxes ? s.d_boxes : nullptr, mask ? s.d_mask : nullptr,
+                                     area ? s.d_area : nullptr, logits ? s.d_logits : nullptr);
+            if (rc2) return rc2;
+        }
         if (zc) {
             HIPCHK(hipEventRecord(s.ev_out, s_out));
             s.b0 = b0;
@@ -2133,6 +2258,58 @@ int og_unet_stream_frames_u8(og_unet* h, const uint8_t* const* frame_ptrs, int B
                              const int32_t* boxes, uint8_t* mask, int32_t* area) {
     if (!frame_ptrs && B > 0) return fail(OG_EINVAL, "frame_ptrs is null");
     return stream_impl(h, nullptr, frame_ptrs, B, H, W, channels, thr, boxes, mask, area, nullptr);
+}
+
+int og_unet_stream_resized_u8(og_unet* h, const uint8_t* frames, int B, int H, int W, int channels, int net_h, int net_w, float thr,
+                              const int32_t* boxes, uint8_t* mask, int32_t* area) {
+    if (H == net_h && W == net_w && H > 0 && W > 0 && H <= kResizeMaxSide && W <= kResizeMaxSide)   // already at network size
+        return stream_impl(h, frames, nullptr, B, H, W, channels, thr, boxes, mask, area, nullptr);
+    return stream_impl(h, frames, nullptr, B, H, W, channels, thr, boxes, mask, area, nullptr, net_h, net_w);
+}
+
+int og_unet_stream_frames_resized_u8(og_unet* h, const uint8_t* const* frame_ptrs, int B, int H, int W, int channels, int net_h,
+                                     int net_w, float thr, const int32_t* boxes, uint8_t* mask, int32_t* area) {
+    if (!frame_ptrs && B > 0) return fail(OG_EINVAL, "frame_ptrs is null");
+    if (H == net_h && W == net_w && H > 0 && W > 0 && H <= kResizeMaxSide && W <= kResizeMaxSide)
+        return stream_impl(h, nullptr, frame_ptrs, B, H, W, channels, thr, boxes, mask, area, nullptr);
+    return stream_impl(h, nullptr, frame_ptrs, B, H, W, channels, thr, boxes, mask, area, nullptr, net_h, net_w);
+}
+
+int og_unet_segment_resized_u8_dev(og_unet* h, const uint8_t* src, int B, int H, int W, int channels, int net_h, int net_w, float thr,
+                                   const int32_t* boxes, uint8_t* mask, int32_t* area, float* net_logits, float* net_prob, float* prob) {
+    OG_SCOPE(h);
+    int rc = check_resized(h, B, H, W, channels, net_h, net_w);
+    if (rc) return rc;
+    if (!src && B > 0) return fail(OG_EINVAL, "src is null");
+    if (B == 0) return OG_OK;
+    const int chunk = resized_chunk(h, H, W, channels), cb = chunk < B ? chunk : B;
+    const size_t HWn = (size_t)net_h * net_w;
+    if ((rc = ensure_arena(h, cb, net_h, net_w))) return rc;
+    if ((rc = ensure_stage(h, al256((size_t)cb * HWn) + (net_logits ? 0 : al256((size_t)cb * HWn * 4))))) return rc;
+    h->active_lanes = 1;
+    if (area) HIPCHK(hipMemsetAsync(area, 0, (size_t)B * sizeof(int32_t), h->stream));
+    rc = resized_dev_run(h, src, B, H, W, channels, net_h, net_w, thr, boxes, mask, area, net_logits, net_prob, prob, cb, (char*)h->stage);
+    if (rc) {
+        const std::string err = g_err;
+        reset_counters(h);
+        (void)hipStreamSynchronize(h->stream);   // error path only: nothing of this call is in flight when the error is reported
+        g_err = err;
+    }
+    return rc;
+}
+
+int og_linear_taps_host(int src_len, int dst_len, int32_t* i0, int32_t* i1, float* frac, int32_t* a1) {
+    if (src_len <= 0 || dst_len <= 0 || !i0 || !i1 || !frac || !a1) return fail(OG_EINVAL, "bad argument");
+    for (int d = 0; d < dst_len; ++d) {
+        int k0, k1;
+        float f;
+        og_linear_pos(d, src_len, dst_len, k0, k1, f);
+        i0[d] = k0;
+        i1[d] = k1;
+        frac[d] = f;
+        a1[d] = og_linear_coef(f);
+    }
+    return OG_OK;
 }
 
 int og_unet_segment_u8(og_unet* h, const uint8_t* gray, int B, int H, int W, float thr, const int32_t* boxes,
@@ -2558,6 +2735,56 @@ int og_unet_plan(const int* features, int n_levels, int B, int H, int W, int lan
     for (auto& r : plan.recs)
         txt += r.kernel + "|" + std::to_string(r.gx) + "|" + std::to_string(r.gy) + "|" + std::to_string(r.gz) + "|" + std::to_string(r.block) + "|" +
                std::to_string(r.lds) + "|" + std::to_string(r.partial_bytes) + "|" + std::to_string(r.counters) + "\n";
+    if (txt.size() + 1 > cap) return fail(OG_EINVAL, "plan text does not fit the buffer");
+    memcpy(out, txt.c_str(), txt.size() + 1);
+    return (int)plan.recs.size();
+}
+
+int og_unet_plan_resized(const int* features, int n_levels, int B, int H, int W, int channels, int net_h, int net_w, int lanes,
+                         const char* options, char* out, size_t cap, long long* arena_bytes) {
+    if (!out || cap == 0 || B < 1) return fail(OG_EINVAL, "bad argument");
+    og_unet* h = og_unet_create(features, n_levels, 1, 1);
+    if (!h) return OG_EINVAL;
+    h->host_only = true;
+    int rc = og_unet_finalize(h);
+    if (!rc) rc = check_resized(h, B, H, W, channels, net_h, net_w);
+    std::string opt = options ? options : "";
+    for (size_t p0 = 0; !rc && p0 < opt.size();) {   // "name=value,name=value"
+        size_t p1 = opt.find(',', p0);
+        if (p1 == std::string::npos) p1 = opt.size();
+        const std::string kv = opt.substr(p0, p1 - p0);
+        const size_t eq = kv.find('=');
+        if (eq == std::string::npos) rc = fail(OG_EINVAL, "option without '=': " + kv);
+        else rc = og_unet_set_option(h, kv.substr(0, eq).c_str(), atoi(kv.c_str() + eq + 1));
+        p0 = p1 + 1;
+    }
+    Plan plan;
+    if (!rc) {
+        const int chunk = resized_chunk(h, H, W, channels), cb = chunk < B ? chunk : B;
+        ArenaPlan ap = arena_layout(h, cb, net_h, net_w);
+        if (arena_bytes) *arena_bytes = (long long)ap.total;
+        adopt_arena(h, ap, (void*)4096, cb, net_h, net_w);   // placeholder bases: nothing dereferences them in a dry run
+        h->active_lanes = lanes < 1 ? 1 : lanes;
+        // og_unet_segment_resized_u8_dev with every caller-owned output asked for, each at its own placeholder base
+        const uintptr_t gap = (uintptr_t)1 << 40;
+        uint8_t* mask = (uint8_t*)(1 * gap);
+        int32_t* area = (int32_t*)(2 * gap);
+        float* net_logits = (float*)(3 * gap);
+        float* net_prob = (float*)(4 * gap);
+        float* prob = (float*)(5 * gap);
+        plan.bases = {{"mask", mask}, {"area", area}, {"net_logits", net_logits}, {"net_prob", net_prob}, {"prob", prob}};
+        g_plan = &plan;
+        rc = resized_dev_run(h, (const uint8_t*)(6 * gap), B, H, W, channels, net_h, net_w, 0.5f, (const int32_t*)(7 * gap), mask, area,
+                             net_logits, net_prob, prob, cb, (char*)(8 * gap));
+        g_plan = nullptr;
+    }
+    og_unet_destroy(h);
+    if (rc) return rc;
+    std::string txt;
+    for (auto& r : plan.recs)
+        txt += r.kernel + "|" + std::to_string(r.gx) + "|" + std::to_string(r.gy) + "|" + std::to_string(r.gz) + "|" + std::to_string(r.block) + "|" +
+               std::to_string(r.lds) + "|" + std::to_string(r.partial_bytes) + "|" + std::to_string(r.counters) + "|" +
+               (r.writes.empty() ? "-" : r.writes) + "\n";
     if (txt.size() + 1 > cap) return fail(OG_EINVAL, "plan text does not fit the buffer");
     memcpy(out, txt.c_str(), txt.size() + 1);
     return (int)plan.recs.size();

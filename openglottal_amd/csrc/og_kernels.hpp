@@ -3713,3 +3713,104 @@ __global__ __launch_bounds__(256) void k_mask_stats(const uint8_t* __restrict__ 
         if (ng) atomicAdd(&stats[b * 3 + 2], ng);
     }
 }
+
+// =======================================================================================
+// Frames of any size around the U-Net (utils.py:218-241 `unet_segment_frame`: cv2.resize u8 -> 256x256, U-Net, sigmoid,
+// cv2.resize f32 back to the frame's size, > threshold; features.py:235,238-245 around it).  Arithmetic = OpenCV INTER_LINEAR as
+// restated in openglottal_amd/geometry.py (parity against a real cv2 unpinned, as for BAGLS):
+//   * og_linear_pos is geometry._linear_taps: half-pixel centre in f64, floor, f32 fraction, edge clamp.  Written with fp
+//     contraction OFF: hipcc would otherwise fuse ((d + 0.5) * scale) - 0.5 into one v_fma_f64 (it does in og_linear_tap),
+//     which rounds once where numpy rounds twice.  The same function runs on the host (og_linear_taps_host, the CPU test).
+//   * k_resize_in<C>: u8 source [B,H,W,C] -> u8 gray [B,Hn,Wn]; 11-bit coefficients and the
+//     ((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2 vertical pass.  C = 3 converts each tap with k_bgr2gray's rule first,
+//     which equals cvtColor at source resolution followed by the resize (the conversion is per pixel).
+//   * k_resize_out: f32 logits [B,Hn,Wn] -> sigmoid (as the fused head: 1 / (1 + expf(-x))) -> horizontal then vertical f32
+//     pass with the unrounded fractions -> strict > thr -> mask [B,H,W] {0,255} and the per-frame count (inside boxes[b] in
+//     SOURCE coordinates when given; x1 < 0 = no detection = 0).  Contraction OFF around the interpolation: an FMA would not
+//     equal numpy's a*(1-f) + b*f (tests/test_resize_host.py checks the ISA).  One thread per output pixel: the sigmoid of a
+//     net pixel is recomputed by the (up to 4) outputs that tap it -- the same bits each time.
+// =======================================================================================
+__host__ __device__ inline void og_linear_pos(int d, int src_len, int dst_len, int& i0, int& i1, float& frac) {
+#pragma clang fp contract(off)
+    const double f = ((double)d + 0.5) * ((double)src_len / (double)dst_len) - 0.5;
+    int k = (int)floor(f);
+    float fr = (float)(f - (double)k);
+    if (k < 0) { k = 0; fr = 0.f; }
+    if (k >= src_len - 1) { k = src_len - 1; fr = 0.f; }
+    i0 = k;
+    i1 = (k + 1 < src_len) ? k + 1 : src_len - 1;
+    frac = fr;
+}
+
+__host__ __device__ inline int og_linear_coef(float frac) { return (int)rintf(frac * 2048.0f); }
+
+template <int C>
+__device__ __forceinline__ int og_gray_at(const uint8_t* __restrict__ s, long long i) {
+    if (C == 1) return s[i];
+    return (s[3 * i] * 3735 + s[3 * i + 1] * 19235 + s[3 * i + 2] * 9798 + (1 << 14)) >> 15;   // k_bgr2gray
+}
+
+// grid (ceil(Hn*Wn / 256), B): one thread per net pixel
+template <int C>
+__global__ __launch_bounds__(256) void k_resize_in(const uint8_t* __restrict__ src, int H, int W, int Hn, int Wn, uint8_t* __restrict__ out) {
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= Hn * Wn) return;
+    const int ty = t / Wn, tx = t - ty * Wn;
+    int x0, x1, y0, y1;
+    float fx, fy;
+    og_linear_pos(tx, W, Wn, x0, x1, fx);
+    og_linear_pos(ty, H, Hn, y0, y1, fy);
+    const int ax1 = og_linear_coef(fx), ax0 = 2048 - ax1, ay1 = og_linear_coef(fy), ay0 = 2048 - ay1;
+    const uint8_t* s = src + (long long)b * H * W * C;
+    const int r0 = og_gray_at<C>(s, (long long)y0 * W + x0) * ax0 + og_gray_at<C>(s, (long long)y0 * W + x1) * ax1;
+    const int r1 = og_gray_at<C>(s, (long long)y1 * W + x0) * ax0 + og_gray_at<C>(s, (long long)y1 * W + x1) * ax1;
+    const int v = (((ay0 * (r0 >> 4)) >> 16) + ((ay1 * (r1 >> 4)) >> 16) + 2) >> 2;
+    out[(long long)b * Hn * Wn + t] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+__device__ __forceinline__ float og_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }   // the fused head's expression
+
+__device__ __noinline__ float og_resize_lerp(float p00, float p01, float p10, float p11, float fx, float fy) {
+#pragma clang fp contract(off)
+    const float gx = 1.0f - fx, gy = 1.0f - fy;
+    const float r0 = p00 * gx + p01 * fx;   // horizontal pass (rows y0, y1), then vertical: geometry.resize_linear's f32 order
+    const float r1 = p10 * gx + p11 * fx;
+    return r0 * gy + r1 * fy;
+}
+
+// grid (ceil(max(H*W, Hn*Wn) / 256), B): one thread per source pixel (threads < Hn*Wn also write net_prob when asked).
+// mask / area / boxes / net_prob / prob may each be null; area must be zeroed by the caller (counts are added per wave).
+__global__ __launch_bounds__(256) void k_resize_out(const float* __restrict__ logits, int Hn, int Wn, int H, int W, float thr,
+                                                    const int32_t* __restrict__ boxes, uint8_t* __restrict__ mask, int32_t* __restrict__ area,
+                                                    float* __restrict__ net_prob, float* __restrict__ prob) {
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int HWn = Hn * Wn, HW = H * W;
+    const float* lg = logits + (long long)b * HWn;
+    if (net_prob && t < HWn) net_prob[(long long)b * HWn + t] = og_sigmoid(lg[t]);
+    int cnt = 0;
+    if (t < HW) {
+        const int y = t / W, x = t - y * W;
+        int x0, x1, y0, y1;
+        float fx, fy;
+        og_linear_pos(x, Wn, W, x0, x1, fx);
+        og_linear_pos(y, Hn, H, y0, y1, fy);
+        const float p = og_resize_lerp(og_sigmoid(lg[y0 * Wn + x0]), og_sigmoid(lg[y0 * Wn + x1]), og_sigmoid(lg[y1 * Wn + x0]),
+                                       og_sigmoid(lg[y1 * Wn + x1]), fx, fy);
+        const bool on = p > thr;
+        if (prob) prob[(long long)b * HW + t] = p;
+        if (mask) mask[(long long)b * HW + t] = on ? 255 : 0;
+        if (boxes != nullptr) {
+            const int bx1 = boxes[b * 4 + 0], by1 = boxes[b * 4 + 1], bx2 = boxes[b * 4 + 2], by2 = boxes[b * 4 + 3];
+            cnt = (on && bx1 >= 0 && x >= bx1 && x < bx2 && y >= by1 && y < by2) ? 1 : 0;
+        } else {
+            cnt = on ? 1 : 0;
+        }
+    }
+    if (area) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+        if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&area[b], cnt);
+    }
+}

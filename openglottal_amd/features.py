@@ -157,13 +157,24 @@ def _blocks_with_boxes(frames, detector, model=None):
             yield blk, boxes
 
 
+def _shape_runs(frames):
+    """``(lo, hi)`` of each run of consecutive frames with one shape and dtype."""
+    runs, lo = [], 0
+    for i in range(1, len(frames) + 1):
+        if i == len(frames) or frames[i].shape != frames[lo].shape or frames[i].dtype != frames[lo].dtype:
+            runs.append((lo, i))
+            lo = i
+    return runs
+
+
 def area_waveform(frames, detector, model, device=None, threshold: float = 0.5) -> np.ndarray:
     """The frame loop of features.py:234-245 as batched device passes over blocks of the video.
 
     U-Net-only (``detector is None``): area = #(mask>0) per frame.  Gated: the sequential TemporalDetector pass produces
     one box per frame first (the U-Net does not depend on it), then the fused kernel counts inside the boxes.  Frames at
     network size go to the streaming engine as they are — BGR included: `cv2.cvtColor(BGR2GRAY)` (features.py:235) runs on
-    the device — so no per-frame host work is left and device memory does not grow with the video.
+    the device — so no per-frame host work is left and device memory does not grow with the video.  Frames of any other size
+    (each run of one shape inside a mixed block) take the same engine with the two resizes of utils.py:234,239-240 on the device.
     """
     if device is not None and getattr(model, "_device", None) is None:
         model.to(device)
@@ -182,15 +193,27 @@ def area_waveform(frames, detector, model, device=None, threshold: float = 0.5) 
             # frame by frame into its pinned ring -- no np.stack of the block
             _, area = model.segment_stream(blk if isinstance(blk, np.ndarray) else list(blk), threshold=threshold, boxes=boxes)
             out.append(area.astype(np.float64))
-        else:   # mixed / non-256 frames: per-frame path incl. host resizes (utils.py:234,239-240)
+        else:   # other sizes / mixed sizes: each run of equal-shape u8 frames goes to the streamed resized entry
             a = np.zeros(n, np.float64)
-            for i, f in enumerate(blk):
-                m = unet_segment_frame(bgr_to_gray(f), model, device, threshold)
-                if boxes is None:
-                    a[i] = float(np.sum(m > 0))
-                elif boxes[i][0] >= 0:
-                    x1, y1, x2, y2 = boxes[i]
-                    a[i] = float(np.sum(m[y1:y2, x1:x2] > 0))
+            for lo, hi in _shape_runs(blk):
+                run = blk[lo:hi]
+                f0 = run[0]
+                bx = None if boxes is None else boxes[lo:hi]
+                if getattr(f0, "dtype", None) == np.uint8 and (f0.ndim == 2 or (f0.ndim == 3 and f0.shape[2] == 3)):
+                    run = run if isinstance(run, np.ndarray) else list(run)
+                    if f0.shape[:2] == (NET_SIZE, NET_SIZE):
+                        _, ar = model.segment_stream(run, threshold=threshold, boxes=bx)
+                    else:
+                        _, ar = model.segment_resized(run, net=NET_SIZE, threshold=threshold, boxes=bx, want_mask=False)
+                    a[lo:hi] = ar
+                    continue
+                for i in range(lo, hi):   # not u8 gray / BGR: the per-frame loop of features.py:234-245
+                    m = unet_segment_frame(bgr_to_gray(blk[i]), model, device, threshold)
+                    if boxes is None:
+                        a[i] = float(np.sum(m > 0))
+                    elif boxes[i][0] >= 0:
+                        x1, y1, x2, y2 = boxes[i]
+                        a[i] = float(np.sum(m[y1:y2, x1:x2] > 0))
             out.append(a)
         done += n
     return np.concatenate(out) if out else np.zeros(0, np.float64)

@@ -182,6 +182,87 @@ class UNet:
               "og_unet_stream_frames_u8")
         return mask, area
 
+    def segment_resized(self, frames, net: int = 256, threshold: float = 0.5, boxes=None, want_mask: bool = True,
+                        want_prob: bool = False):
+        """`unet_segment_frame` (utils.py:218-241) for frames of ANY size, streamed on the device: u8 → ``net``×``net``
+        (INTER_LINEAR) → U-Net → sigmoid → back to the frame's size (INTER_LINEAR, f32) → ``> threshold``, plus the area count
+        (inside ``boxes`` given in SOURCE coordinates).  ``frames``: ``[B,H,W]`` gray or ``[B,H,W,3]`` BGR u8 as an array, a list
+        of frames of one shape, or a contiguous u8 host torch tensor (pinned goes up without a staging copy).  ``net``: an int or
+        ``(net_h, net_w)``.  Returns ``(mask | None, area int32 [B])``, or ``(mask | None, area, prob f32 [B,H,W])`` with
+        ``want_prob`` (one device pass through ``og_unet_segment_resized_u8_dev``)."""
+        self._require()
+        net_h, net_w = (int(net), int(net)) if np.isscalar(net) else (int(net[0]), int(net[1]))
+        keep = None
+        if isinstance(frames, (list, tuple)):
+            keep = [f if (isinstance(f, np.ndarray) and f.dtype == np.uint8 and f.flags.c_contiguous) else np.ascontiguousarray(f, dtype=np.uint8)
+                    for f in frames]
+            if keep and any(f.shape != keep[0].shape for f in keep):
+                raise OpenGlottalHipError("segment_resized(list): frames must share one [H,W] or [H,W,3] shape")
+            shape = (len(keep),) + (keep[0].shape if keep else (0, 0))
+            f = None
+        elif hasattr(frames, "data_ptr"):
+            if frames.device.type != "cpu" or str(frames.dtype) != "torch.uint8" or not frames.is_contiguous():
+                raise OpenGlottalHipError("segment_resized expects a contiguous uint8 host tensor")
+            f, shape = frames, tuple(frames.shape)
+        else:
+            f = np.ascontiguousarray(frames, dtype=np.uint8)
+            shape = f.shape
+        if len(shape) == 4 and shape[-1] == 3:
+            ch = 3
+        elif len(shape) == 3:
+            ch = 1
+        else:
+            raise OpenGlottalHipError(f"expected [B,H,W] or [B,H,W,3] frames, got {shape}")
+        B, H, W = (int(v) for v in shape[:3])
+        mask = np.empty((B, H, W), np.uint8) if (want_mask or want_prob) else None
+        area = np.zeros(B, np.int32)
+        bx = None if boxes is None else np.ascontiguousarray(boxes, dtype=np.int32).reshape(B, 4)
+        if B == 0:
+            return (mask, area, np.empty((0, H, W), np.float32)) if want_prob else (mask, area)
+        if want_prob:
+            if f is None:
+                f = np.stack(keep)
+            prob = np.empty((B, H, W), np.float32)
+            src = np.ascontiguousarray(f.numpy() if hasattr(f, "numpy") else f)
+            bufs = []
+            try:
+                for n in (src.nbytes, mask.nbytes, area.nbytes, prob.nbytes, 16 * B):
+                    d = lib().og_malloc(max(1, n))
+                    if not d:
+                        raise OpenGlottalHipError("og_malloc failed")
+                    bufs.append(d)
+                d_src, d_mask, d_area, d_prob, d_box = bufs
+                check(lib().og_memcpy_h2d(d_src, ptr(src), src.nbytes), "og_memcpy_h2d")
+                if bx is not None:
+                    check(lib().og_memcpy_h2d(d_box, ptr(bx), bx.nbytes), "og_memcpy_h2d")
+                self.segment_resized_dev(d_src, B, H, W, ch, net_h, net_w, d_area, threshold, d_box if bx is not None else None,
+                                         d_mask, prob_dev=d_prob)
+                self.sync()
+                for host, dev in ((mask, d_mask), (area, d_area), (prob, d_prob)):
+                    check(lib().og_memcpy_d2h(ptr(host), dev, host.nbytes), "og_memcpy_d2h")
+            finally:
+                for d in bufs:
+                    lib().og_free(d)
+            return (mask if want_mask else None), area, prob
+        if f is None:
+            ptrs = (C.c_void_p * B)(*[k.ctypes.data for k in keep])
+            check(lib().og_unet_stream_frames_resized_u8(self._h, ptrs, B, H, W, ch, net_h, net_w, float(threshold), ptr(bx), ptr(mask),
+                                                         ptr(area)), "og_unet_stream_frames_resized_u8")
+        else:
+            check(lib().og_unet_stream_resized_u8(self._h, ptr(f), B, H, W, ch, net_h, net_w, float(threshold), ptr(bx), ptr(mask),
+                                                  ptr(area)), "og_unet_stream_resized_u8")
+        return mask, area
+
+    def segment_resized_dev(self, src_dev, B: int, H: int, W: int, channels: int, net_h: int, net_w: int, area_dev,
+                            threshold: float = 0.5, boxes_dev=None, mask_dev=None, net_logits_dev=None, net_prob_dev=None,
+                            prob_dev=None) -> None:
+        """Device-pointer, asynchronous variant of ``segment_resized`` (torch CUDA tensors or raw ints); the last three are
+        optional debug outputs at network / network / source size."""
+        self._require()
+        check(lib().og_unet_segment_resized_u8_dev(self._h, ptr(src_dev), B, H, W, channels, net_h, net_w, float(threshold),
+                                                   ptr(boxes_dev), ptr(mask_dev), ptr(area_dev), ptr(net_logits_dev),
+                                                   ptr(net_prob_dev), ptr(prob_dev)), "og_unet_segment_resized_u8_dev")
+
     def segment_dev(self, gray_dev, B: int, H: int, W: int, area_dev, threshold: float = 0.5, boxes_dev=None,
                     mask_dev=None, logits_dev=None) -> None:
         """Device-pointer, asynchronous variant (torch CUDA tensors or raw ints)."""

@@ -36,12 +36,11 @@ def bgr_to_gray_numpy(f: np.ndarray) -> np.ndarray:
 
 
 def unet_segment_frame(frame_gray: np.ndarray, model, device=None, threshold: float = 0.5) -> np.ndarray:
-    """Drop-in for `openglottal/utils.py:218-241`: ``(H,W)`` u8 → u8 mask in {0,255}.
+    """Drop-in for `openglottal/utils.py:218-241`: ``(H,W)`` u8 → u8 mask in {0,255}, all on the device.
 
-    256×256 frames (every BASELINE config) run fully on the device: u8 → /255 →
-    U-Net → sigmoid → ``> threshold`` in one kernel chain.  Other sizes go through
-    host bilinear resizes like the reference's two ``cv2.resize`` calls
-    (utils.py:234,239-240; parity unpinned, see ``resize_linear``).
+    256×256 frames (every BASELINE config) run as one kernel chain: u8 → /255 → U-Net → sigmoid → ``> threshold``.
+    Other sizes add the reference's two ``cv2.resize`` calls (utils.py:234,239-240) as device kernels around it
+    (``UNet.segment_resized``; OpenCV's arithmetic as restated in ``geometry.resize_linear``, parity unpinned).
     """
     g = np.asarray(frame_gray)
     if g.ndim != 2:
@@ -52,6 +51,19 @@ def unet_segment_frame(frame_gray: np.ndarray, model, device=None, threshold: fl
     if (H, W) == (NET_SIZE, NET_SIZE):
         mask, _, _ = model.segment(g[None], threshold=threshold, want_mask=True, want_area=False)
         return mask[0]
+    mask, _ = model.segment_resized(np.ascontiguousarray(g, dtype=np.uint8)[None], net=NET_SIZE, threshold=threshold)
+    return mask[0]
+
+
+def unet_segment_frame_host(frame_gray: np.ndarray, model, device=None, threshold: float = 0.5) -> np.ndarray:
+    """The same function with both resizes, the sigmoid and the threshold on the host (numpy) around a device U-Net call:
+    the restatement the device path is tested against (tests/test_gpu_resized.py)."""
+    g = np.asarray(frame_gray)
+    if g.ndim != 2:
+        raise OpenGlottalHipError(f"frame_gray must be (H, W), got {g.shape}")
+    if device is not None and getattr(model, "_device", None) is None:
+        model.to(device)
+    H, W = g.shape
     from .geometry import resize_linear
 
     inp = resize_linear(g.astype(np.uint8), NET_SIZE, NET_SIZE)

@@ -42,6 +42,8 @@ def parse_args() -> argparse.Namespace:
     ap.add_argument("--warmup", type=int, default=20, help="frames pushed through both passes before the clock starts")
     ap.add_argument("--video", default=None, help=".npy / .npz / directory of images to read frames from (read time reported separately)")
     ap.add_argument("--json", action="store_true", help="also print the numbers as one JSON line")
+    ap.add_argument("--height", type=int, default=256, help="height of the synthetic frames (any size: resized on the device)")
+    ap.add_argument("--width", type=int, default=256, help="width of the synthetic frames")
     return ap.parse_args()
 
 
@@ -72,13 +74,14 @@ def build_detector(path: str | None, device: str):
     return TemporalDetector(backend), f"random-init YOLOv8n ({path} does not exist)"
 
 
-def frame_source(video: str | None, count: int):
+def frame_source(video: str | None, count: int, h: int = 256, w: int = 256):
     """(list of BGR frames, seconds spent reading them, description)."""
     from openglottal_amd import synth
     from openglottal_amd.features import load_frames_bgr
 
     if video is None:
-        return [synth.bench_frame_bgr(i) for i in range(count)], 0.0, f"{count} seeded 256x256 BGR frames, RandomState(1234+i)"
+        return ([synth.bench_frame_bgr(i, h, w) for i in range(count)], 0.0,
+                f"{count} seeded {h}x{w} BGR frames, RandomState(1234+i)")
     t = time.perf_counter()
     frames = load_frames_bgr(video)[:count]
     return frames, time.perf_counter() - t, f"{len(frames)} frames of {video}"
@@ -140,7 +143,7 @@ def main() -> None:
     args = parse_args()
     net, unet_origin = build_unet(args.unet_weights, args.device)
     detector, det_origin = build_detector(args.yolo_weights, args.device)
-    frames, read_s, what = frame_source(args.video, args.frames)
+    frames, read_s, what = frame_source(args.video, args.frames, args.height, args.width)
     n = len(frames)
     if n == 0:
         raise SystemExit("no frames to process")

@@ -45,7 +45,7 @@ extern "C" {
 #define OG_EHIP (-3)     /* HIP runtime error, see og_last_error() */
 #define OG_ENOMEM (-4)
 #define OG_ENODEV (-5)   /* no usable gfx950 device */
-#define OG_ERANGE (-6)   /* split precision only: an activation left the f16 range; the call's results are invalid */
+#define OG_ERANGE (-6)   /* split precision and f16 mode: an activation left the f16 range; the call's results are invalid */
 
 #define OG_DTYPE_F32 0
 #define OG_DTYPE_I64 1
@@ -178,7 +178,7 @@ int og_canvas_letterbox_u8_dev(og_unet* h, const uint8_t* packed_dev, const int6
 int og_mask_stats_dev(og_unet* h, const uint8_t* pred_dev, const uint8_t* gt_dev, int B, int H, int W, const int32_t* boxes_dev,
                       int32_t* stats_dev);
 
-int og_unet_sync(og_unet* h);                /* also reports OG_ERANGE of asynchronous split-precision work */
+int og_unet_sync(og_unet* h);                /* also reports OG_ERANGE of asynchronous split-precision / f16-mode work */
 void* og_unet_stream(og_unet* h);          /* hipStream_t the handle launches on */
 
 /* Micro-batch the frame loop uses per kernel chain (default 32); >=1. */
@@ -197,7 +197,7 @@ int og_unet_set_graphs(og_unet* h, int enable);
  * "splitk_occ" 0|1 (K parts of a split launch on the occupancy kernel; 0: persistent kernel), "splitk_slots" 1..4 and "splitk_div" 1..8
  * (its target workgroups per CU / split when the launch fills less than 1/div of them),
  * "occ_min_pct" 0..400 (occupancy kernel when a launch has at least that many workgroups per 100 CUs), "convt_occ" 0|1, "fuse_first" 0|1 (first layer computed inside downs.0's second conv), "fuse_head" 0|1 (head +
- * threshold + area inside the last conv's epilogue), "keep_taps" 0|1, "precision" 0|1 (NOT bit-identical: 0 = exact f32, the default and the parity reference; 1 = opt-in split precision -- activations and weights as f16 hi/lo pairs, three v_mfma_f32_32x32x16_f16 per f32 product, f32 accumulation; passes the reference fixtures at the f32 tolerance, 2.5x faster; an activation beyond the f16 range makes the call fail with OG_ERANGE), "h_square" 0|1 (its wave tiling), "stream" 0|1 (og_unet_segment_u8 through the streaming engine, default 1; 0 = whole batch staged at once), "dual" 0|1 (micro-batches of one call alternate over extra lanes = streams/arenas, so that launch tails overlap) with "lanes" 0..3 (0 = 3 lanes up to 16 frames per launch, else 2), and
+ * threshold + area inside the last conv's epilogue), "keep_taps" 0|1, "precision" 0|1|2 (NOT bit-identical: 0 = exact f32, the default and the parity reference; 1 = opt-in split precision -- activations and weights as f16 hi/lo pairs, three v_mfma_f32_32x32x16_f16 per f32 product, f32 accumulation; passes the reference fixtures at the f32 tolerance, 2.5x faster; an activation beyond the f16 range makes the call fail with OG_ERANGE; 2 = opt-in f16 mode -- weights of the 3x3 and transposed convs rounded to f16 once at og_unet_finalize, every stored activation rounded to f16 once in the epilogue that produces it (2 bytes per channel: half the arena), one v_mfma_f32_32x32x16_f16 per 16 products, f32 accumulation, BN / first layer / head in f32; logits differ from f32 by ~1e-2 and mask pixels may differ where the f32 logit is that close to zero (DESIGN "f16 mode"); same OG_ERANGE rule; never splits K: "splitk" 1 together with "precision" 2 is refused with OG_EINVAL, whichever is set second; og_unet_get_activation returns the stored f16 values widened to f32), "h_square" 0|1 (its wave tiling), "stream" 0|1 (og_unet_segment_u8 through the streaming engine, default 1; 0 = whole batch staged at once), "dual" 0|1 (micro-batches of one call alternate over extra lanes = streams/arenas, so that launch tails overlap) with "lanes" 0..3 (0 = 3 lanes up to 16 frames per launch, else 2), and
  * "wino_w" 0..4 [1] (under-filled Winograd launches -- one frame per kernel chain, the reference's call pattern utils.py:235-237 --
  * on finer tiles with the 16 positions split over the four WAVES of a workgroup, V transformed in registers, accumulators exchanged
  * through LDS (k_conv_wino_w), deep layers with a tile's four position rows on four workgroups (k_conv_wino_wp); the same sums as

@@ -25,9 +25,11 @@ def main(argv=None) -> int:
     r.add_argument("--device", default="cuda")
     r.add_argument("-o", "--output", default="output")
     r.add_argument("--annotate", action="store_true", help="also write the pipeline and video names into features.json")
-    r.add_argument("--precision", choices=["f32", "split"], default="f32",
+    r.add_argument("--precision", choices=["f32", "split", "f16"], default="f32",
                    help="f32: exact fp32 kernels (default, the parity reference); split: opt-in f16 hi/lo split precision "
-                        "(2.5x faster, same reference fixtures and tolerance; fails loudly if an activation leaves the f16 range)")
+                        "(2.5x faster, same reference fixtures and tolerance; fails loudly if an activation leaves the f16 range); "
+                        "f16: opt-in half precision (f16 operands and stored activations, f32 accumulation; fastest, half the "
+                        "memory; logits move by ~1e-2, so masks may differ from f32 where a logit is near zero)")
     a = ap.parse_args(argv)
 
     import torch
@@ -39,8 +41,8 @@ def main(argv=None) -> int:
     model = UNet(1, 1, (32, 64, 128, 256)).to(a.device)
     model.load_state_dict(torch.load(a.unet_weights, map_location="cpu", weights_only=True))
     model.eval()
-    if a.precision == "split":
-        model.set_option("precision", 1)
+    if a.precision != "f32":
+        model.set_option("precision", {"split": 1, "f16": 2}[a.precision])
     detector = TemporalDetector(a.yolo_weights) if a.pipeline == "unet" else None
     feats = extract_features_unet(a.video, detector, model, a.device)
     if feats is None:

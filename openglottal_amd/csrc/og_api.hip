@@ -123,6 +123,7 @@ struct ConvLayer {  // one 3x3 conv + BN + ReLU, or one 2x2 transposed conv
     int NT = 1;
     float* d_w = nullptr;
     float* d_w_h = nullptr;   // the same weights as f16 hi/lo pairs in the H layout (opt-in split precision)
+    float* d_w_f = nullptr;   // the same weights rounded once to f16, 64-channel chunks (opt-in f16 mode, k_conv_mfma_f)
     float* d_w1 = nullptr;    // 3x3 convs with NT == 2: the same weights packed for 32-column tiles (split-K launches)
     float* d_ww = nullptr;    // 3x3 convs: Winograd F(2x2,3x3) image for k_conv_wino<NT> (pack_wino)
     float* d_ww1 = nullptr;   // NT == 2 layers: the same image cut for 32-column tiles and 8-channel chunks (k_conv_wino_w)
@@ -272,7 +273,8 @@ struct og_unet {
         hipStream_t s_h2d = nullptr, s_d2h = nullptr;
     } ring;
     int precision = 0;     // 0: exact f32 (v_mfma_f32_32x32x2_f32) -- the default and the parity reference; 1: opt-in split precision
-                           // (f16 hi/lo pairs, 3 x v_mfma_f32_32x32x16_f16 per f32 product, f32 accumulation; k_conv_mfma_h)
+                           // (f16 hi/lo pairs, 3 x v_mfma_f32_32x32x16_f16 per f32 product, f32 accumulation; k_conv_mfma_h);
+                           // 2: opt-in f16 mode (f16 operands and 2-byte activations, one MFMA per product, f32 accumulation; k_conv_mfma_f)
     int* h_range = nullptr;   // split precision: host-mapped word the kernels raise when an activation leaves the f16 range
     int* d_range = nullptr;   //   (device view of the same word; the lanes share it)
     int h_square = 1;      // split precision, 64-column kernel on 16x16 tiles: 2x2 sub-tiles per wave (fewer LDS reads per MFMA)
@@ -390,6 +392,33 @@ std::vector<float> pack_gemm_b_h(int Ncols_p, int Kp, int taps, int NT, F&& weig
     return out;
 }
 
+// f16-mode image (og_kernels.hpp "F layout"): per (row, 64-channel chunk, tap) the 128 bytes hold eight 16-byte slots, logical
+// slot s = f16 (round to nearest even, once) of k = 64c + 8s .. +7; physical slot = logical ^ ((r>>1)&7) as in the f32 image.
+// A padded Cin that is an odd multiple of 32 leaves the upper half of the last chunk zero (the kernel skips it: ConvArgs::k_half).
+template <typename F>
+std::vector<float> pack_gemm_b_f(int Ncols_p, int Kp, int taps, int NT, F&& weight_at /*(n, k, tap)->float*/) {
+    const int rows = 32 * NT;
+    const int n_tiles = Ncols_p / rows;
+    const int n_chunks = (Kp + 63) / 64;
+    std::vector<float> out((size_t)Ncols_p * n_chunks * 32 * taps, 0.f);
+    _Float16* o16 = (_Float16*)out.data();
+    size_t o = 0;   // in halves
+    for (int nt = 0; nt < n_tiles; ++nt)
+        for (int c = 0; c < n_chunks; ++c)
+            for (int t = 0; t < taps; ++t) {
+                for (int r = 0; r < rows; ++r)
+                    for (int ps = 0; ps < 8; ++ps) {
+                        const int sl = ps ^ ((r >> 1) & 7);
+                        for (int e = 0; e < 8; ++e) {
+                            const int k = c * 64 + sl * 8 + e;
+                            o16[o + (size_t)r * 64 + ps * 8 + e] = (_Float16)((k < Kp) ? weight_at(nt * rows + r, k, t) : 0.f);
+                        }
+                    }
+                o += (size_t)rows * 64;
+            }
+    return out;
+}
+
 int upload(const std::vector<float>& v, float** d) {
     HIPCHK(hipMalloc((void**)d, v.size() * sizeof(float)));
     HIPCHK(hipMemcpy(*d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -407,7 +436,7 @@ int build_conv(og_unet* h, ConvLayer& L, const std::string& wkey, const std::str
     L.Cout_p = cp32(Cout);
     L.NT = (L.Cout_p % 64 == 0) ? 2 : 1;
     if (h->host_only) {   // shapes only: every image a launch decision asks for "exists"
-        L.d_w = L.d_w_h = L.d_ww = L.d_scale = L.d_shift = (float*)8;
+        L.d_w = L.d_w_h = L.d_w_f = L.d_ww = L.d_scale = L.d_shift = (float*)8;
         L.d_w1 = L.d_ww1 = (L.NT == 2) ? (float*)8 : nullptr;
         return OG_OK;
     }
@@ -423,6 +452,7 @@ int build_conv(og_unet* h, ConvLayer& L, const std::string& wkey, const std::str
     int rc;
     if ((rc = upload(pk, &L.d_w))) return rc;
     if ((rc = upload(pack_gemm_b_h(L.Cout_p, L.Cin_p, 9, L.NT, at), &L.d_w_h))) return rc;
+    if ((rc = upload(pack_gemm_b_f(L.Cout_p, L.Cin_p, 9, L.NT, at), &L.d_w_f))) return rc;
     if (L.NT == 2 && (rc = upload(pack_gemm_b(L.Cout_p, L.Cin_p, 9, 1, at), &L.d_w1))) return rc;
     if ((rc = upload(pack_wino(L.Cout_p, L.Cin_p, L.NT, at), &L.d_ww))) return rc;
     if (L.NT == 2 && (rc = upload(pack_wino(L.Cout_p, L.Cin_p, 1, at), &L.d_ww1))) return rc;
@@ -440,7 +470,7 @@ int build_convT(og_unet* h, ConvLayer& L, const std::string& p, int Cin, int Cou
     L.Cout_p = cp32(Cout);
     L.NT = 2;  // N = 4*Cout_p is a multiple of 128
     if (h->host_only) {
-        L.d_w = L.d_w_h = L.d_w1 = L.d_scale = L.d_shift = (float*)8;
+        L.d_w = L.d_w_h = L.d_w_f = L.d_w1 = L.d_scale = L.d_shift = (float*)8;
         return OG_OK;
     }
     const auto& w = h->host.at(p + ".weight").data;  // [Cin][Cout][2][2]
@@ -461,6 +491,7 @@ int build_convT(og_unet* h, ConvLayer& L, const std::string& p, int Cin, int Cou
     if ((rc = upload(pk, &L.d_w))) return rc;
     if ((rc = upload(pack_gemm_b(4 * Cop, L.Cin_p, 1, 1, at), &L.d_w1))) return rc;   // 32-column tiles (k_convt_w)
     if ((rc = upload(pack_gemm_b_h(4 * Cop, L.Cin_p, 1, L.NT, at), &L.d_w_h))) return rc;
+    if ((rc = upload(pack_gemm_b_f(4 * Cop, L.Cin_p, 1, L.NT, at), &L.d_w_f))) return rc;
     if ((rc = upload(sc, &L.d_scale))) return rc;
     if ((rc = upload(sh, &L.d_shift))) return rc;
     return OG_OK;
@@ -475,12 +506,13 @@ std::vector<int> ident_map(int Cin) {
 void free_layer(ConvLayer& L) {
     if (L.d_w) (void)hipFree(L.d_w);
     if (L.d_w_h) (void)hipFree(L.d_w_h);
+    if (L.d_w_f) (void)hipFree(L.d_w_f);
     if (L.d_w1) (void)hipFree(L.d_w1);
     if (L.d_ww) (void)hipFree(L.d_ww);
     if (L.d_ww1) (void)hipFree(L.d_ww1);
     if (L.d_scale) (void)hipFree(L.d_scale);
     if (L.d_shift) (void)hipFree(L.d_shift);
-    L.d_w = L.d_w_h = L.d_w1 = L.d_ww = L.d_ww1 = L.d_scale = L.d_shift = nullptr;
+    L.d_w = L.d_w_h = L.d_w_f = L.d_w1 = L.d_ww = L.d_ww1 = L.d_scale = L.d_shift = nullptr;
 }
 
 void drop_graphs(og_unet* h) {
@@ -507,7 +539,10 @@ ArenaPlan arena_layout(const og_unet* h, int B, int H, int W) {
     const int L = h->L;
     ArenaPlan p;
     p.A.resize(L); p.CAT.resize(L); p.P.resize(L); p.UA.resize(L); p.UB.resize(L);
-    auto plan = [&](Act& a, int C, int hh, int ww) {
+    // f16 mode (F layout): 2 bytes per channel -- Act::C, the pixel stride, stays in 4-byte units and is then HALF the channel count
+    const int cdiv = (h->precision == 2) ? 2 : 1;
+    auto plan = [&](Act& a, int Cch, int hh, int ww) {
+        const int C = Cch / cdiv;
         a.C = C;
         a.H = hh;
         a.W = ww;
@@ -790,6 +825,30 @@ int launch_conv_h(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {   //
     return OG_OK;
 }
 
+template <int NT, int MODE, int TH, int OCC, bool SQ = false>
+int launch_conv_f(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {   // f16-mode twin of launch_conv_h (never splits K)
+    constexpr int lds = conv_o_lds<NT, MODE, TH>();
+    ConvArgs a = a_in;
+    a.stamps = nullptr;
+    a.ksplit = 1;
+    a.tile_counter = nullptr;
+    const int frames = a.n_spatial / (a.tiles_x * a.tiles_y);
+    a.zdiv = n_ntiles;
+    a.frames = frames;
+    a.zgroup_shift = 0;
+    if (c.xcd_group && a.zdiv > 1) {
+        int txy = a.tiles_x * a.tiles_y, g = 8;
+        while (g > 1 && txy % 2 == 0) { txy /= 2; g /= 2; }
+        while (g > frames) g /= 2;
+        while ((1 << a.zgroup_shift) < g) ++a.zgroup_shift;
+    }
+    const int G = 1 << a.zgroup_shift, groups = (frames + G - 1) / G;
+    a.zrcp = 1.0f / (float)(a.zdiv * G);
+    if ((long long)groups * G * a.zdiv > 65535) return fail(OG_EINVAL, "micro-batch too large for one launch (grid.z): lower the chunk size");
+    OG_LAUNCH((k_conv_mfma_f<NT, MODE, TH, OCC, false, SQ>), dim3(a.tiles_x, a.tiles_y, groups * G * a.zdiv), dim3(256), lds, c.stream, a);
+    return OG_OK;
+}
+
 template <int NT, int MODE, int TH, int TPS>
 int launch_conv_p(const LaunchCtx& c, const ConvArgs& a, int n_ntiles) {
     constexpr int lds = conv_p_lds<NT, MODE, TH, TPS>();
@@ -869,6 +928,14 @@ int init_kernel_attrs() {  // must not run inside a stream capture
     HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_h<2, 0, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 0, 8>()));
     HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_h<1, 0, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<1, 0, 8>()));
     HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_h<2, 1, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 1, 8>()));
+    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_f<1, 0, 8, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               conv_o_lds<1, 0, 8>() + (12 * 20 + 352) * 4));
+    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_f<2, 0, 16, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 0, 16>()));
+    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_f<2, 0, 16, 2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 0, 16>()));
+    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_f<1, 0, 16, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<1, 0, 16>()));
+    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_f<2, 0, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 0, 8>()));
+    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_f<1, 0, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<1, 0, 8>()));
+    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_f<2, 1, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 1, 8>()));
     if ((rc = set_conv_p_attr<2, 0, 16, 1>())) return rc;
     if ((rc = set_conv_p_attr<2, 0, 16, 3>())) return rc;
     if ((rc = set_conv_p_attr<1, 0, 16, 3>())) return rc;
@@ -972,6 +1039,44 @@ int launch_conv(og_unet* h, const ConvLayer& L, int B, const Act& in, int in_off
     a.vsplit = 1;
     a.partial = h->d_partial;
     a.tile_counter = (h->splitk_fused && h->d_tile_counter) ? h->d_tile_counter : nullptr;
+    a.k_half = 0;
+    if (h->precision == 2) {   // opt-in f16 mode: k_conv_mfma_f on the occupancy-shaped tiles, never split-K ("splitk" is refused)
+        // F layout: the views' strides are already in 4-byte units (arena_layout); channel offsets become such units here
+        a.in_ch_off = in_off / 2;
+        a.out_ch_off = out_off / 2;
+        a.n_chunks = (L.Cin_p + 63) / 64;
+        a.k_half = (L.Cin_p % 64) ? 1 : 0;
+        big = full16 && h->tile_h != 8;          // as split precision: 16-row tiles wherever they tile the image
+        if (a.head_w != nullptr) big = false;    // per-tile count slots of the fused head are laid out for 8x16 tiles
+        const int th_f = big ? 16 : 8;
+        a.tiles_y = (in.H + th_f - 1) / th_f;
+        a.n_spatial = B * a.tiles_x * a.tiles_y;
+        a.wpk = L.d_w_f;
+        a.stamps = nullptr;
+        const double px_f = (double)B * in.H * in.W;
+        int rc_f;
+        if (L.mode == 0) {
+            if (out.H != in.H || out.W != in.W) return fail(OG_EINVAL, "conv shape mismatch");
+            const int n_ntiles = L.Cout_p / (32 * L.NT);
+            const double fl = 2.0 * px_f * 9.0 * L.Cin * L.Cout;
+            if (big) {
+                prof_begin(h, L.name, L.NT == 2 ? "k_conv_mfma_f<2,0,16>" : "k_conv_mfma_f<1,0,16>", fl);
+                if (L.NT == 2) rc_f = h->h_square ? launch_conv_f<2, 0, 16, 2, true>(ctx, a, n_ntiles) : launch_conv_f<2, 0, 16, 2>(ctx, a, n_ntiles);
+                else rc_f = launch_conv_f<1, 0, 16, 2>(ctx, a, n_ntiles);
+            } else {
+                prof_begin(h, L.name, L.NT == 2 ? "k_conv_mfma_f<2,0,8>" : "k_conv_mfma_f<1,0,8>", fl);
+                rc_f = (L.NT == 2) ? launch_conv_f<2, 0, 8, 3>(ctx, a, n_ntiles) : launch_conv_f<1, 0, 8, 3>(ctx, a, n_ntiles);
+            }
+        } else {
+            if (out.H != 2 * in.H || out.W != 2 * in.W) return fail(OG_EINVAL, "convT shape mismatch");
+            a.tiles_y = (in.H + 7) / 8;
+            a.n_spatial = B * a.tiles_x * a.tiles_y;
+            prof_begin(h, L.name, "k_conv_mfma_f<2,1,8>", 2.0 * px_f * 4.0 * L.Cin * L.Cout);
+            rc_f = launch_conv_f<2, 1, 8, 3>(ctx, a, 4 * L.Cout_p / 64);
+        }
+        prof_end(h);
+        return rc_f;
+    }
     if (h->precision == 1) {   // opt-in split precision: always the occupancy-shaped kernel, no split-K
         // tile height: an MFMA step is 5x shorter here than in the f32 kernels, so barriers and staged bytes per MFMA weigh
         // more: 16-row tiles wherever they tile the image ("tile_h" 8 forces 8 rows, 16 / 0 = this rule)
@@ -1212,9 +1317,16 @@ int enqueue_first(og_unet* h, int kind, const void* in, int B, int H, int W) {
     const int Cp0 = cp32(h->features[0]);
     const int tiles = ((W + 15) / 16) * ((H + 15) / 16);
     const Act& o = h->A[0];
-    prof_begin(h, "downs.0.net.0.weight", kind == KIND_U8 ? "k_conv_first<u8>" : "k_conv_first<f32>",
+    prof_begin(h, "downs.0.net.0.weight", h->precision == 2 ? (kind == KIND_U8 ? "k_conv_first_f<u8>" : "k_conv_first_f<f32>")
+                                          : kind == KIND_U8 ? "k_conv_first<u8>" : "k_conv_first<f32>",
                2.0 * B * H * W * 9.0 * h->features[0]);
-    if (kind == KIND_U8 && h->precision == 1)
+    if (h->precision == 2 && kind == KIND_U8)
+        OG_LAUNCH(k_conv_first_f<uint8_t>, dim3(B * tiles), dim3(256), 0, h->stream, (const uint8_t*)in, o.p,
+                           h->d_first_w, h->d_first_scale, h->d_first_shift, H, W, Cp0, o.C, o.frame_stride(), h->d_range);
+    else if (h->precision == 2)
+        OG_LAUNCH(k_conv_first_f<float>, dim3(B * tiles), dim3(256), 0, h->stream, (const float*)in, o.p,
+                           h->d_first_w, h->d_first_scale, h->d_first_shift, H, W, Cp0, o.C, o.frame_stride(), h->d_range);
+    else if (kind == KIND_U8 && h->precision == 1)
         OG_LAUNCH((k_conv_first<uint8_t, true>), dim3(B * tiles), dim3(256), 0, h->stream, (const uint8_t*)in, o.p,
                            h->d_first_w, h->d_first_scale, h->d_first_shift, H, W, Cp0, o.C, o.frame_stride(), h->d_range);
     else if (kind == KIND_U8)
@@ -1253,7 +1365,8 @@ int enqueue_first_fused(og_unet* h, const uint8_t* gray, int B, int H, int W) {
     a.tiles_x = (W + 15) / 16;
     a.tiles_y = (H + 7) / 8;
     a.n_spatial = B * a.tiles_x * a.tiles_y;
-    a.wpk = (h->precision == 1) ? L.d_w_h : L.d_w;
+    a.wpk = (h->precision == 2) ? L.d_w_f : (h->precision == 1) ? L.d_w_h : L.d_w;
+    a.k_half = (h->precision == 2) ? 1 : 0;   // 32 input channels: half a 64-channel chunk
     a.scale = L.d_scale;
     a.shift = L.d_shift;
     a.aff_mod = L.Cout_p;
@@ -1273,14 +1386,16 @@ int enqueue_first_fused(og_unet* h, const uint8_t* gray, int B, int H, int W) {
     a.first_scale = h->d_first_scale;
     a.first_shift = h->d_first_shift;
     constexpr int lds = conv_o_lds<1, 0, 8>() + (12 * 20 + 352) * 4;
-    prof_begin(h, "downs.0 (first + second conv fused)", h->precision == 1 ? "k_conv_mfma_h<1,0,8,FIRST>" : "k_conv_mfma_o<1,0,8,FIRST>",
+    prof_begin(h, "downs.0 (first + second conv fused)", h->precision == 2 ? "k_conv_mfma_f<1,0,8,FIRST>" : h->precision == 1 ? "k_conv_mfma_h<1,0,8,FIRST>" : "k_conv_mfma_o<1,0,8,FIRST>",
                2.0 * B * H * W * 9.0 * (1.0 * h->features[0] + (double)h->features[0] * h->features[0]));
     a.zdiv = 1;
     a.zrcp = 1.0f;
     a.zgroup_shift = 0;
     a.frames = B;
-    if (h->precision == 1) a.prio_mode = h->prio_mode;
-    if (h->precision == 1)
+    if (h->precision != 0) a.prio_mode = h->prio_mode;
+    if (h->precision == 2)
+        OG_LAUNCH((k_conv_mfma_f<1, 0, 8, 3, true>), dim3(a.tiles_x, a.tiles_y, B), dim3(256), lds, h->stream, a);
+    else if (h->precision == 1)
         OG_LAUNCH((k_conv_mfma_h<1, 0, 8, 3, true>), dim3(a.tiles_x, a.tiles_y, B), dim3(256), lds, h->stream, a);
     else
         OG_LAUNCH((k_conv_mfma_o<1, 0, 8, 3, true>), dim3(a.tiles_x, a.tiles_y, B), dim3(256), lds, h->stream, a);
@@ -1354,8 +1469,11 @@ int enqueue_head(og_unet* h, int B, int H, int W, float thr, const int32_t* boxe
     const Act& u = h->UB[0];
     const int HW = H * W;
     const int bpf = (HW + 1023) / 1024;
-    prof_begin(h, "head", "k_head", 2.0 * B * HW * h->features[0]);
-    if (h->precision == 1)
+    prof_begin(h, "head", h->precision == 2 ? "k_head_f" : "k_head", 2.0 * B * HW * h->features[0]);
+    if (h->precision == 2)
+        OG_LAUNCH(k_head_f, dim3(B * bpf), dim3(256), 0, h->stream, u.p, u.frame_stride(), u.C, h->d_head_w,
+                           h->head_bias, cp32(h->features[0]), HW, W, thr, boxes, logits, mask, area, bpf);
+    else if (h->precision == 1)
         OG_LAUNCH(k_head<true>, dim3(B * bpf), dim3(256), 0, h->stream, u.p, u.frame_stride(), u.C, h->d_head_w,
                            h->head_bias, cp32(h->features[0]), HW, W, thr, boxes, logits, mask, area, bpf);
     else
@@ -1398,7 +1516,8 @@ int run_chunk(og_unet* h, int kind, const void* in, int B, int H, int W, float t
         key.B = B;
         key.H = H;
         key.W = W;
-        key.flags = (fuse ? 1 : 0) | (ff ? 2 : 0) | (h->precision ? 4 : 0) | (h->wino_chain ? 8 : 0) | (h->active_lanes > 1 ? 16 : 0);
+        key.flags = (fuse ? 1 : 0) | (ff ? 2 : 0) | (h->precision ? 4 : 0) | (h->wino_chain ? 8 : 0) | (h->active_lanes > 1 ? 16 : 0) |
+                    (h->precision == 2 ? 32 : 0);
         key.capB = h->capB;
         auto it = h->graphs.find(key);
         if (it == h->graphs.end()) {
@@ -1427,8 +1546,9 @@ int run_chunk(og_unet* h, int kind, const void* in, int B, int H, int W, float t
 int check_range(og_unet* h) {
     if (h->h_range && *(volatile int*)h->h_range) {
         *(volatile int*)h->h_range = 0;
-        return fail(OG_ERANGE, "split precision: an activation exceeded the f16 range (|v| > 60000); the result of this call is not "
-                               "valid -- use og_unet_set_option(h, \"precision\", 0) for these weights");
+        return fail(OG_ERANGE, std::string(h->precision == 2 ? "f16 mode" : "split precision") +
+                                   ": an activation exceeded the f16 range (|v| > 60000); the result of this call is not "
+                                   "valid -- use og_unet_set_option(h, \"precision\", 0) for these weights");
     }
     return OG_OK;
 }
@@ -2009,12 +2129,15 @@ int og_unet_set_option(og_unet* h, const char* name, int value) {
     else if (n == "dual" && (value == 0 || value == 1)) slot = &h->dual;
     else if (n == "lanes" && value >= 0 && value <= kMaxLanes) slot = &h->n_lanes;
     else if (n == "stream" && (value == 0 || value == 1)) slot = &h->stream_host;
-    else if (n == "precision" && (value == 0 || value == 1)) slot = &h->precision;
+    else if (n == "precision" && value >= 0 && value <= 2) slot = &h->precision;
     else if (n == "h_square" && (value == 0 || value == 1)) slot = &h->h_square;
     if (!slot) return fail(OG_EINVAL, "unknown option or bad value: " + n);
+    if ((slot == &h->precision && value == 2 && h->splitk) || (slot == &h->splitk && value == 1 && h->precision == 2))
+        return fail(OG_EINVAL, "f16 mode (precision 2) never splits K: \"splitk\" 1 and \"precision\" 2 exclude each other");
     if (*slot != value) {
         if (h->stream) HIPCHK(hipStreamSynchronize(h->stream));
         drop_graphs(h);
+        if (slot == &h->precision && (value == 2 || *slot == 2)) h->aH = h->aW = 0;   // other bytes per channel: the next call re-plans the arena
         *slot = value;
     }
     if (h->twin && n != "inject_fault") return og_unet_set_option(h->twin, name, value);   // (the test hook arms the first lane only)
@@ -2572,6 +2695,13 @@ int og_unet_get_activation(og_unet* h, const char* name, int B, float* out, size
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(tmp.data(), a->p, tmp.size() * sizeof(float), hipMemcpyDeviceToHost));
     const size_t HW = (size_t)a->H * a->W;
+    if (h->precision == 2) {   // F layout: channel c of a pixel is the f16 at byte 2c; returned widened to f32
+        const _Float16* t16 = (const _Float16*)tmp.data();
+        for (int b = 0; b < B; ++b)
+            for (int c = 0; c < C; ++c)
+                for (size_t p = 0; p < HW; ++p) out[((size_t)b * C + c) * HW + p] = (float)t16[((size_t)b * HW + p) * a->C * 2 + off + c];
+        return OG_OK;
+    }
     if (h->precision == 1) {   // H layout: channel c of a pixel = hi + lo * 2^-11, hi / lo halves of its 32-channel chunk
         const _Float16* t16 = (const _Float16*)tmp.data();
         for (int b = 0; b < B; ++b)

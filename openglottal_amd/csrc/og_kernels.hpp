@@ -123,6 +123,7 @@ __device__ __forceinline__ unsigned og_lds_addr(const void* p) {
 // channels 8s..8s+7, slot 4+s = lo of the same channels -- so the LDS images, the DMA staging, the swizzles and every
 // store address of the f32 kernels carry over unchanged; only fragment contents and the MFMA differ.
 typedef _Float16 og_h8 __attribute__((ext_vector_type(8)));
+typedef _Float16 og_h4 __attribute__((ext_vector_type(4)));
 constexpr float OG_LO_SCALE = 2048.0f, OG_LO_INV = 1.0f / 2048.0f;
 constexpr float OG_H_MAX = 60000.0f;   // f16 tops out at 65504: an activation beyond this makes the split-precision result worthless
 // one word in host-mapped memory per handle: the epilogue raises it (rare path: one atomic per offending wave), the host
@@ -201,6 +202,7 @@ struct ConvArgs {
     unsigned long long* stamps;  // diagnostic only (nullptr in production): per workgroup
                                  // k_conv_mfma_p: 4 x u64 {s_memtime, s_memrealtime} at entry and exit -> in-kernel clock
                                  // k_conv_mfma_o: 8 x u64 {entry, prologue done, main loop done, stores done, HW_ID, XCC_ID}
+    int k_half;             // k_conv_mfma_f only: n_chunks counts 64-channel chunks and the last one holds 32 channels
 };
 
 // MODE 0: 3x3 conv, pad 1, stride 1  (+ per-channel affine, ReLU, optional 2x2 max-pool)
@@ -2609,6 +2611,416 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_h(ConvArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------
+// f16 mode ("precision" 2): f16 operands, f32 accumulation, activations stored as 2 bytes.
+// "F layout": NHWC f16, channels padded to 32 -- a pixel of a C-channel tensor is 2C bytes (a multiple of 64), channel c at
+// byte 2c.  Every stride and channel offset in ConvArgs stays in 4-BYTE UNITS (C / 2 per pixel), so the byte arithmetic of the
+// f32 / H kernels (x 4) carries over.  The K loop walks 64-channel chunks: 128 bytes per pixel = eight 16-byte slots, slot s =
+// channels 8s..8s+7 of the chunk, i.e. the halo image, the LDS-DMA staging, og_halo_swz and the fragment addresses ("k-group j ->
+// slot 2j + lh") of k_conv_mfma_h unchanged; a (chunk, tap) step is 4 MFMAs on ONE accumulator per sub-tile pair, no `cor`.
+// A layer whose padded Cin is an odd multiple of 32 (a.k_half) has a half last chunk: 2 MFMAs per tap there, and when it is the
+// only chunk (the two 32-channel 256x256 layers) only the 64 live bytes per pixel are fetched (the other DMA lanes carry OG_OOB).
+// The concat stays free: skip half and up-sampled half are two byte ranges of the consumer's pixel row.
+// ---------------------------------------------------------------------------------------
+// Epilogue: BN scale / shift (+ ReLU) in f32, ONE rounding to f16, through the wave's LDS scratch (32 pixel rows x 64 bytes) and
+// out in 16-byte stores of 8 channels (two rounds of 64 lanes per 32-pixel sub-tile).  Pooled tile: max of the f32 values,
+// rounded (max commutes with rounding), 8 windows x 64 bytes on lanes 0..31.  Fused head: reads the ROUNDED values back as f32,
+// 4 channels per lane in k_head_f's order, so fused and unfused heads give the same bits.
+template <int NT, int MODE, int TH, int ACT, int MS>
+__device__ __forceinline__ void conv_epilogue_f(const ConvArgs& a, const f32x16* acc, int n_tile, int b, int ty0, int tx0, int wm, int wn,
+                                                int li, int lh, float sc, float sh, unsigned char* scratch) {
+    constexpr int WROWS = 32 * NT;
+    const int lane = li + 32 * lh;
+    const int ncol0 = n_tile * WROWS + wn * 32;
+    int cbase = ncol0, qd = 0;
+    if (MODE == 1) {
+        qd = ncol0 / a.aff_mod;
+        cbase = ncol0 - qd * a.aff_mod;
+    }
+    const int cb4 = cbase >> 1;   // this wave's first channel in 4-byte units
+    const int OW = (MODE == 1) ? 2 * a.W : a.W;
+    // store role: tile-image row (lane >> 2) + 16 q2, 16-byte slot lane & 3; row i sits at x = 2((i&7)>>2) + (i&1) + 4(i>>3), y = (i&3)>>1
+    const int srow = lane >> 2, sslot = lane & 3;
+    const int sxl = 2 * ((srow & 7) >> 2) + (srow & 1) + 4 * (srow >> 3), syl = (srow & 3) >> 1;
+    // head role (as conv_epilogue_b): row (lane >> 3) + 8 q, channels 4 (lane & 7) ..
+    const int rrow = lane >> 3, hk = lane & 7;
+    const int xl = 2 * (rrow >> 2) + (rrow & 1), yl = (rrow & 3) >> 1;
+    const bool fuse_head = (MODE == 0 && NT == 1 && a.head_w != nullptr);
+    const bool store_act = !fuse_head || a.head_store_act;
+
+    const __amdgpu_buffer_rsrc_t out_rs = og_rsrc(a.out + (long long)b * a.out_frame_stride, (unsigned)a.out_frame_stride * 4u);
+    const unsigned lp = (MODE == 1) ? (unsigned)(((2 * syl * OW + 2 * sxl) * a.out_pix_stride + sslot * 4) * 4)
+                                    : (unsigned)(((syl * OW + sxl) * a.out_pix_stride + sslot * 4) * 4);
+    unsigned vq[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) vq[q] = (tx0 + sxl + 8 * q < a.W) ? lp : OG_OOB;
+
+    _Float16* const hw = (_Float16*)scratch + (128 * lh + li);   // + (8g + rr) * 32: row 8g + 4lh + rr, channel li
+    const unsigned char* const sr = scratch + srow * 64 + sslot * 16;   // + q * 1024
+    __amdgpu_buffer_rsrc_t pool_rs = out_rs;
+    unsigned vpool = 0;
+    const bool pool = (MODE == 0 && a.pool != nullptr);
+    if (pool) {
+        pool_rs = og_rsrc(a.pool + (long long)b * a.pool_frame_stride, (unsigned)a.pool_frame_stride * 4u);
+        vpool = (lane < 32 && tx0 + 2 * srow < a.W) ? (unsigned)((srow * a.pool_pix_stride + sslot * 4) * 4) : OG_OOB;
+    }
+    f32x4 wv = {0.f, 0.f, 0.f, 0.f};
+    int hbx1 = 0, hby1 = 0, hbx2 = 1 << 30, hby2 = 1 << 30, head_cnt = 0;
+    unsigned vh = OG_OOB;
+    if (fuse_head) {
+        wv = *(const f32x4*)(a.head_w + hk * 4);
+        if (a.head_boxes != nullptr) {
+            hbx1 = a.head_boxes[b * 4 + 0];
+            hby1 = a.head_boxes[b * 4 + 1];
+            hbx2 = a.head_boxes[b * 4 + 2];
+            hby2 = a.head_boxes[b * 4 + 3];
+            if (hbx1 < 0) { hbx1 = hby1 = hbx2 = hby2 = 0; }
+        }
+        if (hk < 4 && tx0 + xl + 4 * hk < a.W) vh = (unsigned)(yl * a.W + xl + 4 * hk);
+    }
+
+    float h_absmax = 0.f;
+#pragma unroll
+    for (int m = 0; m < MS; ++m) {
+        const int ms = wm * MS + m;
+        const int y0 = ty0 + 2 * ms;
+        float vmaxs[4];
+        const f32x2 sc2 = {sc, sc}, sh2 = {sh, sh};
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x2 a01 = og_fma2(f32x2{acc[m][4 * g], acc[m][4 * g + 1]}, sc2, sh2);
+            const f32x2 a23 = og_fma2(f32x2{acc[m][4 * g + 2], acc[m][4 * g + 3]}, sc2, sh2);
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                float v = (rr == 0) ? a01.x : (rr == 1) ? a01.y : (rr == 2) ? a23.x : a23.y;
+                if (ACT == 1) v = fmaxf(v, 0.f);
+                h_absmax = fmaxf(h_absmax, fabsf(v));
+                hw[(8 * g + rr) * 32] = (_Float16)v;
+                vmaxs[g] = (rr == 0) ? v : fmaxf(vmaxs[g], v);
+            }
+        }
+        asm volatile("" ::: "memory");   // the 2-byte writes above are read back as 16 / 8-byte words below (and vice versa in the next round)
+        if (y0 < a.H) {
+            if (store_act) {
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const f32x4 v4 = *(const f32x4*)(sr + q * 1024);
+                    const int so = (MODE == 1) ? (((2 * y0 + (qd >> 1)) * OW + 2 * (tx0 + 8 * q) + (qd & 1)) * a.out_pix_stride + a.out_ch_off + cb4) * 4
+                                               : ((y0 * OW + tx0 + 8 * q) * a.out_pix_stride + a.out_ch_off + cb4) * 4;
+                    og_buffer_store16(v4, out_rs, vq[q], (unsigned)so);
+                }
+            }
+            if (MODE == 0 && NT == 1 && fuse_head) {
+                float sd[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const og_h4 hv = *(const og_h4*)(scratch + (rrow + 8 * q) * 64 + hk * 8);
+                    float sdot = 0.f;
+                    sdot = fmaf((float)hv.x, wv.x, sdot);
+                    sdot = fmaf((float)hv.y, wv.y, sdot);
+                    sdot = fmaf((float)hv.z, wv.z, sdot);
+                    sdot = fmaf((float)hv.w, wv.w, sdot);
+                    sdot += __shfl_xor(sdot, 1);
+                    sdot += __shfl_xor(sdot, 2);
+                    sdot += __shfl_xor(sdot, 4);
+                    sd[q] = sdot;
+                }
+                const float mine = (hk == 0) ? sd[0] : (hk == 1) ? sd[1] : (hk == 2) ? sd[2] : sd[3];
+                const float lg = mine + a.head_bias;
+                const float prob = 1.0f / (1.0f + expf(-lg));
+                const bool on = prob > a.head_thr;
+                const int x = tx0 + xl + 4 * hk, y = y0 + yl;
+                const bool counted = on && vh != OG_OOB && x >= hbx1 && x < hbx2 && y >= hby1 && y < hby2;
+                head_cnt += __builtin_popcountll(__ballot(counted));
+                const unsigned so = (unsigned)(y0 * a.W + tx0);
+                if (a.head_logits) {
+                    const __amdgpu_buffer_rsrc_t lrs = og_rsrc(a.head_logits + (long long)b * a.H * a.W, (unsigned)(a.H * a.W) * 4u);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, lg), lrs, (vh == OG_OOB) ? OG_OOB : vh * 4u, so * 4u, 0);
+                }
+                if (a.head_mask) {
+                    const __amdgpu_buffer_rsrc_t mrs = og_rsrc(a.head_mask + (long long)b * a.H * a.W, (unsigned)(a.H * a.W));
+                    __builtin_amdgcn_raw_buffer_store_b8((unsigned char)(on ? 255 : 0), mrs, vh, so, 0);
+                }
+            }
+            if (pool) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) ((_Float16*)scratch)[1024 + (2 * g + lh) * 32 + li] = (_Float16)vmaxs[g];   // window 2g + lh
+                asm volatile("" ::: "memory");
+                const f32x4 p4 = *(const f32x4*)(scratch + 2048 + (lane & 31) * 16);
+                const int so = (((y0 >> 1) * (a.W >> 1) + (tx0 >> 1)) * a.pool_pix_stride + a.pool_ch_off + cb4) * 4;
+                og_buffer_store16(p4, pool_rs, vpool, (unsigned)so);
+            }
+        }
+        asm volatile("" ::: "memory");
+    }
+    og_flag_range(h_absmax, a.range_flag);
+    if (MODE == 0 && NT == 1 && fuse_head && a.head_area != nullptr) {
+        if (lane == 0) {
+            const int tile = (ty0 / TH) * a.tiles_x + (tx0 >> 4);
+            a.head_area[((long long)b * a.tiles_x * a.tiles_y + tile) * 4 + (wm * NT + wn)] = head_cnt;
+        }
+    }
+}
+
+// The f16-mode conv (MODE 0: 3x3 conv, MODE 1: 2x2 stride-2 transposed conv): k_conv_mfma_h's tiles, staging, weight ring and
+// counted waits, one v_mfma_f32_32x32x16_f16 per 16 k-values, fixed K order (chunk-major, tap-minor), no split-K.
+// Opt-in ("precision" 2).  SQ as in k_conv_mfma_h: 2 row sub-tiles x both column sub-tiles per wave.
+template <int NT, int MODE, int TH, int OCC, bool FIRST = false, bool SQ = false>
+__global__ __launch_bounds__(256, OCC) void k_conv_mfma_f(ConvArgs a) {
+    static_assert(MODE == 0 || MODE == 1, "f16 mode: 3x3 conv and transposed conv only");
+    static_assert(!SQ || (NT == 2 && TH == 16 && !FIRST), "square wave tiles: 64-column kernel on 16x16 tiles");
+    constexpr int TW = 16;
+    constexpr int PAD = (MODE == 0) ? 1 : 0;
+    constexpr int HW_ = TW + 2 * PAD;
+    constexpr int HH_ = TH + 2 * PAD;
+    constexpr int HALO_PIX = HW_ * HH_;
+    constexpr int HALO_BYTES = HALO_PIX * 128;
+    constexpr int HALO_PIECES = HALO_PIX * 8;
+    constexpr int HALO_IT = (HALO_PIECES + 255) / 256;
+    constexpr int TAPS = (MODE == 0) ? 9 : 1;
+    constexpr int WROWS = 32 * NT;
+    constexpr int WBYTES = WROWS * 128;
+    constexpr int NSTG = (MODE == 0) ? 3 : 2;
+    constexpr int WAHEAD = (NSTG == 3) ? 2 : 1;   // weight slices two steps ahead (a step is at most 16 MFMAs of 32 cycles per wave)
+    constexpr int WM = SQ ? 4 : 4 / NT;
+    constexpr int NC = SQ ? 2 : 1;
+    constexpr int MS = (TH / 2) / WM;
+    static_assert(MS >= 1, "tile too small");
+
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* const halo0 = smem;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wn = SQ ? 0 : wave % NT;
+    const int wm = SQ ? wave : wave / NT;
+    const int li = lane & 31;
+    const int lh = lane >> 5;
+    if (a.prio_mode == 3) __builtin_amdgcn_s_setprio(3);
+
+    // ---- tile decode (scalar): grid = (tile column, tile row, frame group x column tile x frame in group), as k_conv_mfma_o ----
+    const int bz = (int)blockIdx.z;
+    const int gz = a.zdiv << a.zgroup_shift;
+    const int q = (gz == 1) ? bz : (int)(((float)bz + 0.5f) * a.zrcp);
+    const int rz = bz - q * gz;
+    const int n_tile = rz >> a.zgroup_shift;
+    const int b = (q << a.zgroup_shift) + (rz & ((1 << a.zgroup_shift) - 1));
+    if (b >= a.frames) return;   // tail of the last frame group (whole workgroup, before any barrier)
+    const int ty0 = (int)blockIdx.y * TH;
+    const int tx0 = (int)blockIdx.x * TW;
+    const int n_chunks = a.n_chunks;          // 64-channel chunks; the last one holds 32 channels when a.k_half
+    const int n_steps = n_chunks * TAPS;
+    const bool only_half = (a.k_half != 0 && n_chunks == 1);
+
+    const og_i32x4 in_rsrc = og_make_rsrc(a.in + (long long)b * a.in_frame_stride + a.in_ch_off,
+                                          (unsigned)(a.in_frame_stride - a.in_ch_off) * 4u);
+
+    unsigned hoff[HALO_IT];
+    {
+        int hy = ((tid >> 3) >= HW_) ? 1 : 0;
+        int hx = (tid >> 3) - hy * HW_;
+        const int row_b = a.W * a.in_pix_stride * 4;
+        const int col_b = a.in_pix_stride * 4;
+#pragma unroll
+        for (int it = 0; it < HALO_IT; ++it) {
+            const int logical = (tid & 7) ^ og_halo_swz(hy, hx);
+            const int gy = ty0 + hy - PAD, gx = tx0 + hx - PAD;
+            const bool inb = (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W && !(only_half && logical >= 4);
+            hoff[it] = inb ? (unsigned)(gy * row_b + gx * col_b + logical * 16) : OG_OOB;
+            hx += 32 % HW_;
+            hy += 32 / HW_;
+            if (hx >= HW_) { hx -= HW_; hy += 1; }
+        }
+    }
+    const bool last_valid = ((HALO_IT - 1) * 256 + tid) < HALO_PIECES;
+
+    const unsigned lds0 = og_lds_addr(smem);
+    auto stage_halo = [&](int c) {
+        const unsigned base = lds0 + wave * 1024;
+#pragma unroll
+        for (int it = 0; it < HALO_IT; ++it) {
+            if (it < HALO_IT - 1 || last_valid) glds16b(hoff[it], in_rsrc, (unsigned)c * 128u, base + it * 4096);
+        }
+    };
+    const og_i32x4 w_rsrc = og_make_rsrc(a.wpk + (long long)n_tile * n_steps * (WROWS * 32), (unsigned)n_steps * WBYTES);
+    const unsigned woff = (unsigned)tid * 16u;
+    auto stage_w = [&](int stage, int step) {
+        const unsigned base = lds0 + HALO_BYTES + stage * WBYTES + wave * 1024;
+#pragma unroll
+        for (int i = 0; i < NT; ++i) glds16b(woff, w_rsrc, (unsigned)step * WBYTES + i * 4096, base + i * 4096);
+    };
+
+    if (!FIRST) {
+        stage_halo(0);
+        stage_w(0, 0);
+        if (WAHEAD == 2 && 1 < n_steps) stage_w(1, 1);
+    }
+
+    // ---- fragment addressing: k_conv_mfma_h's ----
+    const int px0 = 2 * (li >> 2) + (li & 1);
+    const int pyl = (li >> 1) & 1;
+    const int brow = wn * 32 + li;
+    const int boff = brow * 128 + ((lh ^ ((brow >> 1) & 7)) << 4);
+    constexpr int NDX = (MODE == 0) ? 3 : 1;
+    unsigned abase[NDX][4];
+#pragma unroll
+    for (int dx = 0; dx < NDX; ++dx) {
+        const int px = px0 + dx;
+        const unsigned o = (unsigned)((pyl * HW_ + px) * 128 + ((lh ^ og_halo_swz(pyl, px)) << 4) + wm * (MS * 2 * HW_ * 128));
+#pragma unroll
+        for (int pat = 0; pat < 4; ++pat) {
+            abase[dx][pat] = lds0 + (o ^ (unsigned)(pat << 5));
+            asm volatile("" : "+v"(abase[dx][pat]));
+        }
+    }
+    unsigned bbase[4];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+        bbase[jj] = lds0 + HALO_BYTES + (unsigned)(boff ^ (jj << 5));
+        asm volatile("" : "+v"(bbase[jj]));
+    }
+
+    float esc[NC], esh[NC];
+#pragma unroll
+    for (int n = 0; n < NC; ++n) {
+        const int ecol = n_tile * WROWS + (wn + n) * 32 + li;
+        const int eco = (MODE == 1) ? ecol % a.aff_mod : ecol;
+        esc[n] = a.scale[eco];
+        esh[n] = a.shift[eco];
+    }
+
+    f32x16 acc[NC][MS];
+#pragma unroll
+    for (int n = 0; n < NC; ++n)
+#pragma unroll
+        for (int m = 0; m < MS; ++m)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[n][m][r] = 0.f;
+
+    if (FIRST) {
+        // halo tile of the first layer's OUTPUT, computed here (k_conv_first's fma chain), rounded to f16 once and written in the
+        // swizzled image the LDS-DMA would have produced: 32 channels = slots 0..3 of the (half) chunk
+        float* patch = (float*)(smem + HALO_BYTES + NSTG * WBYTES);  // [HH_+2][HW_+2]
+        float* fw = patch + (HH_ + 2) * (HW_ + 2);                // w9[9][32] | scale[32] | shift[32]
+        const uint8_t* fin = a.first_u8 + (long long)b * a.H * a.W;
+        for (int i = tid; i < (HH_ + 2) * (HW_ + 2); i += 256) {
+            const int hy = i / (HW_ + 2), hx = i - hy * (HW_ + 2);
+            const int gy = ty0 + hy - 2, gx = tx0 + hx - 2;
+            patch[i] = (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) ? (float)fin[(long long)gy * a.W + gx] / 255.0f : 0.f;
+        }
+        for (int i = tid; i < 352; i += 256) fw[i] = (i < 288) ? a.first_w9[i] : (i < 320 ? a.first_scale[i - 288] : a.first_shift[i - 320]);
+        stage_w(0, 0);
+        if (WAHEAD == 2 && 1 < n_steps) stage_w(1, 1);
+        __syncthreads();
+        float first_absmax = 0.f;
+        for (int q2 = tid; q2 < HALO_PIX * 4; q2 += 256) {
+            const int p = q2 >> 2, L = q2 & 3;
+            const int hy = p / HW_, hx = p - hy * HW_;
+            const int gy = ty0 + hy - 1, gx = tx0 + hx - 1;
+            _Float16 hv[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) hv[e] = (_Float16)0.f;   // outside the image: the second conv's zero padding
+            if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) {
+                float sacc[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) sacc[e] = 0.f;
+#pragma unroll
+                for (int t = 0; t < 9; ++t) {
+                    const float xv = patch[(hy + t / 3) * (HW_ + 2) + hx + t % 3];
+                    const f32x4 w0 = *(const f32x4*)(fw + t * 32 + 8 * L), w1 = *(const f32x4*)(fw + t * 32 + 8 * L + 4);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        sacc[e] = fmaf(xv, w0[e], sacc[e]);
+                        sacc[4 + e] = fmaf(xv, w1[e], sacc[4 + e]);
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float v = fmaxf(fmaf(sacc[e], fw[288 + 8 * L + e], fw[320 + 8 * L + e]), 0.f);
+                    hv[e] = (_Float16)v;
+                    first_absmax = fmaxf(first_absmax, v);
+                }
+            }
+            *(f32x4*)(halo0 + p * 128 + ((L ^ og_halo_swz(hy, hx)) << 4)) = og_pack8(hv);
+        }
+        og_flag_range(first_absmax, a.range_flag);
+    }
+    og_wait_dma();
+    __syncthreads();
+    if (a.prio_mode == 3) __builtin_amdgcn_s_setprio(0);
+
+    int step = 0;   // absolute (chunk, tap) index = the weight block's index (stage = step % 3 = t % 3: 9 taps per chunk)
+    for (int c = 0; c < n_chunks; ++c) {
+        const bool half = (a.k_half != 0 && c == n_chunks - 1);   // wave-uniform: k-groups 2, 3 of this chunk do not exist
+#pragma unroll
+        for (int t = 0; t < TAPS; ++t) {
+            const int stg = (NSTG == 3) ? t % 3 : (step & 1), stg_next = (NSTG == 3) ? (t + WAHEAD) % 3 : ((step + 1) & 1);
+            const bool more = (step + WAHEAD < n_steps);
+            if (more) stage_w(stg_next, step + WAHEAD);
+
+            const unsigned wb = (unsigned)stg * WBYTES;
+            const int dy = (MODE == 0) ? t / 3 : 0;
+            const int dx = (MODE == 0) ? t % 3 : 0;
+            // k-group j -> 16-byte slot 2j + lh of the 128-byte row = channels 16j + 8lh .. +7 of the chunk
+            if (!half) {
+                f32x4 bv[NC][4];
+#pragma unroll
+                for (int n = 0; n < NC; ++n)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) bv[n][j] = og_lds_read16(bbase[j] + wb + (unsigned)(n * 4096));
+#pragma unroll
+                for (int m = 0; m < MS; ++m) {
+                    f32x4 av[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) av[j] = og_lds_read16(abase[dx][j ^ ((dy & 1) << 1)] + (unsigned)((dy + 2 * m) * (HW_ * 128)));
+#pragma unroll
+                    for (int n = 0; n < NC; ++n)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            acc[n][m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(og_h8, av[j]), __builtin_bit_cast(og_h8, bv[n][j]), acc[n][m], 0, 0, 0);
+                }
+            } else {
+                f32x4 bv[NC][2];
+#pragma unroll
+                for (int n = 0; n < NC; ++n)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) bv[n][j] = og_lds_read16(bbase[j] + wb + (unsigned)(n * 4096));
+#pragma unroll
+                for (int m = 0; m < MS; ++m) {
+                    f32x4 av[2];
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) av[j] = og_lds_read16(abase[dx][j ^ ((dy & 1) << 1)] + (unsigned)((dy + 2 * m) * (HW_ * 128)));
+#pragma unroll
+                    for (int n = 0; n < NC; ++n)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            acc[n][m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(og_h8, av[j]), __builtin_bit_cast(og_h8, bv[n][j]), acc[n][m], 0, 0, 0);
+                }
+            }
+            // the NEXT step's slice must have landed; the one staged just now (NT instructions per wave) may stay in flight
+            if (WAHEAD == 2 && more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NT) : "memory");
+            else og_wait_dma();
+            __syncthreads();
+            ++step;
+        }
+        if (c + 1 < n_chunks) {  // every read of the halo buffer completed before the barrier above
+            stage_halo(c + 1);
+            og_wait_dma();
+            __syncthreads();
+        }
+    }
+
+    if (a.prio_mode == 3) __builtin_amdgcn_s_setprio(3);
+    // ---- epilogue (all staging buffers are dead behind the last barrier: LDS is scratch now) ----
+    unsigned char* const scr = smem + wave * 5120;
+#pragma unroll
+    for (int n = 0; n < NC; ++n) {
+        if (a.act == 1) conv_epilogue_f<NT, MODE, TH, 1, MS>(a, acc[n], n_tile, b, ty0, tx0, wm, wn + n, li, lh, esc[n], esh[n], scr);
+        else conv_epilogue_f<NT, MODE, TH, 0, MS>(a, acc[n], n_tile, b, ty0, tx0, wm, wn + n, li, lh, esc[n], esh[n], scr);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // Generation 2 of the implicit-GEMM conv: PERSISTENT workgroups walking a flat sequence of
 // (item = (n_tile, frame, spatial tile), 32-channel chunk, tap-group) steps.
 //   * the next step's weight slices and the next unit's halo (possibly of the NEXT tile) are
@@ -3076,6 +3488,108 @@ __global__ __launch_bounds__(256) void k_head(const float* __restrict__ in, long
                 s = fmaf(xv.y, wv.y, s);
                 s = fmaf(xv.z, wv.z, s);
                 s = fmaf(xv.w, wv.w, s);
+            }
+            s += __shfl_xor(s, 1);
+            s += __shfl_xor(s, 2);
+            s += __shfl_xor(s, 4);
+            if (cq == 0) {
+                const float lg = s + bias;
+                const float prob = 1.0f / (1.0f + expf(-lg));
+                const bool on = prob > threshold;
+                if (logits) logits[(long long)b * HW + p] = lg;
+                if (mask) mask[(long long)b * HW + p] = on ? 255 : 0;
+                const int y = p / W, x = p - y * W;
+                cnt += (on && x >= bx1 && x < bx2 && y >= by1 && y < by2) ? 1 : 0;
+            }
+        }
+    }
+    if (area != nullptr) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+        if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&area[b], cnt);
+    }
+}
+
+// f16 mode: k_conv_first's fma chain per channel, output rounded to f16 once and stored in the F layout (channel c at byte 2c
+// of the pixel; out_pix_stride / out_frame_stride in 4-byte units).  Lane cq writes the 16 bytes of channels 8cq..8cq+7 (+64 ..).
+template <typename IN_T>
+__global__ __launch_bounds__(256) void k_conv_first_f(const IN_T* __restrict__ in, float* __restrict__ out, const float* __restrict__ w9,
+                                                      const float* __restrict__ scale, const float* __restrict__ shift, int H, int W, int Cp,
+                                                      int out_pix_stride, long long out_frame_stride, int* range_flag) {
+    __shared__ float tile[18][20];
+    float first_absmax = 0.f;
+    const int tiles_x = (W + 15) >> 4, tiles_y = (H + 15) >> 4;
+    int sp = blockIdx.x;
+    const int b = sp / (tiles_x * tiles_y);
+    sp -= b * tiles_x * tiles_y;
+    const int ty0 = (sp / tiles_x) * 16, tx0 = (sp % tiles_x) * 16;
+    const IN_T* fin = in + (long long)b * H * W;
+    for (int q = threadIdx.x; q < 18 * 18; q += 256) {
+        const int hy = q / 18, hx = q - hy * 18;
+        const int gy = ty0 + hy - 1, gx = tx0 + hx - 1;
+        float v = 0.f;
+        if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+            if (sizeof(IN_T) == 1)
+                v = (float)fin[(long long)gy * W + gx] / 255.0f;
+            else
+                v = (float)fin[(long long)gy * W + gx];
+        }
+        tile[hy][hx] = v;
+    }
+    __syncthreads();
+    const int cq = threadIdx.x & 7;
+    float* fout = out + (long long)b * out_frame_stride;
+    for (int c8 = cq * 8; c8 < Cp; c8 += 64) {
+        for (int pp = threadIdx.x >> 3; pp < 256; pp += 32) {
+            const int py = pp >> 4, px = pp & 15;
+            const int y = ty0 + py, x = tx0 + px;
+            _Float16 hv[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                float sv = 0.f;
+#pragma unroll
+                for (int t = 0; t < 9; ++t) sv = fmaf(tile[py + t / 3][px + t % 3], w9[t * Cp + c8 + e], sv);
+                const float v = fmaxf(fmaf(sv, scale[c8 + e], shift[c8 + e]), 0.f);
+                hv[e] = (_Float16)v;
+                first_absmax = fmaxf(first_absmax, v);
+            }
+            if (y < H && x < W) *(f32x4*)(fout + ((long long)y * W + x) * out_pix_stride + (c8 >> 1)) = og_pack8(hv);
+        }
+    }
+    og_flag_range(first_absmax, range_flag);
+}
+
+// f16 mode: k_head on an F-layout input (the stored f16 values widened to f32; lane cq takes channels 4cq..4cq+3 (+32 ..) in
+// k_head's order, which is also the fused head's).  in_pix_stride / in_frame_stride in 4-byte units.
+__global__ __launch_bounds__(256) void k_head_f(const float* __restrict__ in, long long in_frame_stride, int in_pix_stride,
+                                                const float* __restrict__ w, float bias, int Cp, int HW, int W, float threshold,
+                                                const int32_t* __restrict__ boxes, float* __restrict__ logits, uint8_t* __restrict__ mask,
+                                                int32_t* __restrict__ area, int blocks_per_frame) {
+    const int b = blockIdx.x / blocks_per_frame;
+    const int blk = blockIdx.x - b * blocks_per_frame;
+    const int cq = threadIdx.x & 7;
+    const float* fin = in + (long long)b * in_frame_stride;
+    int bx1 = 0, by1 = 0, bx2 = 1 << 30, by2 = 1 << 30;
+    if (boxes != nullptr) {
+        bx1 = boxes[b * 4 + 0];
+        by1 = boxes[b * 4 + 1];
+        bx2 = boxes[b * 4 + 2];
+        by2 = boxes[b * 4 + 3];
+        if (bx1 < 0) { bx2 = 0; by2 = 0; bx1 = 0; by1 = 0; }
+    }
+    int cnt = 0;
+    const int pix_per_block = 1024;
+    for (int pp = threadIdx.x >> 3; pp < pix_per_block; pp += 32) {
+        const int p = blk * pix_per_block + pp;
+        if (p < HW) {
+            float s = 0.f;
+            for (int c = cq * 4; c < Cp; c += 32) {
+                const og_h4 xv = *(const og_h4*)((const _Float16*)(fin + (long long)p * in_pix_stride) + c);
+                const f32x4 wv = *(const f32x4*)(w + c);
+                s = fmaf((float)xv.x, wv.x, s);
+                s = fmaf((float)xv.y, wv.y, s);
+                s = fmaf((float)xv.z, wv.z, s);
+                s = fmaf((float)xv.w, wv.w, s);
             }
             s += __shfl_xor(s, 1);
             s += __shfl_xor(s, 2);

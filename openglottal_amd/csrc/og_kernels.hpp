@@ -85,6 +85,38 @@ __device__ __forceinline__ void glds16b(unsigned voff, og_i32x4 rsrc, unsigned s
         : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_wave_base)
         : "memory");
 }
+// glds16b for k_conv_wino's chunk loop, where every instruction between two MFMAs takes issue time from the matrix pipe: M0 is an
+// INPUT register of the asm ("{m0}"), so hipcc writes it itself -- one s_mov / s_add straight into M0 -- and nothing saves or
+// restores it (no ds_* instruction reads M0 on gfx9+; hipcc keeps M0 reserved and sets it in front of each of its own uses).  The
+// s_nop is the wait state between an M0 write and its LDS-DMA use.
+// PAD = one more scalar instruction BEHIND the transfer, which is what glds16b's M0 restore amounts to: without it hipcc is free to
+// overwrite an operand register of the transfer in the very next instruction.  It did so in every kernel family when glds16b
+// itself was written this way (the per-lane address pair of the flat form, SGPR offsets of this form), and the direct-form
+// kernels then raised a memory access fault; glds16 / glds16b therefore keep their restore.  PAD = false is for call sites
+// whose operands outlive the transfer by construction (loop-invariant lane offsets, running offsets bumped at the group's end):
+// tools/isa_wino_loop.py checks that no transfer of k_conv_wino is followed by a write of one of its registers.
+template <bool PAD>
+__device__ __forceinline__ void glds16b_m0(unsigned voff, og_i32x4 rsrc, unsigned soff, unsigned lds_wave_base) {
+    if (PAD)
+        asm volatile("s_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds\n\ts_nop 0" : : "v"(voff), "s"(rsrc), "s"(soff), "{m0}"(lds_wave_base) : "memory");
+    else
+        asm volatile("s_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" : : "v"(voff), "s"(rsrc), "s"(soff), "{m0}"(lds_wave_base) : "memory");
+}
+// the same for the lanes of `mask` only (a wave-uniform EXEC image, e.g. a ballot taken once): the other lanes neither read nor
+// WRITE LDS -- a predicate without a branch.  The s_and_saveexec stands in the wait state between the M0 write and the transfer,
+// the EXEC restore behind it.
+__device__ __forceinline__ void glds16b_m0_masked(unsigned voff, og_i32x4 rsrc, unsigned soff, unsigned lds_wave_base, unsigned long long mask) {
+    unsigned long long keep;
+    asm volatile(
+        "s_and_saveexec_b64 %0, %4\n\t"
+        "buffer_load_dwordx4 %1, %2, %3 offen lds\n\t"
+        "s_mov_b64 exec, %0"
+        : "=&s"(keep)
+        : "v"(voff), "s"(rsrc), "s"(soff), "s"(mask), "{m0}"(lds_wave_base)
+        : "memory", "scc");
+}
+// compile-time int / bool as a function argument (generic lambdas: the chunk body of k_conv_wino is instantiated per value)
+template <int V> struct og_const { static constexpr int value = V; };
 __device__ __forceinline__ float og_act(float v, int act) {
     if (act == 1) return fmaxf(v, 0.f);
     if (act == 2) return v / (1.0f + expf(-v));  // SiLU = x * sigmoid(x)
@@ -1189,22 +1221,32 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino(ConvArgs a) {
             if (r >= RP) { r -= RP; hy += 1; }
         }
     }
-    const bool last_valid = ((RAW_IT - 1) * 256 + tid) < RAW_PIECES;
+    // the last raw piece is partial (RAW_PIECES is no multiple of 256) and its idle lanes would land in V: they are masked off
+    // through EXEC (one ballot, kept in an SGPR pair), not through a branch around the transfer
+    const unsigned long long last_mask = __builtin_amdgcn_ballot_w64(((RAW_IT - 1) * 256 + tid) < RAW_PIECES);
     const unsigned lds0 = og_lds_addr(smem);
     const int n_ck = a.n_chunks * (32 / KC);
     const og_i32x4 w_rsrc = og_make_rsrc(a.wpk + (long long)n_tile * n_ck * (16 * UP_BYTES / 4), (unsigned)n_ck * (16u * UP_BYTES));
-    auto u_piece = [&](int stage, int grp, int i) {
-        const unsigned base = __builtin_amdgcn_readfirstlane(lds0 + RAW_BYTES + V_BYTES + stage * UG_BYTES + wave * 1024);
-        glds16b((unsigned)tid * 16u, w_rsrc, (unsigned)grp * UG_BYTES + i * 4096, base + i * 4096);
+    // both DMA streams advance through ONE wave-uniform byte offset each (the buffer instruction's SGPR offset): wso = the U group
+    // to fetch next, hso = the chunk whose halo is fetched next; bumped once per group / chunk, nothing is re-derived per transfer
+    const unsigned woff = (unsigned)tid * 16u;
+    const unsigned ubase = __builtin_amdgcn_readfirstlane(lds0 + RAW_BYTES + V_BYTES + wave * 1024);
+    const unsigned hbase = __builtin_amdgcn_readfirstlane(lds0 + wave * 1024);
+    unsigned wso = 0, hso = 0;
+    // (PAD: the back-to-back transfers of the prologue, where hipcc forms the next offset right behind a transfer; not in the loop)
+    auto u_piece = [&](auto pad_, int stage, int i) {
+        glds16b_m0<decltype(pad_)::value != 0>(woff, w_rsrc, wso + i * 4096, ubase + stage * UG_BYTES + i * 4096);
     };
-    auto raw_piece = [&](int ck, int it) {
-        const unsigned base = __builtin_amdgcn_readfirstlane(lds0 + wave * 1024);
-        if (it < RAW_IT - 1 || last_valid) glds16b(hoff[it], in_rsrc, (unsigned)ck * PB, base + it * 4096);
+    auto raw_piece = [&](auto pad_, int it) {
+        if (it < RAW_IT - 1) glds16b_m0<decltype(pad_)::value != 0>(hoff[it], in_rsrc, hso, hbase + it * 4096);
+        else glds16b_m0_masked(hoff[it], in_rsrc, hso, hbase + it * 4096, last_mask);
     };
 #pragma unroll
-    for (int it = 0; it < RAW_IT; ++it) raw_piece(0, it);
+    for (int it = 0; it < RAW_IT; ++it) raw_piece(og_const<1>{}, it);
 #pragma unroll
-    for (int i = 0; i < U_IT; ++i) u_piece(0, 0, i);
+    for (int i = 0; i < U_IT; ++i) u_piece(og_const<1>{}, 0, i);
+    wso = UG_BYTES;
+    hso = PB;
     if (st != nullptr && tid == 0) st[1] = __builtin_amdgcn_s_memtime();   // first DMAs issued
 
     // Fragment addressing.  MFMA row i of a wave = window (row 4 wm + (i & 3), column wx = 2 (i >> 3) + ((i >> 2) & 1)).
@@ -1267,11 +1309,11 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino(ConvArgs a) {
     };
     auto row_op = [&](int n) {   // V = B^T d B, B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]: rows first (n = 4 * row + j)
         const int r = n >> 2, j = n & 3;
-        t[n] = (r == 0) ? og_sub4(d[0 + j], d[8 + j]) : (r == 1) ? d[4 + j] + d[8 + j] : (r == 2) ? og_sub4(d[8 + j], d[4 + j]) : og_sub4(d[4 + j], d[12 + j]);
+        t[n] = (r == 0) ? og_sub4(d[0 + j], d[8 + j]) : (r == 1) ? og_add4(d[4 + j], d[8 + j]) : (r == 2) ? og_sub4(d[8 + j], d[4 + j]) : og_sub4(d[4 + j], d[12 + j]);
     };
     auto col_op = [&](int n) {   // then columns (n = 4 * i + column)
         const int i = n >> 2, cc = n & 3;
-        tv[n] = (cc == 0) ? og_sub4(t[4 * i + 0], t[4 * i + 2]) : (cc == 1) ? t[4 * i + 1] + t[4 * i + 2] : (cc == 2) ? og_sub4(t[4 * i + 2], t[4 * i + 1])
+        tv[n] = (cc == 0) ? og_sub4(t[4 * i + 0], t[4 * i + 2]) : (cc == 1) ? og_add4(t[4 * i + 1], t[4 * i + 2]) : (cc == 2) ? og_sub4(t[4 * i + 2], t[4 * i + 1])
                                                                                                                      : og_sub4(t[4 * i + 1], t[4 * i + 3]);
     };
     auto v_write = [&](int k) { *(OG_LDS_AS f32x4*)(unsigned long long)(vwbase + (unsigned)(k * 4096)) = tv[k]; };
@@ -1294,75 +1336,88 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino(ConvArgs a) {
     __syncthreads();   // lo half of V (chunk 0) complete; every read of the raw buffer done
     if (st != nullptr && tid == 0) st[3] = __builtin_amdgcn_s_memtime();   // main loop starts
 
-    for (int c = 0; c < n_ck; ++c) {
-        const bool nxt = c + 1 < n_ck;
+    // The chunk body is instantiated twice on a COMPILE-TIME `NXT` (is there a chunk behind this one?): the loop runs the
+    // NXT = true copy over chunks 0 .. n_ck - 2 and holds one branch, its back edge; the last chunk is a straight-line copy without
+    // the transform, the halo DMA and group 1's weight DMA.  A run-time test of `nxt` inside the fenced slots cost a scalar AND +
+    // branch per slot and a dozen v_cndmask to merge `tv` (tools/isa_wino_loop.py, tests/test_isa_wino_loop.py keep it out).
+    auto group = [&](auto g_, auto nxt_) {
+        constexpr int g = decltype(g_)::value;
+        constexpr bool NXT = decltype(nxt_)::value != 0;
+        constexpr bool MORE_U = (g == 0) || NXT;
+        f32x4 fa[2], fb[2];
+        fa[0] = og_lds_read16(abase[0] + (unsigned)(8 * g * 4096));
+        fb[0] = og_lds_read16(bbase[0] + (unsigned)(g * UG_BYTES));
 #pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            const int grp = 2 * c + g;
-            const bool more_u = grp + 1 < 2 * n_ck;
-            f32x4 fa[2], fb[2];
-            fa[0] = og_lds_read16(abase[0] + (unsigned)(8 * g * 4096));
-            fb[0] = og_lds_read16(bbase[0] + (unsigned)(g * UG_BYTES));
-#pragma unroll
-            for (int st = 0; st < NST; ++st) {
-                const int k = 8 * g + st / KS;
-                const f32x4 av = fa[st & 1], bv = fb[st & 1];
-                acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc[k], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (st + 1 < NST) {   // slot 0: the fragments of the next step
-                    const int kn = (st + 1) / KS, jn = (st + 1) % KS;
-                    fa[(st + 1) & 1] = og_lds_read16(abase[jn] + (unsigned)((8 * g + kn) * 4096));
-                    fb[(st + 1) & 1] = og_lds_read16(bbase[jn] + (unsigned)(g * UG_BYTES + kn * UP_BYTES));
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc[k], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                // slot 1
-                if (g == 0) {
-                    if (NT == 2) { if (st < 8) v_write(8 + st); }                 // hi half of this chunk's V
-                    else v_write(8 + st);
-                } else if (nxt) {
-                    if (NT == 2) {   // reads in steps 0-1, row ops 3-6, column ops 7-10, lo writes 11-14
-                        if (st < 2) xf4(8 * st);
-                        else if (st >= 3 && st < 7) { xf_op(16 + 4 * (st - 3)); xf_op(16 + 4 * (st - 3) + 1); }
-                        else if (st >= 7 && st < 11) { xf_op(32 + 4 * (st - 7)); xf_op(32 + 4 * (st - 7) + 1); }
-                        else if (st >= 11 && st < 15) xf_op(48 + 2 * (st - 11));
-                    } else {         // reads in steps 0-1, row ops 2-3, column ops 4-5, lo writes 6-7
-                        if (st < 2) xf4(8 * st);
-                        else if (st < 4) xf4(16 + 8 * (st - 2));
-                        else if (st < 6) xf4(32 + 8 * (st - 4));
-                        else { xf_op(48 + 4 * (st - 6)); xf_op(48 + 4 * (st - 6) + 1); }
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc[k], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                // slot 2
-                if (st < U_IT && more_u) u_piece(g ^ 1, grp + 1, st);
-                if (g == 1 && nxt) {
-                    if (NT == 2) {
-                        if (st < 2) xf4(8 * st + 4);
-                        else if (st >= 3 && st < 7) { xf_op(16 + 4 * (st - 3) + 2); xf_op(16 + 4 * (st - 3) + 3); }
-                        else if (st >= 7 && st < 11) { xf_op(32 + 4 * (st - 7) + 2); xf_op(32 + 4 * (st - 7) + 3); }
-                        else if (st >= 11 && st < 15) xf_op(48 + 2 * (st - 11) + 1);
-                    } else {
-                        if (st < 2) xf4(8 * st + 4);
-                        else if (st < 4) xf4(16 + 8 * (st - 2) + 4);
-                        else if (st < 6) xf4(32 + 8 * (st - 4) + 4);
-                        else { xf_op(48 + 4 * (st - 6) + 2); xf_op(48 + 4 * (st - 6) + 3); }
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc[k], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                // slot 3
-                if (g == 0 && nxt && st < RAW_IT) raw_piece(c + 1, st);   // early in the group: waited at its end
-                __builtin_amdgcn_sched_barrier(0);
+        for (int st = 0; st < NST; ++st) {
+            const int k = 8 * g + st / KS;
+            const f32x4 av = fa[st & 1], bv = fb[st & 1];
+            acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv.x, acc[k], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (st + 1 < NST) {   // slot 0: the fragments of the next step
+                const int kn = (st + 1) / KS, jn = (st + 1) % KS;
+                fa[(st + 1) & 1] = og_lds_read16(abase[jn] + (unsigned)((8 * g + kn) * 4096));
+                fb[(st + 1) & 1] = og_lds_read16(bbase[jn] + (unsigned)(g * UG_BYTES + kn * UP_BYTES));
             }
-            og_wait_dma();
-            __syncthreads();
+            __builtin_amdgcn_sched_barrier(0);
+            acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv.y, acc[k], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            // slot 1
+            if constexpr (g == 0) {
+                if (NT == 2) { if (st < 8) v_write(8 + st); }                 // hi half of this chunk's V
+                else v_write(8 + st);
+            } else if constexpr (NXT) {
+                if (NT == 2) {   // reads in steps 0-1, row ops 3-6, column ops 7-10, lo writes 11-14
+                    if (st < 2) xf4(8 * st);
+                    else if (st >= 3 && st < 7) { xf_op(16 + 4 * (st - 3)); xf_op(16 + 4 * (st - 3) + 1); }
+                    else if (st >= 7 && st < 11) { xf_op(32 + 4 * (st - 7)); xf_op(32 + 4 * (st - 7) + 1); }
+                    else if (st >= 11 && st < 15) xf_op(48 + 2 * (st - 11));
+                } else {         // reads in steps 0-1, row ops 2-3, column ops 4-5, lo writes 6-7
+                    if (st < 2) xf4(8 * st);
+                    else if (st < 4) xf4(16 + 8 * (st - 2));
+                    else if (st < 6) xf4(32 + 8 * (st - 4));
+                    else { xf_op(48 + 4 * (st - 6)); xf_op(48 + 4 * (st - 6) + 1); }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv.z, acc[k], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            // slot 2
+            if constexpr (MORE_U) {
+                if (st < U_IT) u_piece(og_const<0>{}, g ^ 1, st);
+            }
+            if constexpr (g == 1 && NXT) {
+                if (NT == 2) {
+                    if (st < 2) xf4(8 * st + 4);
+                    else if (st >= 3 && st < 7) { xf_op(16 + 4 * (st - 3) + 2); xf_op(16 + 4 * (st - 3) + 3); }
+                    else if (st >= 7 && st < 11) { xf_op(32 + 4 * (st - 7) + 2); xf_op(32 + 4 * (st - 7) + 3); }
+                    else if (st >= 11 && st < 15) xf_op(48 + 2 * (st - 11) + 1);
+                } else {
+                    if (st < 2) xf4(8 * st + 4);
+                    else if (st < 4) xf4(16 + 8 * (st - 2) + 4);
+                    else if (st < 6) xf4(32 + 8 * (st - 4) + 4);
+                    else { xf_op(48 + 4 * (st - 6) + 2); xf_op(48 + 4 * (st - 6) + 3); }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            acc[k] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv.w, acc[k], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            // slot 3
+            if constexpr (g == 0 && NXT) {
+                if (st < RAW_IT) raw_piece(og_const<0>{}, st);   // early in the group: waited at its end
+            }
+            __builtin_amdgcn_sched_barrier(0);
         }
+        wso += UG_BYTES;
+        if constexpr (g == 0) hso += PB;
+        og_wait_dma();
+        __syncthreads();
+    };
+    for (int c = 0; c < n_ck - 1; ++c) {
+        group(og_const<0>{}, og_const<1>{});
+        group(og_const<1>{}, og_const<1>{});
     }
+    group(og_const<0>{}, og_const<0>{});
+    group(og_const<1>{}, og_const<0>{});
 
     if (st != nullptr && tid == 0) st[4] = __builtin_amdgcn_s_memtime();   // main loop done
     // ---- output transform Y = A^T M A, A^T = [1 1 1 0; 0 1 -1 -1], in registers; then the shared epilogue ----

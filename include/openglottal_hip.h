@@ -260,7 +260,8 @@ double og_unet_flops_per_frame(og_unet* h, int H, int W);
  * handle with every launch recorded instead of issued.  `options` = "name=value,name=value" (og_unet_set_option names), `lanes` =
  * lanes of the call the micro-batch belongs to (1..3: a scheduling hint of the under-filled launches).  `out` receives one line per
  * launch, "kernel|grid.x|grid.y|grid.z|block|lds_bytes|workspace_bytes|arrival_counters"; returns the number of launches or a
- * negative error code.  Nothing here has a counterpart in the reference (it launches nothing by hand); it exists so that the bounds
+ * negative error code.  `kernel` is the launch site's text; an f16-mode conv (precision 2) is named by its instantiation and the K
+ * walk it is given, "(k_conv_mfma_f<2, 0, 16, 2, false, true>) chunks=3 k_half=1" (64-channel chunks; k_half: the last one holds 32).  Nothing here has a counterpart in the reference (it launches nothing by hand); it exists so that the bounds
  * every launch must respect -- og_workspace_limit() -- can be checked for every micro-batch size, layer shape and forced option on a
  * machine without a GPU (tests/test_launch_plan.py), instead of being found by a faulting kernel. */
 int og_unet_plan(const int* features, int n_levels, int B, int H, int W, int lanes, const char* options, char* out, size_t cap,

@@ -98,6 +98,12 @@ inline void plan_write(const char* name, const void* p, long long bytes) {
     std::string& w = g_plan->recs.back().writes;
     w += (w.empty() ? "" : ";") + std::string(name) + "=" + std::to_string(end);
 }
+// og_unet_plan only: give the f16-mode conv launch just recorded its instantiation (the launch site's text has template
+// parameters in it) and the K walk it was given: 64-channel chunks, and whether the last one is a half (ConvArgs::k_half)
+inline void plan_label_f(const char* inst, int n_chunks, int k_half) {
+    if (!g_plan || g_plan->recs.empty()) return;
+    g_plan->recs.back().kernel = std::string(inst) + " chunks=" + std::to_string(n_chunks) + " k_half=" + std::to_string(k_half);
+}
 // every launch of the chain goes through here: a failed launch is reported as OG_EHIP by THIS call (not by a later one)
 #define OG_LAUNCH(kern, grid, block, lds, stream, ...)                                                    \
     do {                                                                                                  \
@@ -846,6 +852,11 @@ int launch_conv_f(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {   //
     a.zrcp = 1.0f / (float)(a.zdiv * G);
     if ((long long)groups * G * a.zdiv > 65535) return fail(OG_EINVAL, "micro-batch too large for one launch (grid.z): lower the chunk size");
     OG_LAUNCH((k_conv_mfma_f<NT, MODE, TH, OCC, false, SQ>), dim3(a.tiles_x, a.tiles_y, groups * G * a.zdiv), dim3(256), lds, c.stream, a);
+    if (g_plan) {
+        char inst[64];
+        snprintf(inst, sizeof inst, "(k_conv_mfma_f<%d, %d, %d, %d, false, %s>)", NT, MODE, TH, OCC, SQ ? "true" : "false");
+        plan_label_f(inst, a.n_chunks, a.k_half);
+    }
     return OG_OK;
 }
 
@@ -1393,9 +1404,10 @@ int enqueue_first_fused(og_unet* h, const uint8_t* gray, int B, int H, int W) {
     a.zgroup_shift = 0;
     a.frames = B;
     if (h->precision != 0) a.prio_mode = h->prio_mode;
-    if (h->precision == 2)
+    if (h->precision == 2) {
         OG_LAUNCH((k_conv_mfma_f<1, 0, 8, 3, true>), dim3(a.tiles_x, a.tiles_y, B), dim3(256), lds, h->stream, a);
-    else if (h->precision == 1)
+        plan_label_f("(k_conv_mfma_f<1, 0, 8, 3, true>)", a.n_chunks, a.k_half);
+    } else if (h->precision == 1)
         OG_LAUNCH((k_conv_mfma_h<1, 0, 8, 3, true>), dim3(a.tiles_x, a.tiles_y, B), dim3(256), lds, h->stream, a);
     else
         OG_LAUNCH((k_conv_mfma_o<1, 0, 8, 3, true>), dim3(a.tiles_x, a.tiles_y, B), dim3(256), lds, h->stream, a);

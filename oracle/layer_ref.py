@@ -38,6 +38,22 @@ that every mutant of a kernel's arithmetic still exceeds the bound):
   hi / lo pair again.  ``split_f32`` emulates it; the worst emulated ratio is 3.9 (``SPLIT_EMULATED_MAX``).  16 = 4x that; the
   dropped a_lo * b_hi product (the mutant closest to the arithmetic's own error) is ~100x over.
 
+* ``f16`` = 16.  The f16 mode (``k_conv_mfma_f``, ``k_conv_first_f``, ``k_head_f``, precision 2).  Its reference is the float64 op on
+  the weights the device holds: every 3x3 conv after the first layer and every transposed conv with its weights rounded to f16
+  once (round to nearest even; ``f16_weights``); first-layer, BN and head weights f32.  Inputs and weights are f16 values, so
+  every product is exact in f32 and only the f32 accumulation and the f32 epilogue fma err, as in ``direct``, on the instruction
+  (``v_mfma_f32_32x32x16_f16``) ``split`` passes with at 16.  Every stored activation is rounded to f16 exactly once, so the check
+  is not a tolerance but a condition on bits (``check_f16``): with ``e = kappa * 2^-24 * M + FLOOR`` the stored value must lie in
+  ``[RNE16(ref - e), RNE16(ref + e)]`` (rounding to nearest even is monotone); on a typical layer nine of ten positive outputs
+  have a single admissible f16 value.  Subnormal f16 values are ordinary values of that interval.  The pools stay bit-exact
+  (the rounded max is the max of the rounded values) and the f32 logits keep the magnitude check, from the stored (rounded)
+  last activation.  Unstored boundaries: the inner bound is ``e_a`` plus half an f16 ulp of ``|ref_a| + e_a``, pushed through
+  ``|s| * conv(., |w|)`` (the head's ``|w| . (.)``), the interval test on the outside.  The CPU emulation
+  (``tests/f16_emulation.py``, torch f32 accumulation in two memory formats) needs kappa <= 2.5 on every stored tensor and <= 3.5
+  on the head (``F16_EMULATED_MAX``); 16 = 4.6x the larger.  On the GPU (``F16_GPU_MAX``) the worst stored tensor needs 2.53 (the
+  f32 first layer of the (96, 192) net; every ``k_conv_mfma_f`` tensor <= 1.58) and the head 1.94.  kappa is not a knob: a layer
+  that needs more is a finding about the kernel (summation order inside the MFMA, a double rounding, a flushed subnormal).
+
 ``FLOOR`` (1e-30) only keeps exact zeros and subnormal references from dividing by zero; it is far below every M of these nets.
 """
 
@@ -49,9 +65,19 @@ from .unet_oracle import BN_EPS, n_levels
 
 U = 2.0 ** -24
 FLOOR = 1e-30
-KAPPA = {"direct": 16.0, "wino": 24.0, "split": 16.0}
+KAPPA = {"direct": 16.0, "wino": 24.0, "split": 16.0, "f16": 16.0}
 WINO_EMULATED_MAX = 8.6      # recorded by tests/test_layer_ref.py::test_winograd_emulation_passes_at_its_kappa (asserts <= 2x this)
 SPLIT_EMULATED_MAX = 3.9     # recorded by tests/test_layer_ref.py::test_split_precision_emulation_passes_at_its_kappa
+
+
+# smallest kappa the CPU emulation of the f16 mode needs (tests/test_layer_ref.py::test_f16_emulation_passes_at_its_kappa asserts
+# <= 2x each): "stored" = every interval-checked tensor (first layer, 3x3 convs, transposed convs), "head" = the f32 logits
+F16_EMULATED_MAX = {"stored": 2.5, "head": 3.5}
+# the same two figures on the MI355X over the f16 rows of GPU_CASES and the f32 entry point (tests/test_gpu_layer_parity.py prints
+# them per layer): "stored" is downs.0.a of the (96, 192) net (the f32 first-layer chain, rounded); the worst
+# k_conv_mfma_f tensor is ups.1.b of the same net at 1.58, the worst transposed conv ups.6 of the full net at 1.12; "head" is the
+# full-width net's.  Recorded, not asserted: the gate is KAPPA["f16"].
+F16_GPU_MAX = {"stored": 2.53, "head": 1.94}
 
 
 # ───────────────────────────── float64 ops ─────────────────────────────
@@ -165,6 +191,74 @@ def bound_of(M: np.ndarray, kappa: float) -> np.ndarray:
     return kappa * U * M + FLOOR
 
 
+# ───────────────────────────── the f16 form: a condition on bits ─────────────────────────────
+
+
+def rne16(v) -> np.ndarray:
+    """float64 -> the nearest f16 value (ties to even, subnormals kept, one rounding), as float64."""
+    with np.errstate(over="ignore"):
+        return np.asarray(v, dtype=np.float64).astype(np.float16).astype(np.float64)
+
+
+def half_ulp16(v) -> np.ndarray:
+    """Half the f16 spacing at magnitude |v|: the most a single rounding to f16 moves a value of that magnitude."""
+    v = np.abs(np.asarray(v, dtype=np.float64))
+    _, ex = np.frexp(v)
+    return np.where(v > 0, np.maximum(np.ldexp(1.0, ex - 12), 2.0 ** -25), 2.0 ** -25)
+
+
+def f16_weights(sd: dict) -> dict:
+    """The weights an f16-mode device holds: every 3x3 conv after the first layer and every transposed conv rounded to f16 once
+    (ties to even); first-layer weights, BN and the head stay f32."""
+    out = dict(sd)
+    for k, v in sd.items():
+        conv3 = k.endswith(".weight") and np.ndim(v) == 4 and ".net." in k and k != "downs.0.net.0.weight"
+        convt_w = k.endswith(".weight") and np.ndim(v) == 4 and k.startswith("ups.") and ".net." not in k
+        if conv3 or convt_w:
+            out[k] = np.asarray(v, np.float32).astype(np.float16).astype(np.float32)
+    return out
+
+
+def f16_needed(got: np.ndarray, ref: np.ndarray) -> np.ndarray:
+    """Per element, the smallest e for which the f16 value ``got`` lies in [RNE16(ref - e), RNE16(ref + e)]: the distance from
+    ``ref`` to the set of reals that round to ``got`` (0 where ``got`` is the rounded reference)."""
+    g16 = np.asarray(got).astype(np.float16)
+    g = g16.astype(np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        up = np.nextafter(g16, np.float16(np.inf)).astype(np.float64)
+        dn = np.nextafter(g16, np.float16(-np.inf)).astype(np.float64)
+        return np.maximum(0.0, np.maximum(ref - (g + up) / 2, (g + dn) / 2 - ref))
+
+
+def check_f16(name: str, got: np.ndarray, ref: np.ndarray, e: np.ndarray, frames=None, tile=(16, 16), kappa: float = KAPPA["f16"]) -> float:
+    """RNE16(ref - e) <= got <= RNE16(ref + e) elementwise ([B,C,H,W]); every ``got`` must be a finite f16 value.  ``e`` is the
+    f32 error bound of the value BEFORE its one rounding to f16 (``bound_of(M, kappa)``, or a composed bound).  Returns the
+    smallest kappa that would have admitted every element (``kappa`` scaled by the largest needed e / e).  On failure the message
+    names the layer, the frame, the channel, (y, x), the ``tile``-sized grid cell, got, ref, both interval ends and the number of
+    elements outside."""
+    got = np.asarray(got, dtype=np.float64)
+    assert got.shape == ref.shape == e.shape, (name, got.shape, ref.shape, e.shape)
+    if not np.all(np.isfinite(got)):
+        b, c, y, x = (int(v) for v in np.argwhere(~np.isfinite(got))[0])
+        raise LayerMismatch(f"{name}: non-finite value {got[b, c, y, x]} at frame {_frame(frames, b)} ch {c} (y,x)=({y},{x})")
+    not16 = np.argwhere(rne16(got) != got)
+    if len(not16):
+        b, c, y, x = (int(v) for v in not16[0])
+        raise LayerMismatch(f"{name}: stored value {got[b, c, y, x]!r} at frame {_frame(frames, b)} ch {c} (y,x)=({y},{x}) is not an f16 "
+                            f"value; {len(not16)} such element(s)")
+    lo, hi = rne16(ref - e), rne16(ref + e)
+    need = f16_needed(got, ref) / e
+    outside = (got < lo) | (got > hi)
+    if outside.any():
+        b, c, y, x = (int(v) for v in np.unravel_index(int(np.argmax(np.where(outside, need, -1.0))), need.shape))
+        raise LayerMismatch(
+            f"{name}: outside its f16 interval at frame {_frame(frames, b)} ch {c} (y,x)=({y},{x}) in {tile[0]}x{tile[1]} grid cell "
+            f"({y // tile[0]},{x // tile[1]}) at ({y % tile[0]},{x % tile[1]}) inside it; got {got[b, c, y, x]!r} ref {ref[b, c, y, x]!r} "
+            f"interval [{lo[b, c, y, x]!r}, {hi[b, c, y, x]!r}] (e {e[b, c, y, x]:.3g}, needs kappa {kappa * need[b, c, y, x]:.3g} of {kappa:g}); "
+            f"{int(outside.sum())} element(s) outside the interval")
+    return kappa * float(need.max()) if need.size else 0.0
+
+
 # ───────────────────────────── the whole net, layer by layer ─────────────────────────────
 
 
@@ -180,15 +274,21 @@ def layer_names(L: int):
 
 
 def check_net(sd: dict, gray: np.ndarray, get, logits: np.ndarray, kappa: dict, frames=None, mask=None, area=None,
-              threshold: float = 0.5, fused_first: bool = False, fused_head: bool = False, tile=(16, 16)) -> dict:
+              threshold: float = 0.5, fused_first: bool = False, fused_head: bool = False, tile=(16, 16), form: str = "") -> dict:
     """Every layer tensor of one forward against its float64 reference computed from the GPU's own input.
 
     ``get(name)`` returns the GPU's tap ``[B,C,H,W]`` (the frames of ``gray``); ``logits`` ``[B,H,W]``; ``kappa`` maps the op kind
     (``first``, ``conv3``, ``convt``, ``head``) to the form's kappa.  ``fused_first``: ``downs.0.a`` was never stored, ``downs.0.b``
     is checked against the composed reference.  ``fused_head``: ``ups.N.b`` was never stored, the logits are checked against the
     composed reference.  ``mask`` / ``area``: checked exactly against the GPU's own logits.  Returns {layer: worst |err| / bound}.
+
+    ``form="f16"``: the reference weights are ``f16_weights(sd)``, every stored tensor goes through ``check_f16`` (the interval
+    test), the pools stay bit-exact, the f32 logits keep the magnitude check; the returned figures are then the smallest kappa
+    each layer needs (for the head: its |err| / bound times its kappa).
     """
     L = n_levels(sd)
+    f16 = form == "f16"
+    sdw = f16_weights(sd) if f16 else sd
     worst = {}
     cache = {}
 
@@ -198,7 +298,15 @@ def check_net(sd: dict, gray: np.ndarray, get, logits: np.ndarray, kappa: dict, 
         return cache[n]
 
     def dc(prefix, x_in, idx):
-        return conv3_bn_relu(sd, f"{prefix}.net.{idx}.weight", f"{prefix}.net.{idx + 1}", x_in)
+        return conv3_bn_relu(sdw, f"{prefix}.net.{idx}.weight", f"{prefix}.net.{idx + 1}", x_in)
+
+    def chk(name, got, ref, bound, kind):
+        if f16:
+            return check_f16(name, got, ref, bound, frames, tile, kappa[kind])
+        return check(name, got, ref, bound, frames, tile)
+
+    def stored(bound, ref):   # the bound of a boundary that is not stored, as the next op reads it: rounded to f16 once in the f16 form
+        return bound + half_ulp16(np.abs(ref) + bound) if f16 else bound
 
     x0 = first_input(gray)
     for i in range(L):
@@ -209,43 +317,44 @@ def check_net(sd: dict, gray: np.ndarray, get, logits: np.ndarray, kappa: dict, 
             if fused_first:   # downs.0.b from the frames: own bound + |s| conv(bound_a, |w|)
                 ref_b, _, M_b = dc(p, ref_a, 3)
                 s, _, _ = fold_bn(sd, p + ".net.4")
-                bnd = bound_of(M_b, kappa["conv3"]) + np.abs(s)[None, :, None, None] * conv3_raw(b_a, np.abs(sd[p + ".net.3.weight"]))
-                worst[p + ".b (fused first)"] = check(p + ".b (fused with the first layer)", tap(p + ".b"), ref_b, bnd, frames, tile)
+                bnd = bound_of(M_b, kappa["conv3"]) + np.abs(s)[None, :, None, None] * conv3_raw(stored(b_a, ref_a), np.abs(sdw[p + ".net.3.weight"]))
+                worst[p + ".b (fused first)"] = chk(p + ".b (fused with the first layer)", tap(p + ".b"), ref_b, bnd, "conv3")
             else:
-                worst[p + ".a"] = check(p + ".a", tap(p + ".a"), ref_a, b_a, frames, tile)
+                worst[p + ".a"] = chk(p + ".a", tap(p + ".a"), ref_a, b_a, "first")
         else:
             ref_a, _, M_a = dc(p, tap(f"pool{i - 1}"), 0)
-            worst[p + ".a"] = check(p + ".a", tap(p + ".a"), ref_a, bound_of(M_a, kappa["conv3"]), frames, tile)
+            worst[p + ".a"] = chk(p + ".a", tap(p + ".a"), ref_a, bound_of(M_a, kappa["conv3"]), "conv3")
         if not (i == 0 and fused_first):
             ref_b, _, M_b = dc(p, tap(p + ".a"), 3)
-            worst[p + ".b"] = check(p + ".b", tap(p + ".b"), ref_b, bound_of(M_b, kappa["conv3"]), frames, tile)
+            worst[p + ".b"] = chk(p + ".b", tap(p + ".b"), ref_b, bound_of(M_b, kappa["conv3"]), "conv3")
         check_exact(f"pool{i}", tap(f"pool{i}"), maxpool2(tap(p + ".b")), frames)
         worst[f"pool{i}"] = 0.0
     ref, _, M = dc("bottleneck", tap(f"pool{L - 1}"), 0)
-    worst["bottleneck.a"] = check("bottleneck.a", tap("bottleneck.a"), ref, bound_of(M, kappa["conv3"]), frames, tile)
+    worst["bottleneck.a"] = chk("bottleneck.a", tap("bottleneck.a"), ref, bound_of(M, kappa["conv3"]), "conv3")
     ref, _, M = dc("bottleneck", tap("bottleneck.a"), 3)
-    worst["bottleneck.b"] = check("bottleneck.b", tap("bottleneck.b"), ref, bound_of(M, kappa["conv3"]), frames, tile)
+    worst["bottleneck.b"] = chk("bottleneck.b", tap("bottleneck.b"), ref, bound_of(M, kappa["conv3"]), "conv3")
+    hs = kappa["head"] if f16 else 1.0      # f16 form: the head's figure in kappa units, like the other layers'
     for j in range(L):
         i = L - 1 - j
         src = "bottleneck.b" if j == 0 else f"ups.{2 * j - 1}.b"
-        ref, M = convt(sd, f"ups.{2 * j}", tap(src))
+        ref, M = convt(sdw, f"ups.{2 * j}", tap(src))
         n = f"ups.{2 * j}"
-        worst[n] = check(n, tap(n), ref, bound_of(M, kappa["convt"]), frames, tile)
+        worst[n] = chk(n, tap(n), ref, bound_of(M, kappa["convt"]), "convt")
         p = f"ups.{2 * j + 1}"
         cat = np.concatenate([tap(f"downs.{i}.b"), tap(n)], axis=1)      # skip first (unet.py:86)
         ref, _, M = dc(p, cat, 0)
-        worst[p + ".a"] = check(p + ".a", tap(p + ".a"), ref, bound_of(M, kappa["conv3"]), frames, tile)
+        worst[p + ".a"] = chk(p + ".a", tap(p + ".a"), ref, bound_of(M, kappa["conv3"]), "conv3")
         ref_b, _, M_b = dc(p, tap(p + ".a"), 3)
         if j == L - 1 and fused_head:   # logits from ups.N.a: own bound + |w_head| . bound_b
-            b_b = bound_of(M_b, kappa["conv3"])
+            b_b = stored(bound_of(M_b, kappa["conv3"]), ref_b)
             ref_h, M_h = head(sd, ref_b)
             bnd = bound_of(M_h, kappa["head"]) + head_abs(sd, b_b)
-            worst["head (fused)"] = check("head (fused with the last conv)", logits[:, None], ref_h, bnd, frames, tile)
+            worst["head (fused)"] = hs * check("head (fused with the last conv)", logits[:, None], ref_h, bnd, frames, tile)
         else:
-            worst[p + ".b"] = check(p + ".b", tap(p + ".b"), ref_b, bound_of(M_b, kappa["conv3"]), frames, tile)
+            worst[p + ".b"] = chk(p + ".b", tap(p + ".b"), ref_b, bound_of(M_b, kappa["conv3"]), "conv3")
     if not fused_head:
         ref_h, M_h = head(sd, tap(f"ups.{2 * L - 1}.b"))
-        worst["head"] = check("head", logits[:, None], ref_h, bound_of(M_h, kappa["head"]), frames, tile)
+        worst["head"] = hs * check("head", logits[:, None], ref_h, bound_of(M_h, kappa["head"]), frames, tile)
     if mask is not None:
         check_mask(logits, mask, threshold, frames)
     if area is not None:
@@ -446,12 +555,53 @@ GPU_CASES = [
     _case("large-512x512", (32, 64), 512, 512, 8, {}, ["k_conv_wino"], nread=1),
 ]
 
+# every kernel the f16 mode can launch, by the short label of its instantiation -> its text in og_unet_plan / in UNet.profile
+F16_KERNELS = {
+    "<2,0,16,2>": ("k_conv_mfma_f<2, 0, 16, 2, false, false>", "k_conv_mfma_f<2,0,16>"),
+    "<2,0,16,2,SQ>": ("k_conv_mfma_f<2, 0, 16, 2, false, true>", "k_conv_mfma_f<2,0,16>"),
+    "<1,0,16,2>": ("k_conv_mfma_f<1, 0, 16, 2, false, false>", "k_conv_mfma_f<1,0,16>"),
+    "<2,0,8,3>": ("k_conv_mfma_f<2, 0, 8, 3, false, false>", "k_conv_mfma_f<2,0,8>"),
+    "<1,0,8,3>": ("k_conv_mfma_f<1, 0, 8, 3, false, false>", "k_conv_mfma_f<1,0,8>"),
+    "<2,1,8,3>": ("k_conv_mfma_f<2, 1, 8, 3, false, false>", "k_conv_mfma_f<2,1,8>"),
+    "<1,0,8,3,FIRST>": ("k_conv_mfma_f<1, 0, 8, 3, true>", "k_conv_mfma_f<1,0,8,FIRST>"),
+    "k_conv_first_f": ("k_conv_first_f", "k_conv_first_f<u8>"),
+    "k_head_f": ("k_head_f", "k_head_f"),
+}
+
+
+def _f16(cid, feats, H, W, B, options, kernels, nread=2, fused_first=False, fused_head=False):
+    opts = {"precision": 2}
+    opts.update(options)
+    return _case(cid, feats, H, W, B, opts, [F16_KERNELS[k][0] for k in kernels], form="f16", nread=nread, fused_first=fused_first,
+                 fused_head=fused_head, prof=[F16_KERNELS[k][1] for k in kernels])
+
+
+_F16_BIG = ["<2,0,16,2,SQ>", "<1,0,16,2>", "<2,1,8,3>"]
+GPU_CASES += [
+    _f16("f16-default-64", FULL, 256, 256, 64, {}, _F16_BIG + ["<1,0,8,3>", "k_conv_first_f"]),
+    _f16("f16-fused-first-and-head-64", FULL, 256, 256, 64, {"keep_taps": 0}, _F16_BIG + ["<1,0,8,3>", "<1,0,8,3,FIRST>"],
+         fused_first=True, fused_head=True),
+    _f16("f16-default-1", FULL, 256, 256, 1, {}, _F16_BIG + ["<1,0,8,3>", "k_conv_first_f"], nread=1),
+    _f16("f16-tile-h8-2", FULL, 256, 256, 2, {"tile_h": 8}, ["<2,0,8,3>", "<1,0,8,3>", "<2,1,8,3>", "k_conv_first_f"]),
+    _f16("f16-h-square0-2", FULL, 256, 256, 2, {"h_square": 0}, ["<2,0,16,2>", "<1,0,16,2>", "<2,1,8,3>", "k_conv_first_f"]),
+    _f16("f16-unfused-head-2", FULL, 256, 256, 2, {"fuse_head": 0}, _F16_BIG + ["k_conv_first_f", "k_head_f"]),
+    _f16("f16-tiles-128x256", (32, 64), 128, 256, 64, {}, _F16_BIG + ["<1,0,8,3>", "k_conv_first_f"]),
+    _f16("f16-tiles-96x160", (32, 64), 96, 160, 16, {}, _F16_BIG + ["<2,0,8,3>", "<1,0,8,3>", "k_conv_first_f"], nread=4),
+    _f16("f16-padded-40x80-64x64", (40, 80), 64, 64, 8, {}, _F16_BIG + ["k_conv_first_f", "k_head_f"], nread=6),
+    _f16("f16-padded-33x66-32x64", (33, 66), 32, 64, 4, {}, _F16_BIG + ["<1,0,8,3>", "k_conv_first_f", "k_head_f"], nread=4),
+    _f16("f16-wide-96x192-64x128", (96, 192), 64, 128, 4, {}, _F16_BIG + ["k_conv_first_f", "k_head_f"], nread=4),
+    _f16("f16-bottleneck-1x1-16x16", (4, 8, 16, 32), 16, 16, 4, {}, ["<2,0,8,3>", "<1,0,16,2>", "<1,0,8,3>", "<2,1,8,3>", "k_conv_first_f"], nread=4),
+    _f16("f16-maps-1x16-16x256", (4, 8, 16, 32), 16, 256, 2, {}, ["<2,0,8,3>", "<1,0,16,2>", "<1,0,8,3>", "<2,1,8,3>", "k_conv_first_f"], nread=2),
+    _f16("f16-five-levels-64x96", (3, 6, 12, 24, 48), 64, 96, 4, {}, ["<2,0,8,3>", "<1,0,16,2>", "<1,0,8,3>", "<2,1,8,3>", "k_conv_first_f"], nread=4),
+    _f16("f16-large-512x512", (32, 64), 512, 512, 8, {}, _F16_BIG + ["<1,0,8,3>", "k_conv_first_f"], nread=1),
+]
+
 
 def kappa_of(form: str) -> dict:
     """kappa per op kind for a chain of the given form (the first layer, the transposed convs and the heads are direct in every
-    f32 chain; split precision runs every op through the hi / lo arithmetic)."""
+    f32 chain; split precision runs every op through the hi / lo arithmetic, the f16 mode through its own kernels)."""
     k, d = KAPPA[form], KAPPA["direct"]
-    if form == "split":
+    if form in ("split", "f16"):
         return {"first": k, "conv3": k, "convt": k, "head": k}
     return {"first": d, "conv3": k, "convt": d, "head": d}
 
@@ -481,6 +631,32 @@ def plan_families(recs, B: int) -> set:
     return out
 
 
+def plan_instantiations(recs) -> set:
+    """Kernels of an f16-mode og_unet_plan record list by instantiation: the record's text without its parentheses and its K-walk
+    suffix (``k_conv_mfma_f<2, 0, 16, 2, false, true>``), ``k_conv_first_f`` and ``k_head_f`` without their arguments."""
+    import re
+
+    out = set()
+    for r in recs:
+        m = re.match(r"\(?\s*(k_conv_mfma_f<[^>]*>)", r["kernel"]) or re.match(r"\(?\s*(k_conv_first_f|k_head_f)\b", r["kernel"])
+        if m:
+            out.add(m.group(1))
+    return out
+
+
+def plan_half_chunks(recs) -> set:
+    """Which kinds of half last chunk (``ConvArgs::k_half``) the f16 launches of a plan walk: ``"only"`` (the half chunk is the
+    whole K loop) and / or ``"after-full"`` (it follows full 64-channel chunks)."""
+    import re
+
+    out = set()
+    for r in recs:
+        m = re.search(r"k_conv_mfma_f<.* chunks=(\d+) k_half=(\d+)", r["kernel"])
+        if m and int(m.group(2)):
+            out.add("only" if int(m.group(1)) == 1 else "after-full")
+    return out
+
+
 def profile_families(prof) -> set:
     """Kernel families of a ``UNet.profile`` list (its kernel names are the launch sites' labels)."""
     import re
@@ -496,3 +672,8 @@ def profile_families(prof) -> set:
         if "+splitK" in k:
             out.add("splitK")
     return out
+
+
+def profile_instantiations(prof) -> set:
+    """The launch-site labels of a ``UNet.profile`` list, whole (``k_conv_mfma_f<2,0,16>``, ``k_conv_first_f<u8>``, ``k_head_f``)."""
+    return {p["kernel"] for p in prof}

@@ -19,6 +19,7 @@ import pytest
 import f16_emulation as EMU
 import openglottal_amd as og
 from openglottal_amd import synth
+from oracle import layer_ref as R
 
 pytestmark = pytest.mark.gpu
 
@@ -151,6 +152,12 @@ def test_every_layer_boundary_small_net_f16(golden_dir):
             assert err <= 2 * El, (k, err, El)
             if k != "head":
                 assert np.array_equal(got, got.astype(np.float16).astype(np.float32)), k      # stored values are f16 values
+        # and each launch alone, from its own input tap, at half-ulp sharpness (oracle/layer_ref.py: check_f16)
+        need = R.check_net(sd, f, lambda k: m.activation(k, 1), np.asarray(logits)[:, 0], R.kappa_of("f16"), form="f16")
+        assert len(need) == 27
+        layer = max(need, key=need.get)
+        print(f"fuse_head {fuse}: smallest kappa each layer needs (of {R.KAPPA['f16']:g}): "
+              + " ".join(f"{k}={v:.2f}" for k, v in need.items() if not k.startswith("pool")) + f"  (max {need[layer]:.2f} at {layer})")
     print(f"largest |gpu - ref| / E_l over the 27 tensors: {worst:.2f}")
 
 

@@ -11,6 +11,10 @@ the mosaic only: its quadrants keep the four patterns pure in the shallow layers
 them; the pure special frames are checked by the cases that read 3 or more frames (the 96 x 160, padded, 16 x 16 and five-level
 nets).  Which kernels ran is asserted through
 ``UNet.profile`` here, and through ``og_unet_plan`` on the CPU (tests/test_layer_ref.py).
+
+The f16 rows (``form`` "f16", precision 2) are judged by the interval test of ``layer_ref.check_f16``: every stored f16 value must
+lie between the roundings of ``ref -+ kappa * 2^-24 * M``, a condition on its bits; their print line shows the smallest kappa each
+layer needs.  ``test_f32_entry_point_in_f16_mode`` runs the same check on ``m(x)`` (NCHW floats in: ``k_conv_first_f<f32>``).
 """
 import numpy as np
 import pytest
@@ -54,9 +58,46 @@ def test_every_layer_against_float64(case):
         return taps[name]
 
     worst = R.check_net(sd, gray[:n], get, logits[:n], R.kappa_of(case["form"]), frames=[ORDER[i] if i < len(ORDER) else i for i in range(n)],
-                        mask=masks[:n], area=areas[:n], fused_first=case["fused_first"], fused_head=case["fused_head"])
+                        mask=masks[:n], area=areas[:n], fused_first=case["fused_first"], fused_head=case["fused_head"], form=case["form"])
     assert np.array_equal(areas, (masks > 0).reshape(B, -1).sum(1))
-    fams = R.profile_families(m.profile(torch.from_numpy(gray).cuda(), B, H, W, reps=1))
+    prof = m.profile(torch.from_numpy(gray).cuda(), B, H, W, reps=1)
+    if case["form"] == "f16":      # by the launch sites' whole labels, and nothing but f16-mode kernels
+        labels = R.profile_instantiations(prof)
+        assert set(case["prof"]) <= labels, (case["id"], sorted(set(case["prof"]) - labels), sorted(labels))
+        assert all(k.startswith(("k_conv_mfma_f<", "k_conv_first_f<", "k_head_f", "k_sum_counts")) for k in labels), sorted(labels)
+        layer = max(worst, key=worst.get)
+        print(f"{case['id']} [f16 kappa {R.KAPPA['f16']:g}] smallest kappa each layer needs: "
+              + " ".join(f"{k}={v:.2f}" for k, v in worst.items() if not k.startswith("pool")) + f"  (max {worst[layer]:.2f} at {layer})")
+        return
+    fams = R.profile_families(prof)
     assert set(case["prof"]) <= fams, (case["id"], sorted(set(case["prof"]) - fams), sorted(fams))
     print(f"{case['id']} [{case['form']} kappa {R.KAPPA[case['form']]:g}] worst |err|/bound per layer: "
           + " ".join(f"{k}={v:.3f}" for k, v in worst.items() if not k.startswith("pool")) + f"  (max {max(worst.values()):.3f})")
+
+
+@pytest.mark.parametrize("feats", [(33, 66), R.FULL], ids=["padded-33x66", "full"])
+def test_f32_entry_point_in_f16_mode(feats):
+    """``m(x)``, NCHW floats in, in the f16 mode: the first layer is ``k_conv_first_f<f32>`` (the only first-layer kernel this entry
+    point launches at precision 2).  The six special frames at 64 x 64 through the same per-layer interval check, and every tap and
+    logit bit for bit what the u8 entry point (``segment``) gives for the same frames."""
+    H = W = 64
+    sd = synth.make_unet_state_dict(feats, seed=11, head_scale=3.0, head_bias=-0.5)
+    m = og.UNet(1, 1, feats)
+    m.load_state_dict(sd)
+    m.to("cuda:0").eval()
+    m.set_option("precision", 2)
+    gray = batch(H, W, len(ORDER))
+    B = len(gray)
+    m.set_chunk(B)
+    logits = np.asarray(m((gray.astype(np.float32) / 255.0)[:, None]))[:, 0]
+    taps = {name: m.activation(name, B) for name in R.layer_names(len(feats))}
+    worst = R.check_net(sd, gray, taps.__getitem__, logits, R.kappa_of("f16"), frames=ORDER, form="f16")
+    layer = max(worst, key=worst.get)
+    print(f"f32 entry point {feats} [f16 kappa {R.KAPPA['f16']:g}] smallest kappa each layer needs: "
+          + " ".join(f"{k}={v:.2f}" for k, v in worst.items() if not k.startswith("pool")) + f"  (max {worst[layer]:.2f} at {layer})")
+    m.set_option("keep_taps", 1)
+    _, _, lg_u8 = m.segment(gray, want_logits=True)
+    assert np.array_equal(lg_u8, logits)
+    for name, t in taps.items():
+        assert np.array_equal(m.activation(name, B), t), name
+

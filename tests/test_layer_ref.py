@@ -3,7 +3,10 @@
 * f32 arithmetic of every kernel form -- a torch-CPU f32 conv (the direct form), the numpy f32 Winograd emulation and the f16
   hi / lo emulation of split precision -- passes the check at its form's kappa, on the GPU matrix's nets scaled down;
 * each mutant of a kernel's arithmetic, applied to ONE output element of an otherwise correct f32 result, is flagged;
-* every case of tests/test_gpu_layer_parity.py runs the kernel families it is meant to exercise (og_unet_plan, no GPU needed).
+* every case of tests/test_gpu_layer_parity.py runs the kernel families it is meant to exercise (og_unet_plan, no GPU needed);
+* the f16 mode's form ("f16": an interval of f16 values per element, not a tolerance): its torch-CPU emulation passes at kappa 16,
+  eleven mutants planted into one element each are flagged there, and the f16 rows of the matrix run, by instantiation, every
+  kernel the mode can launch, with a half last chunk (ConvArgs::k_half) both alone and after full chunks.
 """
 import numpy as np
 import pytest
@@ -106,6 +109,39 @@ def test_split_precision_emulation_passes_at_its_kappa():
     worst = max(w.values())
     assert worst <= R.KAPPA["split"]
     assert worst <= 2 * R.SPLIT_EMULATED_MAX, "the emulated figure the kappa was derived from has moved: re-derive kappa"
+
+
+def f16_emulated_taps(sd, gray, channels_last):
+    """The taps and logits of the f16 mode's torch-CPU emulation (tests/f16_emulation.py) under check_net's names."""
+    import f16_emulation as EMU
+
+    taps = EMU.layer_taps(sd, (gray.astype(np.float32) / 255.0)[:, None], True, channels_last)
+    return taps, taps["head"][:, 0]
+
+
+def test_f16_emulation_passes_at_its_kappa():
+    """The f16 mode's emulation in both memory formats (two summation orders) through the interval check, on the matrix's nets
+    scaled down, the five-level net of the GPU matrix with its own weights and frames, the six special frames; then the composed
+    checks (no downs.0.a, no ups.N.b) on the same taps."""
+    k = R.kappa_of("f16")
+    nets = [(f, H, W, synth.make_unet_state_dict(f, seed=3), frames_of(H, W)) for f, H, W in EMU_NETS]
+    nets += [(f, H, W, synth.make_unet_state_dict(f, seed=11, head_scale=3.0, head_bias=-0.5), gpu_case_frames(H, W, 6))
+             for f, H, W, _ in EMU_GPU_NETS]
+    stored, head, composed = 0.0, 0.0, 0.0
+    for feats, H, W, sd, gray in nets:
+        for cl in (False, True):
+            taps, logits = f16_emulated_taps(sd, gray, cl)
+            w = R.check_net(sd, gray, taps.__getitem__, logits, k, frames=FRAME_ORDER, form="f16")
+            layer, worst = max(((n, v) for n, v in w.items() if n != "head"), key=lambda t: t[1])
+            print(f"f16 emulation {feats} {H}x{W} channels_last={cl}: needs kappa {worst:.2f} ({layer}), head {w['head']:.2f}")
+            stored, head = max(stored, worst), max(head, w["head"])
+            hidden = {n: v for n, v in taps.items() if n not in ("downs.0.a", f"ups.{2 * len(feats) - 1}.b")}
+            wc = R.check_net(sd, gray, hidden.__getitem__, logits, k, frames=FRAME_ORDER, form="f16", fused_first=True, fused_head=True)
+            composed = max(composed, wc["downs.0.b (fused first)"], wc["head (fused)"])
+    print(f"f16 emulation: stored tensors need kappa {stored:.2f}, the head {head:.2f}, the composed checks {composed:.2f}")
+    assert stored <= R.KAPPA["f16"] and head <= R.KAPPA["f16"] and composed <= R.KAPPA["f16"]
+    assert stored <= 2 * R.F16_EMULATED_MAX["stored"] and head <= 2 * R.F16_EMULATED_MAX["head"], \
+        "the emulated figures the kappa was derived from have moved: re-derive kappa"
 
 
 def test_composed_bounds_and_exact_checks_on_the_cpu_chain():
@@ -228,6 +264,171 @@ def test_mutant_is_flagged(mutant):
     print(mutant, "flagged at element", idx, "|err|/bound:", {f: round(v, 2) for f, v in ratios.items()})
 
 
+# ───────────────────────────── mutants of the f16 mode ─────────────────────────────
+
+
+def _q16(v):
+    return np.asarray(v, np.float32).astype(np.float16).astype(np.float32)
+
+
+def _toward_zero16(v):
+    """f32 -> f16 by truncation (round toward zero), as f32."""
+    v = np.asarray(v, np.float32)
+    r = v.astype(np.float16)
+    over = np.abs(r.astype(np.float32)) > np.abs(v)
+    return np.where(over, np.nextafter(r, np.float16(0)), r).astype(np.float32)
+
+
+def _f16_layer(feats=(33, 66), seed=6):
+    """As ``_layer``, with the input an f16 tensor (what an f16-mode layer reads)."""
+    sd, x, wk, bn = _layer(feats, seed)
+    return sd, _q16(x), wk, bn
+
+
+def _f16_conv(sd, x, wk, bn, w=None, eps=O.BN_EPS, store=_q16):
+    """The f16 mode's conv3 + BN + ReLU on the CPU: torch f32 accumulation of exact products, one rounding at the store."""
+    sdm = dict(sd)
+    sdm[wk] = _q16(sd[wk]) if w is None else np.asarray(w, np.float32)
+    import torch
+    import torch.nn.functional as F
+
+    with torch.no_grad():
+        y = F.conv2d(torch.from_numpy(x), torch.from_numpy(sdm[wk]), None, 1, 1)
+        y = F.batch_norm(y, torch.from_numpy(sd[bn + ".running_mean"]), torch.from_numpy(sd[bn + ".running_var"]),
+                         torch.from_numpy(sd[bn + ".weight"]), torch.from_numpy(sd[bn + ".bias"]), False, 0.1, eps)
+        return store(F.relu(y).numpy())
+
+
+def _plant_f16(name, correct, mutated, ref, e, idx=None):
+    """One element of the correct f16 result replaced by the mutant's -- the element where it shows most -- must be flagged there."""
+    need = R.f16_needed(mutated, ref) / e
+    if idx is None:
+        idx = tuple(int(v) for v in np.unravel_index(int(np.argmax(need)), need.shape))
+    got = correct.copy()
+    got[idx] = mutated[idx]
+    with pytest.raises(R.LayerMismatch) as err:
+        R.check_f16(name, got, ref, e)
+    b, c, y, x = idx
+    assert f"ch {c} (y,x)=({y},{x})" in str(err.value) and "1 element(s) outside the interval" in str(err.value), str(err.value)
+    outside = (mutated < R.rne16(ref - e)) | (mutated > R.rne16(ref + e))
+    return float(need[idx]) * R.KAPPA["f16"], idx, float(outside.mean())
+
+
+F16_MUTANTS = ["store_toward_zero", "one_ulp_high", "weights_left_f32", "weights_truncated", "k_half_chunk_dropped",
+               "padded_slot_last_channel", "padding_tap_from_neighbour", "convt_dy_dx_swapped", "bn_eps_10x", "head_from_unrounded",
+               "pool_one_ulp_off"]
+
+
+@pytest.mark.parametrize("mutant", F16_MUTANTS)
+def test_f16_mutant_is_flagged(mutant):
+    kap = R.KAPPA["f16"]
+    sd, x, wk, bn = _f16_layer((96, 192), 8) if mutant == "k_half_chunk_dropped" else _f16_layer()
+    sd16 = R.f16_weights(sd)
+    assert np.array_equal(sd16[wk], _q16(sd[wk])) and not np.array_equal(sd16[wk], sd[wk])
+    assert all(np.array_equal(sd16[k], sd[k]) for k in sd if k.startswith("head.") or ".net." in k and not k.endswith(("0.weight", "3.weight")))
+    assert np.array_equal(sd16["downs.0.net.0.weight"], sd["downs.0.net.0.weight"])
+    ref, _, M = R.conv3_bn_relu(sd16, wk, bn, x)
+    e = R.bound_of(M, kap)
+    correct = _f16_conv(sd, x, wk, bn)
+    s, _, _ = R.fold_bn(sd, bn)
+    sc = s[None, :, None, None]
+    idx = None
+
+    def pre_shifted(delta):   # the float64 result with ``delta`` added before the ReLU, rounded once
+        pre = sc * R.conv3_raw(x, sd16[wk]) + R.fold_bn(sd, bn)[1][None, :, None, None] + delta
+        return _q16(np.maximum(pre, 0))
+
+    if mutant == "store_toward_zero":
+        mutated = _f16_conv(sd, x, wk, bn, store=_toward_zero16)
+    elif mutant == "one_ulp_high":
+        single = (R.rne16(ref - e) == R.rne16(ref + e)) & (ref > 0)
+        print("positive outputs whose interval holds exactly one f16 value: %.1f %%" % (100.0 * single.sum() / (ref > 0).sum()))
+        assert single.sum() > 0.8 * (ref > 0).sum()
+        idx = tuple(int(v) for v in np.argwhere(single)[len(np.argwhere(single)) // 2])
+        mutated = np.nextafter(correct.astype(np.float16), np.float16(np.inf)).astype(np.float32)
+    elif mutant == "weights_left_f32":
+        mutated = _f16_conv(sd, x, wk, bn, w=sd[wk])
+    elif mutant == "weights_truncated":
+        mutated = _f16_conv(sd, x, wk, bn, w=_toward_zero16(sd[wk]))
+    elif mutant == "k_half_chunk_dropped":
+        assert x.shape[1] == 96          # one full 64-channel chunk and a half one: channels 64..95 never accumulated
+        mutated = pre_shifted(-sc * R.conv3_raw(x[:, 64:], sd16[wk][:, 64:]))
+    elif mutant == "padded_slot_last_channel":
+        c = x.shape[1] - 1               # 33 channels: index 32, the only real channel of the half chunk
+        mutated = pre_shifted(-sc * R.conv3_raw(x[:, c:c + 1], sd16[wk][:, c:c + 1]))
+    elif mutant == "padding_tap_from_neighbour":
+        H, W = x.shape[2:]
+        xs = np.zeros_like(x, dtype=np.float64)
+        xs[:, :, 1:, 0] = x[:, :, :-1, W - 1]
+        d = np.zeros((1, sd[wk].shape[0], H, W))
+        for dy in range(3):
+            rows = np.arange(H) + dy - 1
+            ok = (rows >= 0) & (rows < H)
+            d[:, :, ok, 0] += np.einsum("oc,bch->boh", sd16[wk][:, :, dy, 0].astype(np.float64), xs[:, :, rows[ok], 0])
+        mutated = pre_shifted(sc * d)
+    elif mutant == "convt_dy_dx_swapped":
+        t = _q16(np.maximum(np.random.RandomState(2).randn(1, sd["ups.0.weight"].shape[0], 6, 8), 0))
+        ref, M = R.convt(sd16, "ups.0", t)
+        e = R.bound_of(M, kap)
+        import torch
+        import torch.nn.functional as F
+
+        correct = _q16(F.conv_transpose2d(torch.from_numpy(t), torch.from_numpy(sd16["ups.0.weight"]), torch.from_numpy(sd["ups.0.bias"]), 2).numpy())
+        ws = np.ascontiguousarray(sd16["ups.0.weight"].transpose(0, 1, 3, 2))
+        mutated = _q16(R.convt_raw(t, ws) + sd["ups.0.bias"].astype(np.float64)[None, :, None, None])
+    elif mutant == "bn_eps_10x":
+        mutated = _f16_conv(sd, x, wk, bn, eps=10 * O.BN_EPS)
+    elif mutant == "head_from_unrounded":
+        # the f32 logits are held to the magnitude check from the STORED (rounded) last activation
+        sdh = synth.make_unet_state_dict((33, 66), seed=6, head_scale=3.0, head_bias=-0.5)
+        act32 = np.maximum(np.random.RandomState(3).randn(1, 33, 16, 24), 0).astype(np.float32)    # the f32 value before its rounding
+        stored = _q16(act32)
+        ref_h, M_h = R.head(sdh, stored)
+        bound = R.bound_of(M_h, kap)
+        good = ref_h.astype(np.float32)
+        assert R.check("head (correct)", good, ref_h, bound) <= 1.0
+        ratio, idx = _plant(mutant, good, R.head(sdh, act32)[0].astype(np.float32), ref_h, bound)
+        print(mutant, "flagged at element", idx, "|err|/bound: %.1f" % ratio)
+        return
+    elif mutant == "pool_one_ulp_off":
+        # pool of a tensor one f16 ulp off in one element (the maximum of its window): bit-exact check against maxpool2 of the stored tensor
+        pooled = R.maxpool2(correct)
+        y, xx = 4, 6
+        win = correct[0, 2, 2 * y:2 * y + 2, 2 * xx:2 * xx + 2]
+        off = correct.copy()
+        iy, ix = np.unravel_index(int(np.argmax(win)), win.shape)
+        off[0, 2, 2 * y + iy, 2 * xx + ix] = np.nextafter(np.float16(win.max()), np.float16(np.inf))
+        R.check_exact("pool1", pooled, R.maxpool2(correct))
+        with pytest.raises(R.LayerMismatch, match=rf"pool1: not bit-identical at frame 0 ch 2 \(y,x\)=\({y},{xx}\)"):
+            R.check_exact("pool1", R.maxpool2(off), R.maxpool2(correct))
+        return
+    assert R.check_f16(mutant + " (correct)", correct, ref, e) <= kap      # the unmutated result passes
+    need, idx, frac = _plant_f16(mutant, correct, mutated, ref, e, idx)
+    print(mutant, "flagged at element", idx, "needs kappa %.3g; all elements outside if applied everywhere: %.1f %%" % (need, 100 * frac))
+
+
+def test_check_f16_refuses_values_that_are_not_f16_and_non_finite_ones():
+    sd, x, wk, bn = _f16_layer()
+    ref, _, M = R.conv3_bn_relu(R.f16_weights(sd), wk, bn, x)
+    e = R.bound_of(M, R.KAPPA["f16"])
+    good = _f16_conv(sd, x, wk, bn)
+    idx = np.unravel_index(int(np.argmax(ref)), ref.shape)
+    bad = good.copy()
+    bad[idx] = np.float32(ref[idx])                     # the better value, but not one the f16 store can hold
+    assert bad[idx] != good[idx]
+    with pytest.raises(R.LayerMismatch, match="is not an f16 value"):
+        R.check_f16("layer", bad, ref, e)
+    bad[idx] = np.inf
+    with pytest.raises(R.LayerMismatch, match="non-finite"):
+        R.check_f16("layer", bad, ref, e)
+    # subnormal f16 references are ordinary values: a flushed one is flagged, the kept one passes
+    tiny = np.full((1, 1, 1, 2), 3 * 2.0 ** -24)
+    et = R.bound_of(tiny, R.KAPPA["f16"])
+    assert R.check_f16("subnormal", tiny.astype(np.float32), tiny, et) == 0.0
+    with pytest.raises(R.LayerMismatch, match="outside its f16 interval"):
+        R.check_f16("subnormal", np.zeros((1, 1, 1, 2), np.float32), tiny, et)
+
+
 # ───────────────────────────── coverage of the GPU matrix ─────────────────────────────
 
 
@@ -237,6 +438,18 @@ def test_gpu_matrix_case_runs_the_kernels_it_claims(case):
 
     recs, _ = plan(case["feats"], case["B"], case["H"], case["W"], 1, R.option_string(case["options"]))
     check(recs, case["id"])
+    if case["form"] == "f16":      # by instantiation: the text og_unet_plan records for each f16 launch
+        assert case["options"]["precision"] == 2
+        insts = R.plan_instantiations(recs)
+        missing = set(case["families"]) - insts
+        assert not missing, (case["id"], sorted(missing), sorted(insts))
+        first, first_fused, head = (R.F16_KERNELS[k][0] for k in ("k_conv_first_f", "<1,0,8,3,FIRST>", "k_head_f"))
+        assert (first_fused in insts) == case["fused_first"] and (first in insts) != case["fused_first"], (case["id"], sorted(insts))
+        if case["fused_head"]:
+            assert head not in insts and case["options"]["keep_taps"] == 0
+        assert all("k_conv_mfma_f<" in r["kernel"] for r in recs if "k_conv" in r["kernel"] and "k_conv_first" not in r["kernel"])
+        assert set(case["prof"]) <= {v[1] for v in R.F16_KERNELS.values()}
+        return
     fams = R.plan_families(recs, case["B"])
     missing = set(case["families"]) - fams
     assert not missing, (case["id"], sorted(missing), sorted(fams))
@@ -246,3 +459,30 @@ def test_gpu_matrix_case_runs_the_kernels_it_claims(case):
         assert "first-fused" not in fams
     if case["fused_head"]:
         assert "k_head" not in fams and case["options"]["keep_taps"] == 0
+
+
+def test_f16_matrix_covers_every_instantiation_and_both_half_chunks():
+    """Over the f16 rows: every kernel instantiation the library can launch in the f16 mode (the list of its launch sites:
+    launch_conv_f's six, the fused first layer, the first-layer and head kernels), and a half last chunk (ConvArgs::k_half) both
+    as the only chunk of a layer and after full 64-channel chunks."""
+    from test_launch_plan import plan
+
+    cases = [c for c in R.GPU_CASES if c["form"] == "f16"]
+    assert len(cases) == 15 and all(c["options"]["precision"] == 2 for c in cases)
+    claimed, seen, halves = set(), set(), {}
+    for c in cases:
+        recs, _ = plan(c["feats"], c["B"], c["H"], c["W"], 1, R.option_string(c["options"]))
+        claimed |= set(c["families"])
+        seen |= R.plan_instantiations(recs)
+        for kind in R.plan_half_chunks(recs):
+            halves.setdefault(kind, []).append(c["id"])
+    every = {v[0] for v in R.F16_KERNELS.values()}
+    assert len(every) == 9
+    assert claimed == every, sorted(every - claimed)
+    assert seen == every, sorted(seen ^ every)          # and the plans show no f16 kernel the list does not know
+    assert set(halves) == {"only", "after-full"}, halves
+    assert "f16-padded-33x66-32x64" in halves["after-full"]     # the 96- and 160-channel layers
+    # the existing helper is untouched by the f16 labels: it still reports families, not instantiations
+    recs, _ = plan(R.FULL, 2, 256, 256, 1, "precision=2")
+    assert "k_conv_mfma_f" in R.plan_families(recs, 2) and "first-fused" not in R.plan_families(recs, 2)
+

@@ -297,7 +297,14 @@ int og_yolo_finalize(og_yolo* h);
  * "splitk_max" [8], "splitk_min_steps" [3], "splitk_slots" [1], "splitk_div" [2], "latency_nt1" [1] shape the split (they change the
  * summation order, for every call of the handle alike); "head_fused" [1]: a Detect level's box and class branches as one chain;
  * "zero_copy" [1]: latency-path calls without `pred` read the frame from, and write `best` to, the handle's pinned host buffer directly
- * (no H2D / D2H command on the 58-launch chain's one stream). */
+ * (no H2D / D2H command on the 58-launch chain's one stream).
+ * "precision" [0]: 0 = f32 (the default, unchanged); 2 = opt-in f16 mode: the weights of every MFMA conv rounded to f16 once at
+ * finalize, activations stored as f16 (each rounded exactly once, in the epilogue that produces it), f32 accumulation on
+ * v_mfma_f32_32x32x16_f16 in ONE fixed K order with no split of K, model.0 on its f32 fma chain with a rounded output, and the DFL /
+ * class logits of Detect's last layers kept in f32 for the unchanged decode.  1 and >= 3 return OG_EINVAL (no split precision for the
+ * detector).  Settable before and after og_yolo_finalize; a switch re-plans the arena on the next call.  An activation beyond
+ * |v| > 60000 makes the call (or the og_yolo_sync / og_yolo_detect_u8_end that waits for it) return OG_ERANGE; the handle stays usable.
+ * og_yolo_get_activation returns f32 in both modes. */
 int og_yolo_set_option(og_yolo* h, const char* name, int value);
 int og_yolo_num_anchors(og_yolo* h, int H, int W);    /* (H/8)(W/8)+(H/16)(W/16)+(H/32)(W/32) */
 /* frames [B,H,W,3] u8 BGR at network resolution (H,W multiples of 32; the caller letterboxes).

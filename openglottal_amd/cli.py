@@ -30,6 +30,10 @@ def main(argv=None) -> int:
                         "(2.5x faster, same reference fixtures and tolerance; fails loudly if an activation leaves the f16 range); "
                         "f16: opt-in half precision (f16 operands and stored activations, f32 accumulation; fastest, half the "
                         "memory; logits move by ~1e-2, so masks may differ from f32 where a logit is near zero)")
+    r.add_argument("--detector-precision", choices=["f32", "f16"], default="f32",
+                   help="arithmetic of the YOLOv8 detector (--pipeline unet), independent of --precision (which is the U-Net's): "
+                        "f32 (default) or the opt-in f16 mode (f16 weights and activations, f32 accumulation, f32 logits; the "
+                        "throughput mode of batched calls)")
     a = ap.parse_args(argv)
 
     import torch
@@ -43,7 +47,7 @@ def main(argv=None) -> int:
     model.eval()
     if a.precision != "f32":
         model.set_option("precision", {"split": 1, "f16": 2}[a.precision])
-    detector = TemporalDetector(a.yolo_weights) if a.pipeline == "unet" else None
+    detector = TemporalDetector(a.yolo_weights, precision=a.detector_precision) if a.pipeline == "unet" else None
     feats = extract_features_unet(a.video, detector, model, a.device)
     if feats is None:
         print("No glottis detected — check your weights or input video.")

@@ -3076,6 +3076,265 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_f(ConvArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------
+// The detector's f16 mode (og_yolo "precision" 2): k_conv_mfma_f's machinery (F layout, 64-channel chunks with k_half, LDS-DMA
+// halo image, weight ring, strides in 4-byte units) with what the YOLOv8 graph needs: MODE 2 (1x1), MODE 3 (3x3 stride 2 through
+// the space-to-depth view), SiLU, the Bottleneck residual, channel segments of wider buffers on both sides, partial tiles
+// (8x8 and 5x8 maps) clipped by the bounds check.  ONE fixed K order per layer -- chunk-major, tap-minor; MODE 3: parity-major,
+// chunk, tap -- and no split of K in any form, so a frame's bits do not depend on the launch it rides in.
+// ---------------------------------------------------------------------------------------
+// Epilogue: fmaf(acc, scale, shift) -> SiLU (ACT 2) or identity in f32 -> (+ residual, read as f16 and widened, added in f32) ->
+// ONE rounding to f16 -> the wave's LDS scratch -> 16-byte stores of 8 channels, as conv_epilogue_f.
+template <int NT, int ACT, bool RES, int MS>
+__device__ __forceinline__ void conv_epilogue_fy(const ConvArgs& a, const f32x16* acc, int n_tile, int b, int ty0, int tx0, int wm, int wn,
+                                                 int li, int lh, float sc, float sh, unsigned char* scratch) {
+    constexpr int WROWS = 32 * NT;
+    const int lane = li + 32 * lh;
+    const int cbase = n_tile * WROWS + wn * 32;
+    const int cb4 = cbase >> 1;   // this wave's first channel in 4-byte units
+    // store role: tile-image row (lane >> 2) + 16 q, 16-byte slot lane & 3; row i sits at x = 2((i&7)>>2) + (i&1) + 4(i>>3), y = (i&3)>>1
+    const int srow = lane >> 2, sslot = lane & 3;
+    const int sxl = 2 * ((srow & 7) >> 2) + (srow & 1) + 4 * (srow >> 3), syl = (srow & 3) >> 1;
+    const __amdgpu_buffer_rsrc_t out_rs = og_rsrc(a.out + (long long)b * a.out_frame_stride, (unsigned)a.out_frame_stride * 4u);
+    const unsigned lp = (unsigned)(((syl * a.W + sxl) * a.out_pix_stride + sslot * 4) * 4);
+    unsigned vq[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) vq[q] = (tx0 + sxl + 8 * q < a.W) ? lp : OG_OOB;
+    _Float16* const hw = (_Float16*)scratch + (128 * lh + li);   // + (8g + rr) * 32: row 8g + 4lh + rr, channel li
+    const unsigned char* const sr = scratch + srow * 64 + sslot * 16;   // + q * 1024
+    const _Float16* const resp = RES ? (const _Float16*)(a.res + (long long)b * a.res_frame_stride + a.res_ch_off) + cbase + li : nullptr;
+
+    float h_absmax = 0.f;
+#pragma unroll
+    for (int m = 0; m < MS; ++m) {
+        const int y0 = ty0 + 2 * (wm * MS + m);
+        const f32x2 sc2 = {sc, sc}, sh2 = {sh, sh};
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x2 a01 = og_fma2(f32x2{acc[m][4 * g], acc[m][4 * g + 1]}, sc2, sh2);
+            const f32x2 a23 = og_fma2(f32x2{acc[m][4 * g + 2], acc[m][4 * g + 3]}, sc2, sh2);
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                float v = (rr == 0) ? a01.x : (rr == 1) ? a01.y : (rr == 2) ? a23.x : a23.y;
+                if (ACT == 2) v = v / (1.0f + expf(-v));
+                if (RES) {
+                    const int y = y0 + (rr >> 1), x = tx0 + 4 * g + 2 * lh + (rr & 1);
+                    if (y < a.H && x < a.W) v += (float)resp[((long long)y * a.W + x) * a.res_pix_stride * 2];
+                }
+                h_absmax = fmaxf(h_absmax, fabsf(v));
+                hw[(8 * g + rr) * 32] = (_Float16)v;
+            }
+        }
+        asm volatile("" ::: "memory");   // the 2-byte writes above are read back as 16-byte words below (and vice versa in the next round)
+        if (y0 < a.H) {
+            const bool half = (y0 + 1 >= a.H);   // odd H (maps of 160-pixel inputs): only the first row exists
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const f32x4 v4 = *(const f32x4*)(sr + q * 1024);
+                const int so = ((y0 * a.W + tx0 + 8 * q) * a.out_pix_stride + a.out_ch_off + cb4) * 4;
+                og_buffer_store16(v4, out_rs, (half && syl) ? OG_OOB : vq[q], (unsigned)so);
+            }
+        }
+        asm volatile("" ::: "memory");
+    }
+    og_flag_range(h_absmax, a.range_flag);
+}
+
+// MODE 0: 3x3 stride 1; MODE 2: 1x1; MODE 3: 3x3 stride 2 (a.H, a.W = OUTPUT size; virtual chunk = (input-pixel parity, 64-channel
+// chunk), a.n_chunks = 4 x chunks per pixel, only the 9 non-zero (tap, parity) pairs are executed and packed).  8x16 tiles.
+// F32OUT (the Detect logit layers): f16 operands as everywhere, the output stored in f32 through conv_epilogue_b, so a.out_* count
+// floats there.  a.k_half: the last 64-channel chunk of a pixel holds 32 channels (2 MFMAs per tap; a lone half chunk fetches 64 bytes).
+template <int NT, int MODE, int OCC, bool F32OUT = false>
+__global__ __launch_bounds__(256, OCC) void k_conv_mfma_fy(ConvArgs a) {
+    static_assert(MODE == 0 || MODE == 2 || MODE == 3, "detector f16 mode: 3x3, 1x1 and 3x3 stride-2 convs");
+    constexpr int TW = 16, TH = 8;
+    constexpr int PAD = (MODE == 0 || MODE == 3) ? 1 : 0;
+    constexpr int HW_ = (MODE == 3) ? TW + 2 : TW + 2 * PAD;   // MODE 3 needs 17 columns; an even pitch keeps the slot swizzle conflict-free
+    constexpr int HH_ = (MODE == 3) ? TH + 1 : TH + 2 * PAD;
+    constexpr int HALO_PIX = HW_ * HH_;
+    constexpr int HALO_BYTES = HALO_PIX * 128;
+    constexpr int HALO_PIECES = HALO_PIX * 8;
+    constexpr int HALO_IT = (HALO_PIECES + 255) / 256;
+    constexpr int TAPS = (MODE == 0) ? 9 : (MODE == 3) ? 4 : 1;
+    constexpr int WROWS = 32 * NT;
+    constexpr int WBYTES = WROWS * 128;
+    constexpr int NSTG = (MODE == 0) ? 3 : 2;
+    constexpr int WAHEAD = (NSTG == 3) ? 2 : 1;
+    constexpr int WM = 4 / NT;
+    constexpr int MS = (TH / 2) / WM;
+
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wn = wave % NT;
+    const int wm = wave / NT;
+    const int li = lane & 31;
+    const int lh = lane >> 5;
+
+    // ---- tile decode (scalar): grid = (tile column, tile row, frame group x column tile x frame in group), as k_conv_mfma_f ----
+    const int bz = (int)blockIdx.z;
+    const int gz = a.zdiv << a.zgroup_shift;
+    const int q = (gz == 1) ? bz : (int)(((float)bz + 0.5f) * a.zrcp);
+    const int rz = bz - q * gz;
+    const int n_tile = rz >> a.zgroup_shift;
+    const int b = (q << a.zgroup_shift) + (rz & ((1 << a.zgroup_shift) - 1));
+    if (b >= a.frames) return;   // tail of the last frame group (whole workgroup, before any barrier)
+    const int ty0 = (int)blockIdx.y * TH;
+    const int tx0 = (int)blockIdx.x * TW;
+    const int n_chunks = a.n_chunks;
+    const int cpc = (MODE == 3) ? n_chunks >> 2 : n_chunks;     // 64-channel chunks per pixel; the last one holds 32 channels when a.k_half
+    const int n_steps = (MODE == 3) ? cpc * 9 : n_chunks * TAPS;
+    const bool only_half = (a.k_half != 0 && cpc == 1);
+
+    const og_i32x4 in_rsrc = og_make_rsrc(a.in + (long long)b * a.in_frame_stride + a.in_ch_off,
+                                          (unsigned)(a.in_frame_stride - a.in_ch_off) * 4u);
+
+    unsigned hoff[HALO_IT];
+    {
+        int hy = ((tid >> 3) >= HW_) ? 1 : 0;
+        int hx = (tid >> 3) - hy * HW_;
+        const int in_w = (MODE == 3) ? 2 * a.W : a.W;
+        const int row_b = in_w * a.in_pix_stride * ((MODE == 3) ? 8 : 4);   // bytes per halo row step (MODE 3: a 2x2 input block per step)
+        const int col_b = a.in_pix_stride * ((MODE == 3) ? 8 : 4);
+#pragma unroll
+        for (int it = 0; it < HALO_IT; ++it) {
+            const int logical = (tid & 7) ^ og_halo_swz(hy, hx);
+            const int gy = ty0 + hy - PAD, gx = tx0 + hx - PAD;
+            const bool inb = (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W && !(only_half && logical >= 4);
+            hoff[it] = inb ? (unsigned)(gy * row_b + gx * col_b + logical * 16) : OG_OOB;
+            hx += 32 % HW_;
+            hy += 32 / HW_;
+            if (hx >= HW_) { hx -= HW_; hy += 1; }
+        }
+    }
+    const bool last_valid = ((HALO_IT - 1) * 256 + tid) < HALO_PIECES;
+
+    const unsigned lds0 = og_lds_addr(smem);
+    auto stage_halo = [&](int par, int cc) {   // (input-pixel parity (MODE 3 only), 64-channel chunk of the pixel)
+        const unsigned base = lds0 + wave * 1024;
+        unsigned soff = (unsigned)cc * 128u;
+        if (MODE == 3) soff += (unsigned)((((par >> 1) * 2 * a.W + (par & 1)) * a.in_pix_stride) * 4);
+#pragma unroll
+        for (int it = 0; it < HALO_IT; ++it) {
+            if (it < HALO_IT - 1 || last_valid) glds16b(hoff[it], in_rsrc, soff, base + it * 4096);
+        }
+    };
+    const og_i32x4 w_rsrc = og_make_rsrc(a.wpk + (long long)n_tile * n_steps * (WROWS * 32), (unsigned)n_steps * WBYTES);
+    const unsigned woff = (unsigned)tid * 16u;
+    auto stage_w = [&](int stage, int step) {
+        const unsigned base = lds0 + HALO_BYTES + stage * WBYTES + wave * 1024;
+#pragma unroll
+        for (int i = 0; i < NT; ++i) glds16b(woff, w_rsrc, (unsigned)step * WBYTES + i * 4096, base + i * 4096);
+    };
+
+    stage_halo(0, 0);
+    stage_w(0, 0);
+    if (WAHEAD == 2 && 1 < n_steps) stage_w(1, 1);
+
+    // ---- fragment addressing: k_conv_mfma_f's ----
+    const int px0 = 2 * (li >> 2) + (li & 1);
+    const int pyl = (li >> 1) & 1;
+    const int brow = wn * 32 + li;
+    const int boff = brow * 128 + ((lh ^ ((brow >> 1) & 7)) << 4);
+    constexpr int NDX = (MODE == 0) ? 3 : (MODE == 3) ? 2 : 1;
+    unsigned abase[NDX][4];
+#pragma unroll
+    for (int dx = 0; dx < NDX; ++dx) {
+        const int px = px0 + dx;
+        const unsigned o = (unsigned)((pyl * HW_ + px) * 128 + ((lh ^ og_halo_swz(pyl, px)) << 4) + wm * (MS * 2 * HW_ * 128));
+#pragma unroll
+        for (int pat = 0; pat < 4; ++pat) {
+            abase[dx][pat] = lds0 + (o ^ (unsigned)(pat << 5));
+            asm volatile("" : "+v"(abase[dx][pat]));
+        }
+    }
+    unsigned bbase[4];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+        bbase[jj] = lds0 + HALO_BYTES + (unsigned)(boff ^ (jj << 5));
+        asm volatile("" : "+v"(bbase[jj]));
+    }
+
+    const int ecol = n_tile * WROWS + wn * 32 + li;
+    const float esc = a.scale[ecol], esh = a.shift[ecol];
+
+    f32x16 acc[MS];
+#pragma unroll
+    for (int m = 0; m < MS; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
+
+    og_wait_dma();
+    __syncthreads();
+
+    int step = 0;   // index of the weight block = of the executed (chunk, tap) step
+    int par = 0, cc = 0;
+    for (int c = 0; c < n_chunks; ++c) {
+        const bool half = (a.k_half != 0 && cc == cpc - 1);   // wave-uniform: k-groups 2, 3 of this chunk do not exist
+#pragma unroll
+        for (int t = 0; t < TAPS; ++t) {
+            if (MODE == 3) {  // tap (ty,tx) of the 2x2 kernel meets parity (py,px): zero unless (ty==1 || py==1) and (tx==1 || px==1)
+                if (((t >> 1) == 0 && (par & 2) == 0) || ((t & 1) == 0 && (par & 1) == 0)) continue;
+            }
+            const int stg = (NSTG == 3) ? t % 3 : (step & 1), stg_next = (NSTG == 3) ? (t + WAHEAD) % 3 : ((step + 1) & 1);
+            const bool more = (step + WAHEAD < n_steps);
+            if (more) stage_w(stg_next, step + WAHEAD);
+
+            const unsigned wb = (unsigned)stg * WBYTES;
+            const int dy = (MODE == 0) ? t / 3 : (MODE == 3) ? (t >> 1) : 0;
+            const int dx = (MODE == 0) ? t % 3 : (MODE == 3) ? (t & 1) : 0;
+            // k-group j -> 16-byte slot 2j + lh of the 128-byte row = channels 16j + 8lh .. +7 of the chunk
+            if (!half) {
+                f32x4 bv[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) bv[j] = og_lds_read16(bbase[j] + wb);
+#pragma unroll
+                for (int m = 0; m < MS; ++m) {
+                    f32x4 av[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) av[j] = og_lds_read16(abase[dx][j ^ ((dy & 1) << 1)] + (unsigned)((dy + 2 * m) * (HW_ * 128)));
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(og_h8, av[j]), __builtin_bit_cast(og_h8, bv[j]), acc[m], 0, 0, 0);
+                }
+            } else {
+                f32x4 bv[2];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) bv[j] = og_lds_read16(bbase[j] + wb);
+#pragma unroll
+                for (int m = 0; m < MS; ++m) {
+                    f32x4 av[2];
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) av[j] = og_lds_read16(abase[dx][j ^ ((dy & 1) << 1)] + (unsigned)((dy + 2 * m) * (HW_ * 128)));
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+                        acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(og_h8, av[j]), __builtin_bit_cast(og_h8, bv[j]), acc[m], 0, 0, 0);
+                }
+            }
+            // the NEXT step's slice must have landed; the one staged just now (NT instructions per wave) may stay in flight
+            if (WAHEAD == 2 && more) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NT) : "memory");
+            else og_wait_dma();
+            __syncthreads();
+            ++step;
+        }
+        if (++cc == cpc) { cc = 0; ++par; }
+        if (c + 1 < n_chunks) {  // every read of the halo buffer completed before the barrier above
+            stage_halo(par, cc);
+            og_wait_dma();
+            __syncthreads();
+        }
+    }
+
+    // ---- epilogue (all staging buffers are dead behind the last barrier: LDS is scratch now) ----
+    unsigned char* const scr = smem + wave * 5120;
+    if (F32OUT) conv_epilogue_b<NT, 2, TH, 0, false>(a, acc, n_tile, b, ty0, tx0, wm, wn, li, lh, esc, esh, scr);
+    else if (a.act == 2 && a.res != nullptr) conv_epilogue_fy<NT, 2, true, MS>(a, acc, n_tile, b, ty0, tx0, wm, wn, li, lh, esc, esh, scr);
+    else if (a.act == 2) conv_epilogue_fy<NT, 2, false, MS>(a, acc, n_tile, b, ty0, tx0, wm, wn, li, lh, esc, esh, scr);
+    else conv_epilogue_fy<NT, 0, false, MS>(a, acc, n_tile, b, ty0, tx0, wm, wn, li, lh, esc, esh, scr);
+}
+
+// ---------------------------------------------------------------------------------------
 // Generation 2 of the implicit-GEMM conv: PERSISTENT workgroups walking a flat sequence of
 // (item = (n_tile, frame, spatial tile), 32-channel chunk, tap-group) steps.
 //   * the next step's weight slices and the next unit's halo (possibly of the NEXT tile) are
@@ -3886,6 +4145,98 @@ __global__ __launch_bounds__(256) void k_upsample2(const float* __restrict__ in,
     const long long b = p / Hout;
     const f32x4 v = *(const f32x4*)(in + b * in_frame_stride + ((long long)(y >> 1) * (Wout >> 1) + (x >> 1)) * in_pix_stride + in_off + c);
     *(f32x4*)(out + b * out_frame_stride + ((long long)y * Wout + x) * out_pix_stride + out_off + c) = v;
+}
+
+// ---- detector f16 mode ("precision" 2): the helper kernels on the F layout (strides and channel offsets in 4-byte units) ----
+// k_upsample2 serves as it is (a 16-byte copy is 8 f16 channels: the host passes channels / 8 as C4).
+
+// model.0 (u8 BGR frame -> 16 channels): k_conv_direct<true>'s f32 weights and fma chain (ky, kx, ci), SiLU in f32, ONE rounding
+// to f16, 8-byte stores of 4 channels -- the detector's counterpart of k_conv_first_f.
+__global__ __launch_bounds__(256) void k_conv_direct_u8h(const uint8_t* __restrict__ in, int Hin, int Win, const float* __restrict__ w,
+                                                         const float* __restrict__ scale, const float* __restrict__ shift, int Cout_p,
+                                                         float* __restrict__ out, long long out_frame_stride, int out_pix_stride,
+                                                         int out_ch_off, int Hout, int Wout, int ks, int stride, int pad, int act,
+                                                         int total_quads, int cq_shift, int* range_flag) {
+    constexpr int PX = 4;
+    const int cq = threadIdx.x & ((1 << cq_shift) - 1);
+    const int q = (blockIdx.x * 256 + threadIdx.x) >> cq_shift;
+    float vmax = 0.f;
+    if (q < total_quads) {
+        const int qpr = (Wout + PX - 1) / PX;
+        const int row = q / qpr;
+        const int ox0 = (q - row * qpr) * PX;
+        const int b = row / Hout;
+        const int oy = row - b * Hout;
+        const int c0 = blockIdx.y * 32 + cq * 4;
+        f32x4 acc[PX];
+#pragma unroll
+        for (int j = 0; j < PX; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int ky = 0; ky < ks; ++ky) {
+            const int iy = oy * stride - pad + ky;
+            if (iy < 0 || iy >= Hin) continue;
+            const uint8_t* rowp = in + ((long long)b * Hin + iy) * Win * 3;
+            for (int kx = 0; kx < ks; ++kx) {
+                const float* wp = w + (long long)((ky * ks + kx) * 3) * Cout_p + c0;
+#pragma unroll
+                for (int ci = 0; ci < 3; ++ci) {
+                    const f32x4 wv = *(const f32x4*)(wp + ci * Cout_p);
+#pragma unroll
+                    for (int j = 0; j < PX; ++j) {
+                        const int ix = (ox0 + j) * stride - pad + kx;
+                        const bool ok = ix >= 0 && ix < Win && (ox0 + j) < Wout;
+                        const float xv = ok ? (float)rowp[ix * 3 + 2 - ci] / 255.0f : 0.f;  // RGB[ci] = BGR[2-ci]
+                        acc[j].x = fmaf(xv, wv.x, acc[j].x);
+                        acc[j].y = fmaf(xv, wv.y, acc[j].y);
+                        acc[j].z = fmaf(xv, wv.z, acc[j].z);
+                        acc[j].w = fmaf(xv, wv.w, acc[j].w);
+                    }
+                }
+            }
+        }
+        const f32x4 sc = *(const f32x4*)(scale + c0);
+        const f32x4 sh = *(const f32x4*)(shift + c0);
+#pragma unroll
+        for (int j = 0; j < PX; ++j) {
+            if (ox0 + j < Wout) {
+                og_h4 o;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float v = og_act(fmaf(acc[j][e], sc[e], sh[e]), act);
+                    vmax = fmaxf(vmax, fabsf(v));
+                    o[e] = (_Float16)v;
+                }
+                float* const px = out + (long long)b * out_frame_stride + ((long long)oy * Wout + ox0 + j) * out_pix_stride + out_ch_off;
+                *(og_h4*)((_Float16*)px + c0) = o;
+            }
+        }
+    }
+    og_flag_range(vmax, range_flag);
+}
+
+// SPPF's MaxPool2d(5, 1, 2) on f16 values: a packed max of 8 channels per thread (exact: no rounding takes place).
+__global__ __launch_bounds__(256) void k_maxpool5_h(const float* __restrict__ buf_in, float* __restrict__ buf_out, long long frame_stride,
+                                                    int pix_stride, int in_off, int out_off, int C8 /*channels/8*/, int H, int W, long long total) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int c = (int)(t % C8) * 4;   // 4-byte units
+    long long p = t / C8;
+    const int x = (int)(p % W);
+    p /= W;
+    const int y = (int)(p % H);
+    const long long b = p / H;
+    const _Float16 ninf = (_Float16)(-INFINITY);
+    og_h8 m = {ninf, ninf, ninf, ninf, ninf, ninf, ninf, ninf};
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int yy = y + dy;
+        if (yy < 0 || yy >= H) continue;
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int xx = x + dx;
+            if (xx < 0 || xx >= W) continue;
+            const og_h8 v = *(const og_h8*)(buf_in + b * frame_stride + ((long long)yy * W + xx) * pix_stride + in_off + c);
+            m = __builtin_elementwise_max(m, v);
+        }
+    }
+    *(og_h8*)(buf_out + b * frame_stride + ((long long)y * W + x) * pix_stride + out_off + c) = m;
 }
 
 // Detect head decode: DFL (softmax expectation over 16 bins per side), dist2bbox around the

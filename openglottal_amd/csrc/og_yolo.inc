@@ -20,7 +20,12 @@ struct YView {  // one logical tensor = a channel segment of an NHWC buffer
     int off = 0;      // first channel of the segment
     int C = 0;        // logical channels
     int H = 0, W = 0;
+    int es = 1;       // elements per 4-byte unit: 1 = f32, 2 = f16 ("precision" 2; Ctot, off and C keep counting CHANNELS)
     long long frame_stride() const { return (long long)H * W * Ctot; }
+    // what the kernels take: strides and channel offsets in 4-byte units (every physical width and offset is a multiple of 32 channels)
+    long long fs4() const { return frame_stride() / es; }
+    int ps4() const { return Ctot / es; }
+    int off4() const { return off / es; }
 };
 
 struct YSeg {
@@ -33,6 +38,13 @@ struct YConv {
     int Cin = 0, Cout = 0, Cin_p = 0, Cout_p = 0, ks = 1, stride = 1, act = 2, NT = 1;
     float *d_w = nullptr, *d_scale = nullptr, *d_shift = nullptr;
     float* d_w1 = nullptr;   // NT == 2 layers: the same weights packed for 32-column tiles (latency path: twice the workgroups)
+    float* d_wf = nullptr;   // MFMA convs: the f16 image of the same weights ("precision" 2, k_conv_mfma_fy), rounded once at finalize
+    bool f32out = false;     // Detect's last Conv2d layers: their logits stay f32 in f16 mode
+};
+
+struct YAct {  // a named tensor: channel segments of one buffer, concatenated in order
+    YView v;
+    std::vector<YSeg> segs;   // (first channel in the buffer, logical width)
 };
 
 }  // namespace
@@ -52,7 +64,10 @@ struct og_yolo {
     // arena
     int capB = 0, aH = 0, aW = 0;
     void* arena = nullptr;
-    std::map<std::string, YView> acts;  // named logical tensors (for parity tests)
+    std::map<std::string, YAct> acts;   // named logical tensors (for parity tests)
+    int precision = 0;           // 0: f32 (default); 2: opt-in f16 mode (f16 weights and activations, f32 accumulation, f32 logits)
+    int* h_range = nullptr;      // f16 mode: host-mapped word the kernels raise when an activation leaves the f16 range
+    int* d_range = nullptr;
     void* stage = nullptr;
     size_t stage_bytes = 0;
     int lastB = 0;
@@ -262,7 +277,37 @@ int y_build_conv(og_yolo* h, const std::string& mod, bool plain_conv2d, int kind
         };
         pk = pack_gemm_b(L.Cout_p, L.Cin_p, kk, L.NT, at);
         if (L.NT == 2) pk1 = pack_gemm_b(L.Cout_p, L.Cin_p, kk, 1, at);
+        if ((rc = upload(pack_gemm_b_f(L.Cout_p, L.Cin_p, kk, L.NT, at), &L.d_wf))) return rc;
     }
+    if (kind == 4) {
+        // k_conv_mfma_fy MODE 3: the same 9 (parity, tap) pairs over 64-channel chunks (F layout: eight 16-byte slots of 8 f16),
+        // in the kernel's execution order: parity-major, chunk, tap.  A padded Cin that is an odd multiple of 32 leaves the upper
+        // half of each parity's last chunk zero (the kernel skips it: ConvArgs::k_half).
+        const int rows = 32 * L.NT, n_tiles = L.Cout_p / rows, cpc = (L.Cin_p + 63) / 64;
+        std::vector<float> pf((size_t)L.Cout_p * cpc * 32 * 9, 0.f);
+        _Float16* o16 = (_Float16*)pf.data();
+        size_t o = 0;   // in halves
+        for (int nt = 0; nt < n_tiles; ++nt)
+            for (int par = 0; par < 4; ++par)
+                for (int cc = 0; cc < cpc; ++cc)
+                    for (int t = 0; t < 4; ++t) {
+                        const int ty = t >> 1, tx = t & 1, py = par >> 1, px = par & 1;
+                        if ((ty == 0 && py == 0) || (tx == 0 && px == 0)) continue;
+                        const int ky = (ty == 0) ? 0 : 1 + py, kx = (tx == 0) ? 0 : 1 + px;
+                        for (int r = 0; r < rows; ++r)
+                            for (int ps = 0; ps < 8; ++ps) {
+                                const int sl = ps ^ ((r >> 1) & 7);
+                                for (int e = 0; e < 8; ++e) {
+                                    const int k = cc * 64 + sl * 8 + e;
+                                    const int co = cout_map[nt * rows + r], ci = (k < L.Cin_p) ? cin_map[k] : -1;
+                                    o16[o + (size_t)r * 64 + ps * 8 + e] = (_Float16)((co < 0 || ci < 0) ? 0.f : w[((size_t)co * Cin + ci) * 9 + ky * 3 + kx]);
+                                }
+                            }
+                        o += (size_t)rows * 64;
+                    }
+        if ((rc = upload(pf, &L.d_wf))) return rc;
+    }
+    L.f32out = plain_conv2d;
     if ((rc = upload(pk, &L.d_w))) return rc;
     if (!pk1.empty() && (rc = upload(pk1, &L.d_w1))) return rc;
     if ((rc = upload(sc, &L.d_scale))) return rc;
@@ -271,10 +316,102 @@ int y_build_conv(og_yolo* h, const std::string& mod, bool plain_conv2d, int kind
     return OG_OK;
 }
 
+// k_conv_mfma_fy: the occupancy-shaped grid of launch_conv_f (tile column, tile row, frame group x column tile x frame in group)
+template <int NT, int MODE, bool F32OUT = false>
+int launch_conv_fy(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {
+    constexpr int lds = conv_o_lds<NT, MODE, 8>();
+    static_assert(lds >= 4 * 5120, "the epilogue's per-wave scratch needs 20 KB");
+    ConvArgs a = a_in;
+    const int frames = a.n_spatial / (a.tiles_x * a.tiles_y);
+    a.zdiv = n_ntiles;
+    a.frames = frames;
+    a.zgroup_shift = 0;
+    if (c.xcd_group && a.zdiv > 1) {
+        int txy = a.tiles_x * a.tiles_y, g = 8;
+        while (g > 1 && txy % 2 == 0) { txy /= 2; g /= 2; }
+        while (g > frames) g /= 2;
+        while ((1 << a.zgroup_shift) < g) ++a.zgroup_shift;
+    }
+    const int G = 1 << a.zgroup_shift, groups = (frames + G - 1) / G;
+    a.zrcp = 1.0f / (float)(a.zdiv * G);
+    if ((long long)groups * G * a.zdiv > 65535) return fail(OG_EINVAL, "micro-batch too large for one launch (grid.z): lower the chunk size");
+    OG_LAUNCH((k_conv_mfma_fy<NT, MODE, 3, F32OUT>), dim3(a.tiles_x, a.tiles_y, groups * G * a.zdiv), dim3(256), lds, c.stream, a);
+    return OG_OK;
+}
+
+template <int NT, int MODE, bool F32OUT>
+int set_conv_fy_attr() {
+    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_fy<NT, MODE, 3, F32OUT>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<NT, MODE, 8>()));
+    return OG_OK;
+}
+
+// f16 mode ("precision" 2): every MFMA conv on k_conv_mfma_fy, the whole K range in ONE workgroup in ONE order at every B -- no
+// split-K, no virtual split, no workspace, never k_conv_mfma_p -- so a frame's bits cannot depend on the launch it rides in.
+int y_launch_f(og_yolo* h, const YConv& L, int B, const void* in_u8, const YView& in, const YView& out, const YView* res) {
+    if (L.kind == 3) {   // model.0: f32 weights, f32 fma chain, rounded output
+        if (!in_u8) return fail(OG_ESTATE, "f16 mode runs the stride-2 convs on the MFMA kernel: " + L.name);
+        const int Hout = out.H, Wout = out.W, total = B * Hout * ((Wout + 3) / 4);
+        // all eight channel quads of a 32-channel group, padded ones included (zero weights: they store 0).  The f32 path leaves the
+        // padded slots at whatever the arena holds (finite f32, times a zero weight); here stale bytes of another batch size's
+        // layout -- f32 logits -- can read as f16 NaN, and 0 x NaN would poison the next conv
+        const int cq_shift = 3;
+        const unsigned gx = (unsigned)(((long long)total * (1 << cq_shift) + 255) / 256);
+        hipLaunchKernelGGL(k_conv_direct_u8h, dim3(gx, L.Cout_p / 32), dim3(256), 0, h->stream, (const uint8_t*)in_u8, in.H, in.W, L.d_w,
+                           L.d_scale, L.d_shift, L.Cout_p, out.base, out.fs4(), out.ps4(), out.off4(), Hout, Wout, L.ks, L.stride, L.ks / 2,
+                           L.act, total, cq_shift, h->d_range);
+        HIPCHK(hipGetLastError());
+        return OG_OK;
+    }
+    if (!L.d_wf) return fail(OG_ESTATE, "no f16 weight image for " + L.name);
+    if (L.f32out != (out.es == 1) || in.es != 2) return fail(OG_ESTATE, "f16 mode: buffer format mismatch at " + L.name);
+    ConvArgs a{};
+    a.in = in.base;
+    a.in_frame_stride = in.fs4();
+    a.in_pix_stride = in.ps4();
+    a.in_ch_off = in.off4();
+    const int cpc = (L.Cin_p + 63) / 64;
+    a.n_chunks = (L.kind == 4) ? 4 * cpc : cpc;
+    a.k_half = (L.Cin_p % 64) ? 1 : 0;
+    if (L.kind == 4 && (in.H != 2 * out.H || in.W != 2 * out.W)) return fail(OG_EINVAL, "stride-2 conv needs even input sizes: " + L.name);
+    a.H = out.H;   // (kind 4: the kernel addresses the (2H x 2W) input through the space-to-depth view)
+    a.W = out.W;
+    a.tiles_x = (a.W + 15) / 16;
+    a.tiles_y = (a.H + 7) / 8;
+    a.n_spatial = B * a.tiles_x * a.tiles_y;
+    a.wpk = L.d_wf;
+    a.scale = L.d_scale;
+    a.shift = L.d_shift;
+    a.aff_mod = L.Cout_p;
+    a.out = out.base;
+    a.out_frame_stride = out.fs4();
+    a.out_pix_stride = out.ps4();
+    a.out_ch_off = out.off4();
+    a.zero_page = h->d_zero;
+    a.act = L.act;
+    a.res = res ? res->base : nullptr;
+    a.res_frame_stride = res ? res->fs4() : 0;
+    a.res_pix_stride = res ? res->ps4() : 0;
+    a.res_ch_off = res ? res->off4() : 0;
+    a.head_thr = 0.5f;
+    a.range_flag = h->d_range;
+    a.ksplit = 1;
+    a.vsplit = 1;
+    const LaunchCtx ctx{h->stream, h->n_cu, 2};
+    const int n_ntiles = L.Cout_p / (32 * L.NT);
+    if (L.f32out) {
+        if (L.kind != 2 || L.act != 0 || res) return fail(OG_ESTATE, "f32 logits come from the plain 1x1 Conv2d layers only: " + L.name);
+        return (L.NT == 2) ? launch_conv_fy<2, 2, true>(ctx, a, n_ntiles) : launch_conv_fy<1, 2, true>(ctx, a, n_ntiles);
+    }
+    if (L.kind == 4) return (L.NT == 2) ? launch_conv_fy<2, 3>(ctx, a, n_ntiles) : launch_conv_fy<1, 3>(ctx, a, n_ntiles);
+    if (L.kind == 0) return (L.NT == 2) ? launch_conv_fy<2, 0>(ctx, a, n_ntiles) : launch_conv_fy<1, 0>(ctx, a, n_ntiles);
+    return (L.NT == 2) ? launch_conv_fy<2, 2>(ctx, a, n_ntiles) : launch_conv_fy<1, 2>(ctx, a, n_ntiles);
+}
+
 int y_launch(og_yolo* h, const std::string& mod, int B, const void* in_u8, const YView& in, const YView& out, const YView* res) {
     auto it = h->convs.find(mod);
     if (it == h->convs.end()) return fail(OG_ESTATE, "conv not built: " + mod);
     const YConv& L = it->second;
+    if (h->precision == 2) return y_launch_f(h, L, B, in_u8, in, out, res);
     if (L.kind == 3) {
         const bool px1 = B <= h->latency_batch;   // one-frame calls: one output pixel per thread
         const int Hout = out.H, Wout = out.W, total = px1 ? B * Hout * Wout : B * Hout * ((Wout + 3) / 4);
@@ -438,15 +575,21 @@ struct YNet {
     float* best = nullptr;  // device
     int n_anchors = 0;
 
-    YView alloc(int segsC, int Hh, int Ww) {  // buffer of `segsC` physical channels
+    // INVARIANT (both modes, vital in f16): the arena is zeroed only when it is (re)allocated, and a buffer's place moves with B.
+    // So every byte a conv reads must have been written in THIS run: each producer stores all Cout_p padded channels of every
+    // segment (padded columns have zero weights, scale and shift: they store act(0) = 0), pools and up-sampling copy whole padded
+    // segments, model.0 in f16 mode stores its padded quads too.  A slot left to stale bytes is multiplied by a zero weight, which
+    // is harmless for finite f32 (the f32 model.0) but not for f16: stale f32 logits can read as NaN, and 0 x NaN = NaN in the MFMA.
+    YView alloc(int segsC, int Hh, int Ww, bool f32 = false) {  // buffer of `segsC` physical channels (f32: also in f16 mode)
         YView v;
+        v.es = (h->precision == 2 && !f32) ? 2 : 1;
         v.Ctot = segsC;
         v.off = 0;
         v.C = segsC;
         v.H = Hh;
         v.W = Ww;
         v.base = (float*)((char*)h->arena + bump);
-        bump += ((size_t)B * Hh * Ww * segsC * sizeof(float) + 255) / 256 * 256;
+        bump += ((size_t)B * Hh * Ww * segsC * (sizeof(float) / v.es) + 255) / 256 * 256;
         return v;
     }
     static YView seg(const YView& buf, int off, int C) {
@@ -466,10 +609,11 @@ struct YNet {
             YView o2 = out;
             o2.off = out_segs.front().off;
             rc = y_launch(h, mod, B, first ? in_u8 : nullptr, i2, o2, res);
+            if (mod.compare(0, 12, "model.22.hd.") != 0) h->acts[mod] = YAct{out, out_segs};   // every Conv's output by its module path
         }
     }
     void name(const std::string& n, const YView& v) {
-        if (mode == 2) h->acts[n] = v;
+        if (mode == 2) h->acts[n] = YAct{v, {{v.off, v.C}}};
     }
 
     // C2f (ultralytics nn/modules/block.py): cv1 1x1 -> split in two -> n Bottlenecks(3x3,3x3) chained on the
@@ -478,10 +622,10 @@ struct YNet {
         const std::string p = "model." + std::to_string(idx);
         const int c = c2 / 2, cp = cp32(c);
         YView cat = alloc((2 + n) * cp, in.H, in.W);
-        YView tmp = alloc(cp, in.H, in.W);
         conv(p + ".cv1", false, 2, 1, 2, in, in_segs, cat, {{0, c}, {cp, c}});
         for (int j = 0; j < n; ++j) {
             const std::string m = p + ".m." + std::to_string(j);
+            YView tmp = alloc(cp, in.H, in.W);   // one per bottleneck: every stored tensor stays readable (og_yolo_get_activation)
             YView src = seg(cat, (1 + j) * cp, c);
             conv(m + ".cv1", false, 0, 1, 2, cat, {{(1 + j) * cp, c}}, tmp, {{0, c}});
             conv(m + ".cv2", false, 0, 1, 2, tmp, {{0, c}}, cat, {{(2 + j) * cp, c}}, shortcut ? &src : nullptr);
@@ -494,10 +638,10 @@ struct YNet {
 
     void upsample(const YView& in, const YView& out, int out_off) {
         if (rc || mode != 2) return;
-        const int C4 = cp32(in.C) / 4;
+        const int C4 = cp32(in.C) / (4 * in.es);   // 16-byte pieces per pixel: 4 f32 or 8 f16 channels
         const long long total = (long long)B * out.H * out.W * C4;
-        hipLaunchKernelGGL(k_upsample2, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, in.base, in.frame_stride(),
-                           in.Ctot, in.off, out.base, out.frame_stride(), out.Ctot, out_off, C4, out.H, out.W, total);
+        hipLaunchKernelGGL(k_upsample2, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, in.base, in.fs4(),
+                           in.ps4(), in.off4(), out.base, out.fs4(), out.ps4(), out_off / out.es, C4, out.H, out.W, total);
         if (hipGetLastError() != hipSuccess) rc = fail(OG_EHIP, "k_upsample2 launch failed");
     }
 
@@ -546,7 +690,12 @@ struct YNet {
         const int cs = c7 / 2, csp = cp32(cs);
         YView sp = alloc(4 * csp, H5, W5);
         conv("model.9.cv1", false, 2, 1, 2, t8, {{0, c7}}, sp, {{0, cs}});
-        if (!rc && mode == 2 && B <= h->latency_batch && H5 * W5 <= 224) {   // one launch: the map's 32-channel slabs pooled in LDS
+        if (!rc && mode == 2 && h->precision == 2) {   // packed f16 max, 8 channels per thread; one-frame calls take it too
+            const long long total = (long long)B * H5 * W5 * (csp / 8);
+            for (int j = 0; j < 3; ++j)
+                hipLaunchKernelGGL(k_maxpool5_h, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, sp.base, sp.base,
+                                   sp.fs4(), sp.ps4(), j * csp / 2, (j + 1) * csp / 2, csp / 8, H5, W5, total);
+        } else if (!rc && mode == 2 && B <= h->latency_batch && H5 * W5 <= 224) {   // one launch: the map's 32-channel slabs pooled in LDS
             hipLaunchKernelGGL(k_sppf_pools, dim3(csp / 32, B), dim3(256), (size_t)H5 * W5 * 256, h->stream, sp.base, sp.frame_stride(), sp.Ctot, csp, H5, W5);
         } else if (!rc && mode == 2) {
             const long long total = (long long)B * H5 * W5 * (csp / 4);
@@ -555,16 +704,19 @@ struct YNet {
                                    sp.frame_stride(), sp.Ctot, j * csp, (j + 1) * csp, csp / 4, H5, W5, total);
         }
         if (!rc && mode == 2 && hipGetLastError() != hipSuccess) rc = fail(OG_EHIP, "SPPF pool launch failed");
+        for (int j = 1; j <= 3; ++j) name("model.9.m." + std::to_string(j), seg(sp, j * csp, cs));   // the three chained pools
         YView cat20 = alloc(cp32(c18) + cp32(c7), H5, W5);    // [19, 9]
         conv("model.9.cv2", false, 2, 1, 2, sp, {{0, cs}, {csp, cs}, {2 * csp, cs}, {3 * csp, cs}}, cat20, {{cp32(c18), c7}});
         YView t9 = seg(cat20, cp32(c18), c7);
         name("model.9", t9);
         // ---- neck ----
         upsample(t9, cat11, 0);
+        name("model.10", seg(cat11, 0, c7));
         YView cat17 = alloc(cp32(c15) + cp32(c12), H4, W4);   // [16, 12]
         c2f(12, h->n_c2f[4], false, cat11, {{0, c7}, {cp32(c7), c5}}, c12, cat17, cp32(c15));
         YView t12 = seg(cat17, cp32(c15), c12);
         upsample(t12, cat14, 0);
+        name("model.13", seg(cat14, 0, c12));
         // ---- Detect (model.22): per level a box branch (-> 4*reg_max DFL logits) and a class branch, three convs each;
         //      one-frame calls run the two branches as one chain of three (y_synth_head)
         const bool fused = h->head_fused;   // every B: the stacked chain has other K-part boundaries than the two branch chains (canonical form)
@@ -586,10 +738,18 @@ struct YNet {
             if (h->head_synth && (mode == 0 || (fused && mode == 2))) {   // BUILD packs both forms
                 const std::string ph = "model.22.hd." + std::to_string(l);
                 const int cbp = cp32(cb), nbp = cp32(nb);
-                YView h1 = alloc(cbp + cp32(cc), x.H, x.W), h2 = alloc(cbp + cp32(cc), x.H, x.W), ho = alloc(nbp + cp32(ncls), x.H, x.W);
+                YView h1 = alloc(cbp + cp32(cc), x.H, x.W), h2 = alloc(cbp + cp32(cc), x.H, x.W), ho = alloc(nbp + cp32(ncls), x.H, x.W, true);
                 conv(ph + ".0", false, 0, 1, 2, x, {{0, cx}}, h1, {{0, cb}, {cbp, cc}});
                 conv(ph + ".1", false, 0, 1, 2, h1, {{0, cb}, {cbp, cc}}, h2, {{0, cb}, {cbp, cc}});
                 conv(ph + ".2", true, 2, 1, 0, h2, {{0, cb}, {cbp, cc}}, ho, {{0, nb}, {nbp, ncls}});
+                if (mode == 2) {   // the stacked chain's two channel segments, by their branch paths
+                    name(pb + ".0", seg(h1, 0, cb));
+                    name(pc + ".0", seg(h1, cbp, cc));
+                    name(pb + ".1", seg(h2, 0, cb));
+                    name(pc + ".1", seg(h2, cbp, cc));
+                    name(pb + ".2", seg(ho, 0, nb));
+                    name(pc + ".2", seg(ho, nbp, ncls));
+                }
                 name("box" + std::to_string(l), seg(ho, 0, nb));
                 name("cls" + std::to_string(l), seg(ho, nbp, ncls));
                 da.lv[l].box = ho.base;
@@ -598,8 +758,8 @@ struct YNet {
                 da.lv[l].box_pix_stride = da.lv[l].cls_pix_stride = ho.Ctot;
                 if (mode == 2) return;
             }
-            YView b1 = alloc(cp32(cb), x.H, x.W), b2 = alloc(cp32(cb), x.H, x.W), bo = alloc(cp32(nb), x.H, x.W);
-            YView k1 = alloc(cp32(cc), x.H, x.W), k2 = alloc(cp32(cc), x.H, x.W), ko = alloc(cp32(ncls), x.H, x.W);
+            YView b1 = alloc(cp32(cb), x.H, x.W), b2 = alloc(cp32(cb), x.H, x.W), bo = alloc(cp32(nb), x.H, x.W, true);
+            YView k1 = alloc(cp32(cc), x.H, x.W), k2 = alloc(cp32(cc), x.H, x.W), ko = alloc(cp32(ncls), x.H, x.W, true);
             conv(pb + ".0", false, 0, 1, 2, x, {{0, cx}}, b1, {{0, cb}});
             conv(pb + ".1", false, 0, 1, 2, b1, {{0, cb}}, b2, {{0, cb}});
             conv(pb + ".2", true, 2, 1, 0, b2, {{0, cb}}, bo, {{0, nb}});
@@ -653,6 +813,7 @@ int y_ensure_arena(og_yolo* h, int B, int H, int W) {
         HIPCHK(hipStreamSynchronize(h->stream));
         HIPCHK(hipFree(h->arena));
         h->arena = nullptr;
+        h->acts.clear();
     }
     YNet plan{h, B, H, W, 1, nullptr};
     plan.run();
@@ -670,6 +831,16 @@ int y_check(og_yolo* h, int B, int H, int W) {
     if (!h->finalized) return fail(OG_ESTATE, "og_yolo_finalize() has not been called");
     if (B < 0 || H <= 0 || W <= 0 || H % 32 || W % 32)
         return fail(OG_EINVAL, "H and W must be positive multiples of 32 (letterbox on the host first)");
+    return OG_OK;
+}
+
+// f16 mode: did any activation leave the f16 range since the last check?  Call after the work has completed.
+int y_check_range(og_yolo* h) {
+    if (h->h_range && *(volatile int*)h->h_range) {
+        *(volatile int*)h->h_range = 0;
+        return fail(OG_ERANGE, "detector f16 mode: an activation exceeded the f16 range (|v| > 60000); the result of this call is not "
+                               "valid.  Use \"precision\" 0 for these weights");
+    }
     return OG_OK;
 }
 
@@ -703,7 +874,7 @@ void og_yolo_destroy(og_yolo* h) {
     if (!h) return;
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (auto& kv : h->convs)
-        for (float* p : {kv.second.d_w, kv.second.d_w1, kv.second.d_scale, kv.second.d_shift})
+        for (float* p : {kv.second.d_w, kv.second.d_w1, kv.second.d_wf, kv.second.d_scale, kv.second.d_shift})
             if (p) (void)hipFree(p);
     if (h->arena) (void)hipFree(h->arena);
     if (h->stage) (void)hipFree(h->stage);
@@ -713,6 +884,7 @@ void og_yolo_destroy(og_yolo* h) {
     if (h->d_cand) (void)hipFree(h->d_cand);
     if (h->d_dec_counter) (void)hipFree(h->d_dec_counter);
     if (h->pin) (void)hipHostFree(h->pin);
+    if (h->h_range) (void)hipHostFree(h->h_range);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -754,6 +926,10 @@ int og_yolo_finalize(og_yolo* h) {
     }
     int rc;
     if ((rc = init_kernel_attrs())) return rc;
+    if ((rc = set_conv_fy_attr<1, 0, false>()) || (rc = set_conv_fy_attr<2, 0, false>()) || (rc = set_conv_fy_attr<1, 2, false>()) ||
+        (rc = set_conv_fy_attr<2, 2, false>()) || (rc = set_conv_fy_attr<1, 2, true>()) || (rc = set_conv_fy_attr<2, 2, true>()) ||
+        (rc = set_conv_fy_attr<1, 3, false>()) || (rc = set_conv_fy_attr<2, 3, false>()))
+        return rc;
     {
         int dev = 0;
         hipDeviceProp_t prop;
@@ -771,6 +947,9 @@ int og_yolo_finalize(og_yolo* h) {
     HIPCHK(hipMalloc((void**)&h->d_cand, (size_t)64 * og_yolo::kDecBlocks * 8 * sizeof(float)));
     HIPCHK(hipMalloc((void**)&h->d_dec_counter, 64 * sizeof(int)));
     HIPCHK(hipMemset(h->d_dec_counter, 0, 64 * sizeof(int)));
+    HIPCHK(hipHostMalloc((void**)&h->h_range, sizeof(int), hipHostMallocMapped));
+    *h->h_range = 0;
+    HIPCHK(hipHostGetDevicePointer((void**)&h->d_range, h->h_range, 0));
     h->head_synth = y_synth_head(h);
     for (auto& kv : h->host)
         if (!kv.second.shape.empty()) h->couts[kv.first] = (int)kv.second.shape[0];
@@ -794,8 +973,15 @@ int og_yolo_set_option(og_yolo* h, const char* name, int value) {
     else if (n == "splitk_min_steps" && (value == 1 || value == 3 || value == 9)) slot = &h->splitk_min_steps;
     else if (n == "splitk_slots" && value >= 1 && value <= 4) slot = &h->splitk_slots;
     else if (n == "splitk_div" && value >= 1 && value <= 8) slot = &h->splitk_div;
+    else if (n == "precision" && (value == 0 || value == 2)) slot = &h->precision;   // (no split precision, 1, for the detector)
     if (!slot) return fail(OG_EINVAL, "unknown detector option or value out of range: " + n);
     if (h->stream) HIPCHK(hipStreamSynchronize(h->stream));
+    if (slot == &h->precision && value != h->precision && h->arena) {   // other buffer sizes: the next call plans the arena anew
+        HIPCHK(hipFree(h->arena));
+        h->arena = nullptr;
+        h->capB = 0;
+        h->acts.clear();
+    }
     *slot = value;
     return OG_OK;
 }
@@ -882,7 +1068,7 @@ int og_yolo_detect_u8_end(og_yolo* h, float* best) {
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     memcpy(best, (char*)h->pin + h->pend_off, (size_t)B * 5 * 4);
-    return OG_OK;
+    return y_check_range(h);
 }
 
 int og_yolo_detect_u8(og_yolo* h, const uint8_t* bgr, int B, int H, int W, float conf, float* best, float* pred) {
@@ -921,7 +1107,7 @@ int og_yolo_detect_u8(og_yolo* h, const uint8_t* bgr, int B, int H, int W, float
             if (rc) return rc;
             HIPCHK(hipStreamSynchronize(h->stream));
             memcpy(best, ps + o_best, (size_t)B * 5 * 4);
-            return OG_OK;
+            return y_check_range(h);
         }
         HIPCHK(hipMemcpyAsync(s, ps, n_in, hipMemcpyHostToDevice, h->stream));
         rc = og_yolo_detect_u8_dev(h, (const uint8_t*)s, B, H, W, conf, (float*)(s + o_best), pred ? (float*)(s + o_pred) : nullptr);
@@ -930,7 +1116,7 @@ int og_yolo_detect_u8(og_yolo* h, const uint8_t* bgr, int B, int H, int W, float
         HIPCHK(hipStreamSynchronize(h->stream));
         memcpy(best, ps + o_best, (size_t)B * 5 * 4);
         if (pred) memcpy(pred, ps + o_pred, (size_t)B * A * 5 * 4);
-        return OG_OK;
+        return y_check_range(h);
     }
     const int chunk = 256;  // the detector's maps are tiny (8x8 at the deepest level): big micro-batches fill the chip (18k -> 35k fps)
     for (int b0 = 0; b0 < B; b0 += chunk) {
@@ -943,14 +1129,14 @@ int og_yolo_detect_u8(og_yolo* h, const uint8_t* bgr, int B, int H, int W, float
     HIPCHK(hipMemcpyAsync(best, s + o_best, (size_t)B * 5 * 4, hipMemcpyDeviceToHost, h->stream));
     if (pred) HIPCHK(hipMemcpyAsync(pred, s + o_pred, (size_t)B * A * 5 * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    return OG_OK;
+    return y_check_range(h);
 }
 
 int og_yolo_sync(og_yolo* h) {
     if (!h || !h->stream) return fail(OG_ESTATE, "handle not finalized");
     OG_SCOPE(h);
     HIPCHK(hipStreamSynchronize(h->stream));
-    return OG_OK;
+    return y_check_range(h);
 }
 
 int og_yolo_get_activation(og_yolo* h, const char* name, int B, float* out, size_t cap, int* dims) {
@@ -958,18 +1144,27 @@ int og_yolo_get_activation(og_yolo* h, const char* name, int B, float* out, size
     if (!name || !out || !dims || B < 1 || B > h->lastB) return fail(OG_EINVAL, "bad argument");
     auto it = h->acts.find(name);
     if (it == h->acts.end()) return fail(OG_EINVAL, std::string("unknown activation ") + name);
-    const YView& v = it->second;
-    dims[0] = v.C;
+    const YView& v = it->second.v;
+    int Cn = 0;
+    for (const auto& s_ : it->second.segs) Cn += s_.C;
+    dims[0] = Cn;
     dims[1] = v.H;
     dims[2] = v.W;
     const size_t HW = (size_t)v.H * v.W;
-    if (cap < (size_t)B * v.C * HW) return fail(OG_EINVAL, "capacity too small");
-    std::vector<float> tmp((size_t)B * v.frame_stride());
+    if (cap < (size_t)B * Cn * HW) return fail(OG_EINVAL, "capacity too small");
+    std::vector<float> tmp((size_t)B * v.fs4());
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(tmp.data(), v.base, tmp.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (int b = 0; b < B; ++b)
-        for (int c = 0; c < v.C; ++c)
-            for (size_t p = 0; p < HW; ++p) out[((size_t)b * v.C + c) * HW + p] = tmp[((size_t)b * HW + p) * v.Ctot + v.off + c];
+    const _Float16* t16 = (const _Float16*)tmp.data();   // f16 mode: widened here, f32 out in both modes
+    for (int b = 0; b < B; ++b) {
+        int c = 0;
+        for (const auto& s_ : it->second.segs)
+            for (int k = 0; k < s_.C; ++k, ++c)
+                for (size_t p = 0; p < HW; ++p) {
+                    const size_t i = ((size_t)b * HW + p) * v.Ctot + s_.off + k;
+                    out[((size_t)b * Cn + c) * HW + p] = (v.es == 2) ? (float)t16[i] : tmp[i];
+                }
+    }
     return OG_OK;
 }
 

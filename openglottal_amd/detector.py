@@ -16,13 +16,13 @@ import numpy as np
 
 class TemporalDetector:
     def __init__(self, model_path, conf: float = 0.25, max_shift_px: int = 30, padding: int = 8,
-                 max_hold_frames: int = 3) -> None:
+                 max_hold_frames: int = 3, precision: str = "f32") -> None:
         if callable(model_path):
             self.model = model_path
         else:
             from .yolo import load_detector_backend
 
-            self.model = load_detector_backend(str(model_path))
+            self.model = load_detector_backend(str(model_path), precision)   # precision: the native backend's arithmetic (yolo.py)
         self.conf = conf
         self.max_shift = max_shift_px
         self.padding = padding

@@ -22,6 +22,7 @@ from ._lib import OpenGlottalHipError, check, lib, ptr
 from .unet import _device_index
 
 STRIDE = 32
+PRECISIONS = {"f32": 0, "f16": 2}   # og_yolo_set_option(h, "precision", v); the detector has no split precision
 
 
 def letterbox_bgr(frame: np.ndarray, imgsz: int = 256, stride: int = STRIDE):
@@ -42,7 +43,17 @@ def letterbox_bgr(frame: np.ndarray, imgsz: int = 256, stride: int = STRIDE):
 
 
 class YoloV8Detector:
-    def __init__(self, weights, nc: int = 1, imgsz: int = 256, device="cuda:0") -> None:
+    """``precision="f16"`` (or ``set_option("precision", 2)``) selects the opt-in f16 mode: the weights of every MFMA conv rounded
+    to f16 once, every stored activation rounded to f16 once, f32 accumulation in one fixed K order, f32 logits into the unchanged
+    decode.  Measured on one MI355X (``profiles/yolo_f16_bench.json``): batched calls of 256 frames run
+    at 117.6 k frames/s against 51.4 k in f32 (2.28 x).  A ONE-FRAME call (``__call__`` / ``submit``) gains nothing to speak of: f16 mode
+    never splits K, where the f32 latency path does, and the call is bound by its ~58 launches either way -- median 557-560 us in
+    f16 against 571-586 us in f32, about equal, f16 marginally faster.  Boxes and confidences move by the f16 rounding of the activations; per-frame and
+    batched calls still return identical bits.  An activation beyond the f16 range fails the call with ``OG_ERANGE``."""
+
+    def __init__(self, weights, nc: int = 1, imgsz: int = 256, device="cuda:0", precision: str = "f32") -> None:
+        if precision not in PRECISIONS:
+            raise OpenGlottalHipError(f"precision must be one of {sorted(PRECISIONS)}, not {precision!r}")
         if isinstance(weights, (str, os.PathLike)):
             p = str(weights)
             if p.endswith(".pt"):
@@ -69,6 +80,8 @@ class YoloV8Detector:
                 v = np.ascontiguousarray(v, dtype=np.float32)
                 shp = (C.c_int64 * max(1, v.ndim))(*v.shape)
                 check(lib().og_yolo_set_tensor(h, k.encode(), ptr(v), shp, v.ndim, _lib.OG_DTYPE_F32), f"set_tensor({k})")
+            if precision != "f32":   # (f32 is the handle's default)
+                check(lib().og_yolo_set_option(h, b"precision", PRECISIONS[precision]), "og_yolo_set_option(precision)")
             check(lib().og_yolo_finalize(h), "og_yolo_finalize")
         except Exception:
             lib().og_yolo_destroy(h)
@@ -76,7 +89,7 @@ class YoloV8Detector:
         self._h = h
 
     def set_option(self, name: str, value: int) -> None:
-        """Tuning knobs of the C-ABI (``og_yolo_set_option``): ``latency_batch``, ``splitk_slots``, ``splitk_div``."""
+        """Options of the C-ABI (``og_yolo_set_option``): ``precision`` (0 f32 | 2 f16), ``latency_batch``, ``splitk_slots``, ``splitk_div``."""
         check(lib().og_yolo_set_option(self._h, name.encode(), int(value)), f"og_yolo_set_option({name})")
 
     def detect_batch(self, frames_bgr: np.ndarray, conf: float = 0.25, want_pred: bool = False):
@@ -168,9 +181,9 @@ class YoloV8Detector:
         b[[1, 3]] = b[[1, 3]].clip(0, H0)
         return b[None, :4].astype(np.float32), b[4:5].astype(np.float32)
 
-    def activation(self, name: str, B: int = 1) -> np.ndarray:
+    def activation(self, name: str, B: int = 1, cap: int = 1 << 22) -> np.ndarray:
+        """The first ``B`` frames of a named tensor of the last call, f32 ``[B,C,H,W]``; ``cap``: room for it, in floats."""
         dims = (C.c_int * 3)()
-        cap = 1 << 22
         buf = np.empty(cap, np.float32)
         check(lib().og_yolo_get_activation(self._h, name.encode(), B, ptr(buf), cap, dims), f"og_yolo_get_activation({name})")
         c, h, w = dims[0], dims[1], dims[2]
@@ -201,5 +214,5 @@ def nms(xyxy: np.ndarray, conf: np.ndarray, conf_thres: float = 0.25, iou_thres:
     return np.array(keep, dtype=np.int64)
 
 
-def load_detector_backend(path: str):
-    return YoloV8Detector(path)
+def load_detector_backend(path: str, precision: str = "f32"):
+    return YoloV8Detector(path, precision=precision)

@@ -304,7 +304,12 @@ int og_yolo_finalize(og_yolo* h);
  * class logits of Detect's last layers kept in f32 for the unchanged decode.  1 and >= 3 return OG_EINVAL (no split precision for the
  * detector).  Settable before and after og_yolo_finalize; a switch re-plans the arena on the next call.  An activation beyond
  * |v| > 60000 makes the call (or the og_yolo_sync / og_yolo_detect_u8_end that waits for it) return OG_ERANGE; the handle stays usable.
- * og_yolo_get_activation returns f32 in both modes. */
+ * og_yolo_get_activation returns f32 in both modes.
+ * "source_stage_kib" [65536]: the resized entries (below) stage at most this many KiB of SOURCE frames per upload (64 MiB, as the
+ * U-Net's resized path); never lower than one frame -- a larger frame is staged alone; 0 and negative values: OG_EINVAL.  Results are
+ * per frame: the setting changes no bit.  "source_mapped" [1]: one-frame resized calls -- k_letterbox_bgr reads the source frame from
+ * the handle's mapped pinned buffer (1, the measured choice: one copy command less on the stream) or after an
+ * asynchronous copy to the device (0). */
 int og_yolo_set_option(og_yolo* h, const char* name, int value);
 int og_yolo_num_anchors(og_yolo* h, int H, int W);    /* (H/8)(W/8)+(H/16)(W/16)+(H/32)(W/32) */
 /* frames [B,H,W,3] u8 BGR at network resolution (H,W multiples of 32; the caller letterboxes).
@@ -321,6 +326,45 @@ int og_yolo_detect_u8_dev(og_yolo* h, const uint8_t* bgr_dev, int B, int H, int 
 int og_yolo_detect_u8_begin(og_yolo* h, const uint8_t* bgr, int B, int H, int W, float conf_thres);
 int og_yolo_detect_u8_end(og_yolo* h, float* best);
 int og_yolo_sync(og_yolo* h);
+
+/* Frames of ANY size: the letterbox of the ultralytics predictor (LetterBox(auto=True, stride=32): long side to `imgsz` with u8
+ * INTER_LINEAR, 114-padding to multiples of 32) and its `scale_boxes` on the device, around the unchanged network -- the host
+ * composition of openglottal_amd/yolo.py (`letterbox_bgr` per frame, np.stack, the network, the f32 scale-back) bit for bit.  The
+ * arithmetic is that of the U-Net's resized path (geometry.resize_linear: half-pixel centres, edge clamp, 11-bit coefficients);
+ * parity against a real cv2 / ultralytics unpinned, and an exact 2x downscale is NOT switched to INTER_AREA as OpenCV does.
+ *
+ * The scalars of `letterbox_bgr` for a frame of H x W (host only, no handle): r = min(imgsz/H, imgsz/W) in double (`gain`), content
+ * size new = rint(side * r) (half to even, Python's round), d = (imgsz - new) % 32, pads rint(d/2 -/+ 0.1) (the odd pixel goes to the
+ * bottom / right), network size net = new + both pads.  OG_EINVAL: a side < 1 or > 8192, imgsz not a positive multiple of 32 (or
+ * > 8192), a content side that rounds to 0 (1 x 700). */
+int og_yolo_letterbox_geometry(int H, int W, int imgsz, int* net_h, int* net_w, int* new_h, int* new_w, int* pad_top, int* pad_left,
+                               double* gain);
+/* One frame src [H,W,channels] u8 (channels 1 = gray, replicated to three; 3 = BGR) -> out [net_h,net_w,3] on the HOST, by the very
+ * inline function the device kernel calls: the arithmetic can be checked without a GPU (tests/test_yolo_letterbox_host.py), as
+ * og_linear_taps_host and og_bgr2gray_host do for theirs. */
+int og_yolo_letterbox_host(const uint8_t* src, int H, int W, int channels, int imgsz, uint8_t* out);
+/* src_dev [B,H,W,channels] u8 -> out_dev [B,net_h,net_w,3] u8, both resident; asynchronous on the handle's stream (og_yolo_sync).
+ * A building block and the parity tap of k_letterbox_bgr. */
+int og_yolo_letterbox_u8_dev(og_yolo* h, const uint8_t* src_dev, int B, int H, int W, int channels, int imgsz, uint8_t* out_dev);
+/* og_yolo_detect_u8 for frames [B,H,W,channels] u8 of any size in HOST memory (pageable or pinned); synchronous.
+ *   best [B,5] f32 in SOURCE pixels: (v - pad) / (float)gain, clipped to [0,W] x [0,H]; conf = -1 and zero coordinates when there is
+ *   no detection.  No `pred`: candidates in network coordinates stay available through og_yolo_detect_u8.
+ * Source frames go up in chunks of "source_stage_kib", each chunk is letterboxed into the network-size input batch, and the network
+ * runs at up to 256 frames per launch whatever the source size; device memory = that stage + the network's arena, independent of B.
+ * Calls of at most "latency_batch" frames take the one-frame kernels with one host wait.  "precision" 2 needs nothing else: model.0
+ * reads the same u8 buffer.  A failed call returns its code with nothing left in flight; the handle stays usable. */
+int og_yolo_detect_resized_u8(og_yolo* h, const uint8_t* frames, int B, int H, int W, int channels, int imgsz, float conf_thres,
+                              float* best);
+/* The same for RESIDENT frames; asynchronous on the handle's stream (best_dev [B,5] is valid after og_yolo_sync); the boxes are
+ * scaled on the device (k_scale_boxes: the same inline function as on the host, the same bits). */
+int og_yolo_detect_resized_u8_dev(og_yolo* h, const uint8_t* src_dev, int B, int H, int W, int channels, int imgsz, float conf_thres,
+                                  float* best_dev);
+/* First half of og_yolo_detect_resized_u8; pairs with og_yolo_detect_u8_end, which delivers SOURCE-pixel boxes for such a call.  The
+ * same rule as og_yolo_detect_u8_begin: one call in flight per handle, anything else in between is OG_EINVAL. */
+int og_yolo_detect_resized_u8_begin(og_yolo* h, const uint8_t* frames, int B, int H, int W, int channels, int imgsz, float conf_thres);
+/* Launches issued so far by this handle of "k_letterbox_bgr" or "k_scale_boxes" (any other name: OG_EINVAL).  For tests: a frame for
+ * which the letterbox is the identity must take the plain entries and launch neither. */
+long long og_yolo_launch_count(og_yolo* h, const char* kernel);
 /* Parity/debug: "model.0" ... "model.21" (module outputs), "box0..2", "cls0..2" (Detect branches), NCHW f32. */
 int og_yolo_get_activation(og_yolo* h, const char* name, int B, float* out_nchw, size_t capacity_floats, int* dims);
 

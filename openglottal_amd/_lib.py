@@ -97,6 +97,14 @@ PROTOTYPES = {
     "og_yolo_detect_u8_end": (C.c_int, [C.c_void_p, C.c_void_p]),
     "og_yolo_detect_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "og_yolo_sync": (C.c_int, [C.c_void_p]),
+    "og_yolo_letterbox_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 6 + [C.POINTER(C.c_double)]),
+    "og_yolo_letterbox_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "og_yolo_letterbox_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "og_yolo_detect_resized_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "og_yolo_detect_resized_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                                C.c_void_p]),
+    "og_yolo_detect_resized_u8_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
+    "og_yolo_launch_count": (C.c_longlong, [C.c_void_p, C.c_char_p]),
     "og_yolo_get_activation": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
 }
 

@@ -4734,3 +4734,87 @@ __global__ __launch_bounds__(256) void k_resize_out(const float* __restrict__ lo
         if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&area[b], cnt);
     }
 }
+
+// =======================================================================================
+// Frames of any size in front of the detector (the ultralytics predictor's LetterBox(auto=True, stride=32) as restated by
+// openglottal_amd/yolo.py `letterbox_bgr`: resize so that the long side is imgsz, pad with 114 to a multiple of 32; then
+// `scale_boxes` back).  Parity against a real cv2 / ultralytics unpinned, as for every other geometry here (and for an exact 2x
+// downscale OpenCV itself switches to INTER_AREA where geometry.resize_linear does not).
+//   * og_letterbox_px<C>: the three bytes of ONE network pixel (y, x) from one source frame [H,W,C], C in {1, 3}.  Outside the
+//     content rectangle [top, top+new_h) x [left, left+new_w): 114.  Inside: k_resize_in's rule per channel -- og_linear_pos,
+//     og_linear_coef, (((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2, clamp.  C = 1 writes the one value to all three channels
+//     (the host's np.repeat: a gray video goes up at one byte per pixel).  Where new_h x new_w == H x W the fractions are 0 and the
+//     rule is a copy: (((2048 * ((s * 2048) >> 4)) >> 16) + 0 + 2) >> 2 = (4s + 2) >> 2 = s for every s in 0..255.
+//     The same function runs on the host (og_yolo_letterbox_host: the CPU test holds it to letterbox_bgr byte for byte).
+//   * k_letterbox_bgr<C>: u8 [B,H,W,C] -> u8 [B,Hn,Wn,3], the buffer model.0's kernel reads.  One thread per network pixel,
+//     three byte stores (the simple form; its share of the detector's kernel time is in DESIGN section 12).
+//   * og_scale_box: one `best` row from network pixels back to source pixels, the f32 expression of
+//     YoloV8Detector.detect_frames_host: (v - pad) / gain when (gain, pads) != (1, 0, 0), clip to the frame, zero coordinates
+//     where there is no detection.  Contraction OFF; IEEE f32 subtract and divide on both sides.
+// =======================================================================================
+template <int C>
+__host__ __device__ inline void og_letterbox_px(const uint8_t* __restrict__ s, int H, int W, int new_h, int new_w, int top, int left,
+                                                int y, int x, uint8_t* o3) {
+    const int cy = y - top, cx = x - left;
+    if (cy < 0 || cy >= new_h || cx < 0 || cx >= new_w) {
+        o3[0] = o3[1] = o3[2] = 114;
+        return;
+    }
+    int x0, x1, y0, y1;
+    float fx, fy;
+    og_linear_pos(cx, W, new_w, x0, x1, fx);
+    og_linear_pos(cy, H, new_h, y0, y1, fy);
+    const int ax1 = og_linear_coef(fx), ax0 = 2048 - ax1, ay1 = og_linear_coef(fy), ay0 = 2048 - ay1;
+    const long long i00 = ((long long)y0 * W + x0) * C, i01 = ((long long)y0 * W + x1) * C, i10 = ((long long)y1 * W + x0) * C,
+                    i11 = ((long long)y1 * W + x1) * C;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const int r0 = s[i00 + c] * ax0 + s[i01 + c] * ax1;
+        const int r1 = s[i10 + c] * ax0 + s[i11 + c] * ax1;
+        const int v = (((ay0 * (r0 >> 4)) >> 16) + ((ay1 * (r1 >> 4)) >> 16) + 2) >> 2;
+        o3[c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+    }
+    if (C == 1) o3[1] = o3[2] = o3[0];
+}
+
+// grid (ceil(Hn*Wn / 256), B): one thread per network pixel
+template <int C>
+__global__ __launch_bounds__(256) void k_letterbox_bgr(const uint8_t* __restrict__ src, int H, int W, int Hn, int Wn, int new_h, int new_w,
+                                                       int top, int left, uint8_t* __restrict__ out) {
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= Hn * Wn) return;
+    const int y = t / Wn, x = t - y * Wn;
+    uint8_t px[3];
+    og_letterbox_px<C>(src + (long long)b * H * W * C, H, W, new_h, new_w, top, left, y, x, px);
+    uint8_t* o = out + ((long long)b * Hn * Wn + t) * 3;
+    o[0] = px[0];
+    o[1] = px[1];
+    o[2] = px[2];
+}
+
+// `row`: x1, y1, x2, y2, conf.  `scale`: (gain, pad_left, pad_top) != (1.0, 0, 0), decided once per call on the host from the double gain.
+__host__ __device__ inline void og_scale_box(float* row, bool scale, float gain, int pad_left, int pad_top, int H, int W) {
+#pragma clang fp contract(off)
+    const float fw = (float)W, fh = (float)H;
+    const bool none = !(row[4] >= 0.0f);   // conf < 0 (the host's `~(conf >= 0)`: a NaN confidence is no detection either)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float v = row[k];
+        const float lim = (k & 1) ? fh : fw;
+        if (scale) v = (v - (float)((k & 1) ? pad_top : pad_left)) / gain;
+        v = (v < 0.0f) ? 0.0f : ((v > lim) ? lim : v);   // np.clip(v, 0, lim): a NaN stays a NaN
+        row[k] = none ? 0.0f : v;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_scale_boxes(float* __restrict__ best, int B, int scale, float gain, int pad_left, int pad_top, int H, int W) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    float row[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) row[k] = best[(long long)b * 5 + k];
+    og_scale_box(row, scale != 0, gain, pad_left, pad_top, H, W);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) best[(long long)b * 5 + k] = row[k];
+}

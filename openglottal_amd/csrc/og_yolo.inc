@@ -93,6 +93,14 @@ struct og_yolo {
     size_t pend_off = 0;         // ... offset of its `best` rows in the pinned buffer
     bool pend_sync = false;      // ... the call ran synchronously; its results wait in pend_best
     std::vector<float> pend_best;
+    // frames of any size (og_yolo_detect_resized_u8*): source frames staged in chunks, letterboxed on the device (k_letterbox_bgr)
+    int source_stage_kib = 65536;   // most KiB of source frames staged per upload (64 MiB, as the U-Net's kResizeSlotBytes); a larger frame is staged alone
+    int source_mapped = 1;          // latency path: k_letterbox_bgr reads the source frame from the mapped pinned buffer (1, measured 12-15 us faster per call) or after an async copy (0)
+    long long n_letterbox = 0, n_scale_boxes = 0;   // launches so far (og_yolo_launch_count)
+    bool pend_resized = false;      // the call in flight came through og_yolo_detect_resized_u8_begin: end maps its boxes to source pixels
+    int pend_H = 0, pend_W = 0, pend_left = 0, pend_top = 0;
+    float pend_gain = 1.f;
+    bool pend_scale = false;
 };
 
 inline bool og_skip_device(const og_yolo* h) { return !h || !h->finalized; }
@@ -974,6 +982,8 @@ int og_yolo_set_option(og_yolo* h, const char* name, int value) {
     else if (n == "splitk_slots" && value >= 1 && value <= 4) slot = &h->splitk_slots;
     else if (n == "splitk_div" && value >= 1 && value <= 8) slot = &h->splitk_div;
     else if (n == "precision" && (value == 0 || value == 2)) slot = &h->precision;   // (no split precision, 1, for the detector)
+    else if (n == "source_stage_kib" && value >= 1 && value <= (1 << 24)) slot = &h->source_stage_kib;
+    else if (n == "source_mapped" && (value == 0 || value == 1)) slot = &h->source_mapped;
     if (!slot) return fail(OG_EINVAL, "unknown detector option or value out of range: " + n);
     if (h->stream) HIPCHK(hipStreamSynchronize(h->stream));
     if (slot == &h->precision && value != h->precision && h->arena) {   // other buffer sizes: the next call plans the arena anew
@@ -1026,6 +1036,7 @@ int og_yolo_detect_u8_begin(og_yolo* h, const uint8_t* bgr, int B, int H, int W,
     if (h->pend_B) return fail(OG_EINVAL, "og_yolo_detect_u8_begin: a call is already in flight on this handle");
     if (B == 0) return OG_OK;
     if (!bgr) return fail(OG_EINVAL, "null buffer");
+    h->pend_resized = false;
     const size_t n_in = (size_t)B * H * W * 3, o_best = al256(n_in), tot = o_best + al256((size_t)B * 5 * 4);
     if (B <= h->latency_batch && h->zero_copy) {
         if (tot > h->pin_bytes) {
@@ -1068,6 +1079,8 @@ int og_yolo_detect_u8_end(og_yolo* h, float* best) {
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     memcpy(best, (char*)h->pin + h->pend_off, (size_t)B * 5 * 4);
+    if (h->pend_resized)   // og_yolo_detect_resized_u8_begin: network pixels -> source pixels
+        for (int b = 0; b < B; ++b) og_scale_box(best + (size_t)b * 5, h->pend_scale, h->pend_gain, h->pend_left, h->pend_top, h->pend_H, h->pend_W);
     return y_check_range(h);
 }
 
@@ -1131,6 +1144,260 @@ int og_yolo_detect_u8(og_yolo* h, const uint8_t* bgr, int B, int H, int W, float
     HIPCHK(hipStreamSynchronize(h->stream));
     return y_check_range(h);
 }
+
+}  // extern "C"
+
+// ---- frames of any size: letterbox on the device (DESIGN section 12) ----
+namespace {
+
+struct YGeo {
+    int net_h = 0, net_w = 0, new_h = 0, new_w = 0, top = 0, left = 0;
+    double gain = 1.0;
+    bool scale() const { return !(gain == 1.0 && left == 0 && top == 0); }   // detect_frames_host's `(gain, px, py) != (1.0, 0, 0)`
+};
+
+// argument checks of every resized entry, before the handle's state is looked at (so they can be tested without a device)
+int y_check_resized(og_yolo* h, int B, int H, int W, int channels, int imgsz, YGeo& g) {
+    if (!h) return fail(OG_EINVAL, "null handle");
+    if (B < 0) return fail(OG_EINVAL, "negative batch size");
+    if (channels != 1 && channels != 3) return fail(OG_EINVAL, "channels must be 1 (gray) or 3 (BGR)");
+    int rc = og_yolo_letterbox_geometry(H, W, imgsz, &g.net_h, &g.net_w, &g.new_h, &g.new_w, &g.top, &g.left, &g.gain);
+    if (rc) return rc;
+    if (!h->finalized) return fail(OG_ESTATE, "og_yolo_finalize() has not been called");
+    return OG_OK;
+}
+
+// nb <= 32768 frames src [nb,H,W,C] -> out [nb,net_h,net_w,3], on the handle's stream
+int y_letterbox(og_yolo* h, const uint8_t* src, int nb, int H, int W, int channels, const YGeo& g, uint8_t* out) {
+    const dim3 grid((unsigned)((g.net_h * g.net_w + 255) / 256), (unsigned)nb);
+    if (channels == 3)
+        OG_LAUNCH(k_letterbox_bgr<3>, grid, dim3(256), 0, h->stream, src, H, W, g.net_h, g.net_w, g.new_h, g.new_w, g.top, g.left, out);
+    else
+        OG_LAUNCH(k_letterbox_bgr<1>, grid, dim3(256), 0, h->stream, src, H, W, g.net_h, g.net_w, g.new_h, g.new_w, g.top, g.left, out);
+    ++h->n_letterbox;
+    return OG_OK;
+}
+
+int y_pin(og_yolo* h, size_t bytes) {
+    if (bytes <= h->pin_bytes) return OG_OK;
+    if (h->pin) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(hipHostFree(h->pin));
+        h->pin = nullptr;
+        h->pin_bytes = 0;
+    }
+    HIPCHK(hipHostMalloc(&h->pin, bytes, hipHostMallocDefault));
+    h->pin_bytes = bytes;
+    return OG_OK;
+}
+
+// an error inside a resized call: nothing of it stays in flight when the code is returned (the message survives the wait)
+int y_fail_sync(og_yolo* h, int rc) {
+    const std::string err = g_err;
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    g_err = err;
+    return rc;
+}
+
+constexpr int kNetLaunch = 256;   // network frames per launch of a resized call, whatever the source size (og_yolo_detect_u8's chunk)
+constexpr int kBestRows = 65536;  // `best` rows kept on the device before they go back to the host (a multiple of kNetLaunch; 1.25 MiB)
+
+// One-frame calls (B <= latency_batch) of the resized entries: the source frames go through the pinned buffer, k_letterbox_bgr
+// writes the network input on the device, the unchanged latency chain follows, and the host waits once (by the caller: `wait`
+// false = og_yolo_detect_resized_u8_begin).  Returns the offset of the `best` rows in the pinned buffer.
+int y_resized_latency(og_yolo* h, const uint8_t* frames, int B, int H, int W, int channels, const YGeo& g, float conf, size_t* o_best_pin) {
+    const size_t n_src = (size_t)B * H * W * channels, n_net = (size_t)B * g.net_h * g.net_w * 3;
+    const size_t p_best = al256(n_src), p_tot = p_best + al256((size_t)B * 5 * 4);
+    const size_t o_net = al256(n_src), o_best = o_net + al256(n_net), tot = o_best + al256((size_t)B * 5 * 4);
+    int rc;
+    if ((rc = y_pin(h, p_tot)) || (rc = y_stage(h, tot))) return rc;
+    char *ps = (char*)h->pin, *s = (char*)h->stage, *zp = nullptr;
+    memcpy(ps, frames, n_src);
+    HIPCHK(hipHostGetDevicePointer((void**)&zp, ps, 0));
+    const uint8_t* src = (const uint8_t*)zp;
+    if (!h->source_mapped) {
+        HIPCHK(hipMemcpyAsync(s, ps, n_src, hipMemcpyHostToDevice, h->stream));
+        src = (const uint8_t*)s;
+    }
+    if ((rc = y_letterbox(h, src, B, H, W, channels, g, (uint8_t*)(s + o_net)))) return rc;
+    float* best_dev = h->zero_copy ? (float*)(zp + p_best) : (float*)(s + o_best);
+    if ((rc = og_yolo_detect_u8_dev(h, (const uint8_t*)(s + o_net), B, g.net_h, g.net_w, conf, best_dev, nullptr))) return rc;
+    if (!h->zero_copy) HIPCHK(hipMemcpyAsync(ps + p_best, s + o_best, (size_t)B * 5 * 4, hipMemcpyDeviceToHost, h->stream));
+    *o_best_pin = p_best;
+    return OG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int og_yolo_letterbox_geometry(int H, int W, int imgsz, int* net_h, int* net_w, int* new_h, int* new_w, int* pad_top, int* pad_left,
+                               double* gain) {
+#pragma clang fp contract(off)
+    if (!net_h || !net_w || !new_h || !new_w || !pad_top || !pad_left || !gain) return fail(OG_EINVAL, "null argument");
+    if (H < 1 || W < 1 || H > 8192 || W > 8192) return fail(OG_EINVAL, "frame sides must be in 1..8192");
+    if (imgsz < 32 || imgsz > 8192 || imgsz % 32) return fail(OG_EINVAL, "imgsz must be a positive multiple of 32 (at most 8192)");
+    const double rh = (double)imgsz / (double)H, rw = (double)imgsz / (double)W, r = rh < rw ? rh : rw;
+    const int nw = (int)std::rint((double)W * r), nh = (int)std::rint((double)H * r);   // Python's round(): half to even
+    if (nw < 1 || nh < 1) return fail(OG_EINVAL, "the letterboxed frame would have a side of 0 pixels");
+    const int dw = (imgsz - nw) % 32, dh = (imgsz - nh) % 32;   // (nw, nh <= imgsz: non-negative)
+    const int top = (int)std::rint((double)dh / 2 - 0.1), bottom = (int)std::rint((double)dh / 2 + 0.1);
+    const int left = (int)std::rint((double)dw / 2 - 0.1), right = (int)std::rint((double)dw / 2 + 0.1);
+    *net_h = nh + top + bottom;
+    *net_w = nw + left + right;
+    *new_h = nh;
+    *new_w = nw;
+    *pad_top = top;
+    *pad_left = left;
+    *gain = r;
+    return OG_OK;
+}
+
+int og_yolo_letterbox_host(const uint8_t* src, int H, int W, int channels, int imgsz, uint8_t* out) {
+    if (!src || !out) return fail(OG_EINVAL, "null buffer");
+    if (channels != 1 && channels != 3) return fail(OG_EINVAL, "channels must be 1 (gray) or 3 (BGR)");
+    YGeo g;
+    int rc = og_yolo_letterbox_geometry(H, W, imgsz, &g.net_h, &g.net_w, &g.new_h, &g.new_w, &g.top, &g.left, &g.gain);
+    if (rc) return rc;
+    for (int y = 0; y < g.net_h; ++y)
+        for (int x = 0; x < g.net_w; ++x) {
+            uint8_t* o = out + ((size_t)y * g.net_w + x) * 3;
+            if (channels == 3) og_letterbox_px<3>(src, H, W, g.new_h, g.new_w, g.top, g.left, y, x, o);
+            else og_letterbox_px<1>(src, H, W, g.new_h, g.new_w, g.top, g.left, y, x, o);
+        }
+    return OG_OK;
+}
+
+int og_yolo_letterbox_u8_dev(og_yolo* h, const uint8_t* src_dev, int B, int H, int W, int channels, int imgsz, uint8_t* out_dev) {
+    OG_SCOPE(h);
+    YGeo g;
+    int rc = y_check_resized(h, B, H, W, channels, imgsz, g);
+    if (rc) return rc;
+    if (B == 0) return OG_OK;
+    if (!src_dev || !out_dev) return fail(OG_EINVAL, "null buffer");
+    constexpr int kMaxY = 32768;   // grid.y
+    for (int b0 = 0; b0 < B; b0 += kMaxY) {
+        const int nb = B - b0 < kMaxY ? B - b0 : kMaxY;
+        if ((rc = y_letterbox(h, src_dev + (size_t)b0 * H * W * channels, nb, H, W, channels, g, out_dev + (size_t)b0 * g.net_h * g.net_w * 3)))
+            return rc;
+    }
+    return OG_OK;
+}
+
+int og_yolo_detect_resized_u8_dev(og_yolo* h, const uint8_t* src_dev, int B, int H, int W, int channels, int imgsz, float conf,
+                                  float* best_dev) {
+    OG_SCOPE(h);
+    YGeo g;
+    int rc = y_check_resized(h, B, H, W, channels, imgsz, g);
+    if (rc) return rc;
+    if (B == 0) return OG_OK;
+    if (!src_dev || !best_dev) return fail(OG_EINVAL, "null buffer");
+    if (h->pend_B) return fail(OG_EINVAL, "og_yolo_detect_resized_u8_dev: a begin / end call is in flight on this handle");
+    const size_t net1 = (size_t)g.net_h * g.net_w * 3, src1 = (size_t)H * W * channels;
+    if ((rc = y_stage(h, al256((size_t)(B < kNetLaunch ? B : kNetLaunch) * net1)))) return rc;
+    uint8_t* net = (uint8_t*)h->stage;   // reused by every launch: the stream orders its writers after its readers
+    for (int b0 = 0; b0 < B; b0 += kNetLaunch) {
+        const int nb = B - b0 < kNetLaunch ? B - b0 : kNetLaunch;
+        if ((rc = y_letterbox(h, src_dev + (size_t)b0 * src1, nb, H, W, channels, g, net)) ||
+            (rc = og_yolo_detect_u8_dev(h, net, nb, g.net_h, g.net_w, conf, best_dev + (size_t)b0 * 5, nullptr)))
+            return y_fail_sync(h, rc);
+        OG_LAUNCH(k_scale_boxes, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, h->stream, best_dev + (size_t)b0 * 5, nb, g.scale() ? 1 : 0,
+                  (float)g.gain, g.left, g.top, H, W);
+        ++h->n_scale_boxes;
+    }
+    return OG_OK;
+}
+
+int og_yolo_detect_resized_u8(og_yolo* h, const uint8_t* frames, int B, int H, int W, int channels, int imgsz, float conf, float* best) {
+    OG_SCOPE(h);
+    YGeo g;
+    int rc = y_check_resized(h, B, H, W, channels, imgsz, g);
+    if (rc) return rc;
+    if (B == 0) return OG_OK;
+    if (!frames || !best) return fail(OG_EINVAL, "null buffer");
+    if (h->pend_B) return fail(OG_EINVAL, "og_yolo_detect_resized_u8: a begin / end call is in flight on this handle");
+    const size_t net1 = (size_t)g.net_h * g.net_w * 3, src1 = (size_t)H * W * channels;
+    if (B <= h->latency_batch) {
+        size_t o_best = 0;
+        if ((rc = y_resized_latency(h, frames, B, H, W, channels, g, conf, &o_best))) return y_fail_sync(h, rc);
+        HIPCHK(hipStreamSynchronize(h->stream));
+        memcpy(best, (char*)h->pin + o_best, (size_t)B * 5 * 4);
+    } else {
+        // the stage: [source chunk | network input of one launch | up to kBestRows best rows] -- bounded by the options, independent of B
+        size_t fit = ((size_t)h->source_stage_kib << 10) / src1;
+        if (fit < 1) fit = 1;   // a frame larger than the setting is staged alone
+        if (fit > (size_t)kNetLaunch) fit = kNetLaunch;
+        if (fit > (size_t)B) fit = B;
+        const int nl = B < kNetLaunch ? B : kNetLaunch;
+        const int nr = B < kBestRows ? B : kBestRows;
+        const size_t o_net = al256(fit * src1), o_best = o_net + al256((size_t)nl * net1), tot = o_best + al256((size_t)nr * 5 * 4);
+        if ((rc = y_stage(h, tot))) return rc;
+        char* s = (char*)h->stage;
+        for (int b0 = 0; b0 < B; b0 += kNetLaunch) {
+            const int nb = B - b0 < kNetLaunch ? B - b0 : kNetLaunch;
+            for (int c0 = 0; c0 < nb; c0 += (int)fit) {
+                const int nc = nb - c0 < (int)fit ? nb - c0 : (int)fit;
+                hipError_t e = hipMemcpyAsync(s, frames + (size_t)(b0 + c0) * src1, (size_t)nc * src1, hipMemcpyHostToDevice, h->stream);
+                if (e != hipSuccess) return y_fail_sync(h, fail(OG_EHIP, std::string("hipMemcpyAsync (source frames): ") + hipGetErrorString(e)));
+                if ((rc = y_letterbox(h, (const uint8_t*)s, nc, H, W, channels, g, (uint8_t*)(s + o_net) + (size_t)c0 * net1))) return y_fail_sync(h, rc);
+            }
+            const int r0 = b0 % kBestRows, end = b0 + nb;
+            if ((rc = og_yolo_detect_u8_dev(h, (const uint8_t*)(s + o_net), nb, g.net_h, g.net_w, conf, (float*)(s + o_best) + (size_t)r0 * 5, nullptr)))
+                return y_fail_sync(h, rc);
+            if (end % kBestRows == 0 || end == B) {   // (a copy to pageable memory waits for the stream: once per kBestRows frames)
+                const int first = end - (r0 + nb);
+                hipError_t e = hipMemcpyAsync(best + (size_t)first * 5, s + o_best, (size_t)(r0 + nb) * 5 * 4, hipMemcpyDeviceToHost, h->stream);
+                if (e != hipSuccess) return y_fail_sync(h, fail(OG_EHIP, std::string("hipMemcpyAsync (best): ") + hipGetErrorString(e)));
+            }
+        }
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    if ((rc = y_check_range(h))) return rc;
+    for (int b = 0; b < B; ++b) og_scale_box(best + (size_t)b * 5, g.scale(), (float)g.gain, g.left, g.top, H, W);
+    return OG_OK;
+}
+
+int og_yolo_detect_resized_u8_begin(og_yolo* h, const uint8_t* frames, int B, int H, int W, int channels, int imgsz, float conf) {
+    OG_SCOPE(h);
+    YGeo g;
+    int rc = y_check_resized(h, B, H, W, channels, imgsz, g);
+    if (rc) return rc;
+    if (h->pend_B) return fail(OG_EINVAL, "og_yolo_detect_resized_u8_begin: a call is already in flight on this handle");
+    if (B == 0) return OG_OK;
+    if (!frames) return fail(OG_EINVAL, "null buffer");
+    if (B <= h->latency_batch && h->zero_copy) {
+        size_t o_best = 0;
+        if ((rc = y_resized_latency(h, frames, B, H, W, channels, g, conf, &o_best))) return y_fail_sync(h, rc);
+        h->pend_sync = false;
+        h->pend_off = o_best;
+        h->pend_resized = true;
+        h->pend_scale = g.scale();
+        h->pend_gain = (float)g.gain;
+        h->pend_left = g.left;
+        h->pend_top = g.top;
+        h->pend_H = H;
+        h->pend_W = W;
+    } else {   // larger calls / "zero_copy" 0: run now, deliver at end (as og_yolo_detect_u8_begin)
+        h->pend_best.resize((size_t)B * 5);
+        if ((rc = og_yolo_detect_resized_u8(h, frames, B, H, W, channels, imgsz, conf, h->pend_best.data()))) return rc;
+        h->pend_sync = true;
+        h->pend_resized = true;
+    }
+    h->pend_B = B;
+    return OG_OK;
+}
+
+long long og_yolo_launch_count(og_yolo* h, const char* kernel) {
+    if (!h || !kernel) return fail(OG_EINVAL, "null argument");
+    const std::string k(kernel);
+    if (k == "k_letterbox_bgr") return h->n_letterbox;
+    if (k == "k_scale_boxes") return h->n_scale_boxes;
+    return fail(OG_EINVAL, "og_yolo_launch_count: no counter for " + k);
+}
+
+}  // extern "C"
+
+extern "C" {
 
 int og_yolo_sync(og_yolo* h) {
     if (!h || !h->stream) return fail(OG_ESTATE, "handle not finalized");

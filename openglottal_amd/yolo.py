@@ -87,9 +87,11 @@ class YoloV8Detector:
             lib().og_yolo_destroy(h)
             raise
         self._h = h
+        self._geo = {}   # (H, W) -> is letterbox_bgr the identity for frames of this size?
 
     def set_option(self, name: str, value: int) -> None:
-        """Options of the C-ABI (``og_yolo_set_option``): ``precision`` (0 f32 | 2 f16), ``latency_batch``, ``splitk_slots``, ``splitk_div``."""
+        """Options of the C-ABI (``og_yolo_set_option``): ``precision`` (0 f32 | 2 f16), ``latency_batch``, ``splitk_slots``, ``splitk_div``,
+        ``source_stage_kib`` (KiB of source frames staged per upload of a resized call), ``source_mapped``."""
         check(lib().og_yolo_set_option(self._h, name.encode(), int(value)), f"og_yolo_set_option({name})")
 
     def detect_batch(self, frames_bgr: np.ndarray, conf: float = 0.25, want_pred: bool = False):
@@ -114,13 +116,89 @@ class YoloV8Detector:
         check(lib().og_yolo_sync(self._h), "og_yolo_sync")
         return best.cpu().numpy()
 
+    def letterbox_dev(self, frames) -> np.ndarray:
+        """``[B,H,W,3]`` / ``[B,H,W]`` u8 frames of one size → the letterboxed batch ``[B,Hn,Wn,3]`` as ``k_letterbox_bgr`` writes it
+        (``og_yolo_letterbox_u8_dev``): the parity tap against ``letterbox_bgr``."""
+        f = np.ascontiguousarray(frames, dtype=np.uint8)
+        B, H0, W0 = f.shape[:3]
+        ch = 1 if f.ndim == 3 else f.shape[3]
+        i = [C.c_int() for _ in range(6)]
+        g = C.c_double()
+        check(lib().og_yolo_letterbox_geometry(H0, W0, self.imgsz, *[C.byref(v) for v in i], C.byref(g)), "og_yolo_letterbox_geometry")
+        out = np.empty((B, i[0].value, i[1].value, 3), np.uint8)
+        src = lib().og_malloc(max(1, f.nbytes))
+        dst = lib().og_malloc(max(1, out.nbytes))
+        try:
+            if not src or not dst:
+                check(-1, "og_malloc")
+            check(lib().og_memcpy_h2d(src, ptr(f), f.nbytes), "og_memcpy_h2d")
+            check(lib().og_yolo_letterbox_u8_dev(self._h, src, B, H0, W0, ch, self.imgsz, dst), "og_yolo_letterbox_u8_dev")
+            check(lib().og_yolo_sync(self._h), "og_yolo_sync")
+            check(lib().og_memcpy_d2h(ptr(out), dst, out.nbytes), "og_memcpy_d2h")
+        finally:
+            for p_ in (src, dst):
+                if p_:
+                    lib().og_free(p_)
+        return out
+
+    def detect_resized_dev(self, src_dev, B: int, H: int, W: int, channels: int = 3, conf: float = 0.25) -> np.ndarray:
+        """``[B,H,W,channels]`` u8 frames of any size RESIDENT ON THE DEVICE → ``best [B,5]`` in source pixels on the host."""
+        import torch
+
+        best = torch.empty((B, 5), dtype=torch.float32, device=src_dev.device)
+        check(lib().og_yolo_detect_resized_u8_dev(self._h, ptr(src_dev), B, H, W, channels, self.imgsz, float(conf), ptr(best)),
+              "og_yolo_detect_resized_u8_dev")
+        check(lib().og_yolo_sync(self._h), "og_yolo_sync")
+        return best.cpu().numpy()
+
+    def launch_count(self, kernel: str) -> int:
+        """Launches of ``k_letterbox_bgr`` / ``k_scale_boxes`` issued by this handle so far (for tests)."""
+        n = lib().og_yolo_launch_count(self._h, kernel.encode())
+        if n < 0:
+            check(int(n), "og_yolo_launch_count")
+        return int(n)
+
+    def _native_geometry(self, shape, dtype):
+        """``(channels, identity)`` when frames of this shape go through the device letterbox (u8, gray or BGR), else ``None``."""
+        if dtype != np.uint8 or len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3):
+            return None
+        key = (shape[0], shape[1])
+        geo = self._geo.get(key)
+        if geo is None:
+            i = [C.c_int() for _ in range(6)]
+            g = C.c_double()
+            check(lib().og_yolo_letterbox_geometry(shape[0], shape[1], self.imgsz, *[C.byref(v) for v in i], C.byref(g)),
+                  "og_yolo_letterbox_geometry")
+            nh, nw, ch, cw, top, left = (v.value for v in i)
+            geo = self._geo[key] = (nh, nw) == (ch, cw) == key and (g.value, left, top) == (1.0, 0, 0)
+        return (1 if len(shape) == 2 else 3), geo
+
     def detect_frames(self, frames_bgr, conf: float = 0.25) -> np.ndarray:
         """Frames of ONE size ``[B,H,W,3]`` (or ``[B,H,W]`` gray) at their ORIGINAL resolution → ``best [B,5]`` in
         original-frame pixels (conf = -1: no detection): what the ultralytics predictor does per call of
         ``self.model(frame_bgr, conf=...)`` (detector.py:58) — letterbox to ``imgsz``, network, ``scale_boxes`` back,
         clip — for the whole batch in one device pass.  ``__call__`` is this with B = 1, so the batched callers
         (`features.area_waveform`, `evaluate.evaluate`, `dist.sharded_gated_area_waveform`) and the per-frame
-        ``TemporalDetector.detect`` see the same boxes for every frame size, not only where the letterbox is the identity."""
+        ``TemporalDetector.detect`` see the same boxes for every frame size, not only where the letterbox is the identity.
+
+        u8 frames whose letterbox is NOT the identity go up at their own size (gray: one byte per pixel) and are letterboxed on
+        the device (``og_yolo_detect_resized_u8``): the bits of ``detect_frames_host``, without its per-frame numpy
+        resize.  Identity frames (sides multiples of 32, long side ``imgsz``) take ``detect_frames_host``'s path as before."""
+        f = np.asarray(frames_bgr)
+        nat = self._native_geometry(f.shape[1:], f.dtype) if f.ndim in (3, 4) and f.shape[0] else None
+        if nat is None or nat[1]:
+            return self.detect_frames_host(f, conf)
+        f = np.ascontiguousarray(f)
+        B, H0, W0 = f.shape[:3]
+        best = np.empty((B, 5), np.float32)
+        check(lib().og_yolo_detect_resized_u8(self._h, ptr(f), B, H0, W0, nat[0], self.imgsz, float(conf), ptr(best)),
+              "og_yolo_detect_resized_u8")
+        return best
+
+    def detect_frames_host(self, frames_bgr, conf: float = 0.25) -> np.ndarray:
+        """``detect_frames`` with the letterbox on the HOST (``letterbox_bgr`` per frame in numpy, ``np.stack``, the network at
+        network size, the f32 scale-back): the specification the device path is held to bit for bit, and the path of frames
+        whose letterbox is the identity."""
         f = np.asarray(frames_bgr)
         if f.ndim == 3:
             f = np.repeat(f[..., None], 3, axis=-1)
@@ -151,10 +229,17 @@ class YoloV8Detector:
         return b[None, :4].astype(np.float32), b[4:5].astype(np.float32)
 
     def submit(self, frame_bgr: np.ndarray, conf: float = 0.25) -> None:
-        """First half of ``__call__`` (``og_yolo_detect_u8_begin``): letterbox on the host, enqueue the detector's chain on its own
-        stream, return.  ``result()`` delivers what ``__call__`` would have returned.  In the reference's frame loop
+        """First half of ``__call__`` (``og_yolo_detect_u8_begin``, or ``og_yolo_detect_resized_u8_begin`` for a u8 frame whose
+        letterbox is not the identity: letterbox on the device): enqueue the detector's chain on its own stream, return.  ``result()`` delivers what ``__call__`` would have returned.  In the reference's frame loop
         (features.py:235-245) the box only gates the count of the U-Net's mask, so the U-Net call of the same frame fits in between."""
         f = np.asarray(frame_bgr)
+        nat = self._native_geometry(f.shape, f.dtype)
+        if nat is not None and not nat[1]:   # letterbox on the device; og_yolo_detect_u8_end delivers source-pixel boxes
+            f = np.ascontiguousarray(f)
+            check(lib().og_yolo_detect_resized_u8_begin(self._h, ptr(f), 1, f.shape[0], f.shape[1], nat[0], self.imgsz, float(conf)),
+                  "og_yolo_detect_resized_u8_begin")
+            self._pending = (f.shape[0], f.shape[1], 1.0, 0, 0)   # nothing left to scale in result()
+            return
         if f.ndim == 2:
             f = np.repeat(f[..., None], 3, axis=-1)
         img, gain, px, py = letterbox_bgr(f, self.imgsz)

@@ -25,6 +25,23 @@
  *  - *_dev entry points take DEVICE pointers (hipMalloc'd or a torch tensor's
  *    data_ptr()), enqueue on the handle's stream and return without syncing;
  *    call og_unet_sync() before reading results.
+ *  - ALIGNMENT of caller-owned buffers, host and device alike: the natural alignment of the element type, nothing more.
+ *      1 byte  (any address): every u8 buffer -- gray, frames, src, src_dev, bgr, bgr_dev, packed, mask, pred_dev / gt_dev of
+ *               og_mask_stats_dev, out, out_dev, out_masks, tiles_scratch, tile_masks_scratch, each frame_ptrs[i];
+ *      4 bytes: every int32 / float buffer -- boxes, geom, shapes, area, stats, logits, net_logits, net_prob, prob, x_nchw,
+ *               logits_nchw, best, pred of the detector, out_nchw, dims, i0 / i1 / frac_f32 / a1_i32, the int* of
+ *               og_yolo_letterbox_geometry;
+ *      8 bytes: offsets (int64), the frame_ptrs array itself, gain (double).
+ *    A pointer that violates this is refused with OG_EINVAL before anything is launched or copied (NULL for an optional buffer
+ *    passes).  Why this is enough: the kernels touch caller memory only with element-sized accesses -- byte loads of frames
+ *    (k_conv_first, the fused first layer, k_bgr2gray, the resize / letterbox kernels), byte stores of masks
+ *    (buffer_store_byte in the fused head, plain stores elsewhere), dword stores of logits / prob / best / pred, dword atomics
+ *    or stores on area / stats; every 16-byte access (f32x4, LDS-DMA, buffer_store_dwordx4) goes to the library's own arenas,
+ *    weights and workspaces, which it allocates 256-byte aligned.  The sub-pointers the library forms for a micro-batch
+ *    starting at frame b0 -- gray + b0*H*W (u8), mask + b0*H*W (u8), area + b0 (int32), boxes + 4*b0 (int32), logits + b0*H*W
+ *    (float), best + 5*b0, pred + 5*A*b0 (float), frames + b0*H*W*channels (u8) -- add whole elements to the caller's pointer,
+ *    so they meet the same rule for every B, H, W and channel count the shape checks admit; a slice such as pinned[lo:lo + B]
+ *    of a u8 video is valid at any lo.
  *  - a handle is not thread-safe; distinct handles are independent.
  *  - tensors are plain C arrays: NCHW float32 for og_unet_forward_f32 (as the
  *    reference's torch tensors), [B,H,W] uint8 for frames and masks.

@@ -24,6 +24,15 @@ int fail(int code, const std::string& msg) {
     return code;
 }
 
+// The header's alignment rule for caller-owned buffers: the natural alignment of the element type (u8: none).  Checked by every
+// entry point before anything is launched or copied; NULL (an optional buffer left out) passes.
+bool og_misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+#define OG_ALIGN(ptr)                                                                                                              \
+    do {                                                                                                                           \
+        if (og_misaligned((ptr), alignof(decltype(*(ptr)))))                                                                       \
+            return fail(OG_EINVAL, std::string(#ptr) + " must be aligned to " + std::to_string(alignof(decltype(*(ptr)))) + " bytes"); \
+    } while (0)
+
 #define HIPCHK(expr)                                                                          \
     do {                                                                                      \
         hipError_t e_ = (expr);                                                               \
@@ -2183,6 +2192,9 @@ int og_unet_segment_u8_dev(og_unet* h, const uint8_t* gray, int B, int H, int W,
     OG_SCOPE(h);
     int rc = check_shape(h, B, H, W);
     if (rc) return rc;
+    OG_ALIGN(boxes);
+    OG_ALIGN(area);
+    OG_ALIGN(logits);
     if (!gray && B > 0) return fail(OG_EINVAL, "gray is null");
     if (B == 0) return OG_OK;
     const int chunk = effective_chunk(h);
@@ -2244,6 +2256,10 @@ static int stream_impl(og_unet* h, const uint8_t* frames, const uint8_t* const* 
     int rc = rs ? check_resized(h, B, H, W, ch, Hn, Wn) : check_shape(h, B, H, W);
     if (rc) return rc;
     if (ch != 1 && ch != 3) return fail(OG_EINVAL, "channels must be 1 (gray) or 3 (BGR)");
+    OG_ALIGN(frame_ptrs);
+    OG_ALIGN(boxes);
+    OG_ALIGN(area);
+    OG_ALIGN(logits);
     if (B == 0) return OG_OK;
     if (!frames && !frame_ptrs) return fail(OG_EINVAL, "frames is null");
     if (frame_ptrs)
@@ -2415,6 +2431,11 @@ int og_unet_segment_resized_u8_dev(og_unet* h, const uint8_t* src, int B, int H,
     OG_SCOPE(h);
     int rc = check_resized(h, B, H, W, channels, net_h, net_w);
     if (rc) return rc;
+    OG_ALIGN(boxes);
+    OG_ALIGN(area);
+    OG_ALIGN(net_logits);
+    OG_ALIGN(net_prob);
+    OG_ALIGN(prob);
     if (!src && B > 0) return fail(OG_EINVAL, "src is null");
     if (B == 0) return OG_OK;
     const int chunk = resized_chunk(h, H, W, channels), cb = chunk < B ? chunk : B;
@@ -2435,6 +2456,10 @@ int og_unet_segment_resized_u8_dev(og_unet* h, const uint8_t* src, int B, int H,
 
 int og_linear_taps_host(int src_len, int dst_len, int32_t* i0, int32_t* i1, float* frac, int32_t* a1) {
     if (src_len <= 0 || dst_len <= 0 || !i0 || !i1 || !frac || !a1) return fail(OG_EINVAL, "bad argument");
+    OG_ALIGN(i0);
+    OG_ALIGN(i1);
+    OG_ALIGN(frac);
+    OG_ALIGN(a1);
     for (int d = 0; d < dst_len; ++d) {
         int k0, k1;
         float f;
@@ -2454,6 +2479,9 @@ int og_unet_segment_u8(og_unet* h, const uint8_t* gray, int B, int H, int W, flo
     OG_SCOPE(h);
     int rc = check_shape(h, B, H, W);
     if (rc) return rc;
+    OG_ALIGN(boxes);
+    OG_ALIGN(area);
+    OG_ALIGN(logits);
     if (B == 0) return OG_OK;
     if (!gray) return fail(OG_EINVAL, "gray is null");
     const size_t HW = (size_t)H * W;
@@ -2480,6 +2508,8 @@ int og_unet_forward_f32(og_unet* h, const float* x, int B, int H, int W, float* 
     if (rc) return rc;
     if (B == 0) return OG_OK;
     if (!x || !logits) return fail(OG_EINVAL, "null buffer");
+    OG_ALIGN(x);
+    OG_ALIGN(logits);
     const size_t HW = (size_t)H * W;
     const size_t o_in = 0, o_out = al256(B * HW * 4), tot = o_out + al256(B * HW * 4);
     if ((rc = ensure_stage(h, tot))) return rc;
@@ -2513,6 +2543,8 @@ int og_mask_area_dev(og_unet* h, const uint8_t* mask, int B, int H, int W, const
     if (!h || !h->finalized) return fail(OG_ESTATE, "handle not finalized");
     OG_SCOPE(h);
     if (!mask || !area || B < 0 || H <= 0 || W <= 0) return fail(OG_EINVAL, "bad argument");
+    OG_ALIGN(boxes);
+    OG_ALIGN(area);
     if (B == 0) return OG_OK;
     HIPCHK(hipMemsetAsync(area, 0, (size_t)B * 4, h->stream));
     const int HW = H * W, bpf = (HW + 4095) / 4096;
@@ -2545,6 +2577,9 @@ int og_canvas_letterbox_u8_dev(og_unet* h, const uint8_t* packed, const int64_t*
     if (B < 0 || size <= 0 || (channels != 1 && channels != 3) || value < 0 || value > 255) return fail(OG_EINVAL, "bad argument");
     if (B == 0) return OG_OK;
     if (!packed || !offsets || !shapes || !geom || !out) return fail(OG_EINVAL, "null buffer");
+    OG_ALIGN(offsets);
+    OG_ALIGN(shapes);
+    OG_ALIGN(geom);
     const size_t SS = (size_t)size * size * channels;
     for (int b0 = 0; b0 < B; b0 += 65535) {   // grid.y <= 65535
         const int nb = (B - b0 < 65535) ? B - b0 : 65535;
@@ -2567,6 +2602,9 @@ int og_canvas_letterbox_u8(og_unet* h, const uint8_t* packed, const int64_t* off
     if (B < 0 || size <= 0 || (channels != 1 && channels != 3)) return fail(OG_EINVAL, "bad argument");
     if (B == 0) return OG_OK;
     if (!packed || !offsets || !shapes || !geom || !out) return fail(OG_EINVAL, "null buffer");
+    OG_ALIGN(offsets);
+    OG_ALIGN(shapes);
+    OG_ALIGN(geom);
     size_t total = 0;
     for (int b = 0; b < B; ++b) {   // host variant: the records are readable here, so check them
         const long long hh = shapes[2 * b], ww = shapes[2 * b + 1];
@@ -2596,6 +2634,8 @@ int og_mask_stats_dev(og_unet* h, const uint8_t* pred, const uint8_t* gt, int B,
     if (!h || !h->finalized) return fail(OG_ESTATE, "handle not finalized");
     OG_SCOPE(h);
     if (!pred || !gt || !stats || B < 0 || H <= 0 || W <= 0) return fail(OG_EINVAL, "bad argument");
+    OG_ALIGN(boxes);
+    OG_ALIGN(stats);
     if (B == 0) return OG_OK;
     HIPCHK(hipMemsetAsync(stats, 0, (size_t)B * 12, h->stream));
     const int HW = H * W, bpf = (HW + 4095) / 4096;
@@ -2612,6 +2652,8 @@ int og_unet_segment_crops_u8_dev(og_unet* h, const uint8_t* gray, int B, int H, 
     if (B == 0) return OG_OK;
     if (!gray || !boxes || !geom || !tiles_scratch || !tile_masks_scratch || !out_masks || H <= 0 || W <= 0)
         return fail(OG_EINVAL, "null buffer / bad size");
+    OG_ALIGN(boxes);
+    OG_ALIGN(geom);
     const size_t HW = (size_t)H * W, SS = (size_t)size * size;
     for (int b0 = 0; b0 < B; b0 += 65535) {   // grid.y <= 65535
         const int nb = (B - b0 < 65535) ? B - b0 : 65535;
@@ -2636,6 +2678,8 @@ int og_unet_segment_crops_u8(og_unet* h, const uint8_t* gray, int B, int H, int 
     if (rc) return rc;
     if (B == 0) return OG_OK;
     if (!gray || !boxes || !geom || !out_masks || H <= 0 || W <= 0) return fail(OG_EINVAL, "null buffer / bad size");
+    OG_ALIGN(boxes);
+    OG_ALIGN(geom);
     for (int b = 0; b < B; ++b) {   // "no detection" (x1 < 0) and empty boxes are legal (all-zero mask); anything else must index inside
         const int32_t *bx = boxes + 4 * b, *g = geom + 4 * b;
         if (bx[0] < 0 || bx[2] <= bx[0] || bx[3] <= bx[1]) continue;
@@ -2664,6 +2708,8 @@ int og_unet_segment_crops_u8(og_unet* h, const uint8_t* gray, int B, int H, int 
 int og_unet_get_activation(og_unet* h, const char* name, int B, float* out, size_t cap, int* dims) {
     if (!h || !h->finalized || !h->arena) return fail(OG_ESTATE, "no forward has run yet");
     if (!name || !out || !dims || B < 1 || B > h->lastB) return fail(OG_EINVAL, "bad argument (B must be <= last chunk size)");
+    OG_ALIGN(out);
+    OG_ALIGN(dims);
     const std::string n(name);
     const int L = h->L;
     const Act* a = nullptr;

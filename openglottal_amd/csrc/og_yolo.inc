@@ -1007,6 +1007,8 @@ int og_yolo_detect_u8_dev(og_yolo* h, const uint8_t* bgr_dev, int B, int H, int 
     if (rc) return rc;
     if (B == 0) return OG_OK;
     if (!bgr_dev || !best_dev) return fail(OG_EINVAL, "null buffer");
+    OG_ALIGN(best_dev);
+    OG_ALIGN(pred_dev);
     // at most kMaxLaunch frames per kernel chain: bounds the arena and keeps the conv kernels' grid.z (frame x column
     // tile) inside 16 bits; callers may pass any B
     constexpr int kMaxLaunch = 512;
@@ -1070,6 +1072,7 @@ int og_yolo_detect_u8_begin(og_yolo* h, const uint8_t* bgr, int B, int H, int W,
 int og_yolo_detect_u8_end(og_yolo* h, float* best) {
     OG_SCOPE(h);
     if (!h || !h->pend_B) return fail(OG_EINVAL, "og_yolo_detect_u8_end: no call in flight");
+    OG_ALIGN(best);   // (refused with the call still in flight: a second og_yolo_detect_u8_end with a good pointer delivers it)
     const int B = h->pend_B;
     h->pend_B = 0;
     if (!best) return fail(OG_EINVAL, "null buffer");
@@ -1090,6 +1093,8 @@ int og_yolo_detect_u8(og_yolo* h, const uint8_t* bgr, int B, int H, int W, float
     if (rc) return rc;
     if (B == 0) return OG_OK;
     if (!bgr || !best) return fail(OG_EINVAL, "null buffer");
+    OG_ALIGN(best);
+    OG_ALIGN(pred);
     if (h->pend_B) return fail(OG_EINVAL, "og_yolo_detect_u8: a begin / end call is in flight on this handle");
     const int A = og_yolo_num_anchors(h, H, W);
     const size_t n_in = (size_t)B * H * W * 3, o_best = al256(n_in), o_pred = o_best + al256((size_t)B * 5 * 4),
@@ -1235,6 +1240,13 @@ int og_yolo_letterbox_geometry(int H, int W, int imgsz, int* net_h, int* net_w, 
                                double* gain) {
 #pragma clang fp contract(off)
     if (!net_h || !net_w || !new_h || !new_w || !pad_top || !pad_left || !gain) return fail(OG_EINVAL, "null argument");
+    OG_ALIGN(net_h);
+    OG_ALIGN(net_w);
+    OG_ALIGN(new_h);
+    OG_ALIGN(new_w);
+    OG_ALIGN(pad_top);
+    OG_ALIGN(pad_left);
+    OG_ALIGN(gain);
     if (H < 1 || W < 1 || H > 8192 || W > 8192) return fail(OG_EINVAL, "frame sides must be in 1..8192");
     if (imgsz < 32 || imgsz > 8192 || imgsz % 32) return fail(OG_EINVAL, "imgsz must be a positive multiple of 32 (at most 8192)");
     const double rh = (double)imgsz / (double)H, rw = (double)imgsz / (double)W, r = rh < rw ? rh : rw;
@@ -1292,6 +1304,7 @@ int og_yolo_detect_resized_u8_dev(og_yolo* h, const uint8_t* src_dev, int B, int
     if (rc) return rc;
     if (B == 0) return OG_OK;
     if (!src_dev || !best_dev) return fail(OG_EINVAL, "null buffer");
+    OG_ALIGN(best_dev);
     if (h->pend_B) return fail(OG_EINVAL, "og_yolo_detect_resized_u8_dev: a begin / end call is in flight on this handle");
     const size_t net1 = (size_t)g.net_h * g.net_w * 3, src1 = (size_t)H * W * channels;
     if ((rc = y_stage(h, al256((size_t)(B < kNetLaunch ? B : kNetLaunch) * net1)))) return rc;
@@ -1315,6 +1328,7 @@ int og_yolo_detect_resized_u8(og_yolo* h, const uint8_t* frames, int B, int H, i
     if (rc) return rc;
     if (B == 0) return OG_OK;
     if (!frames || !best) return fail(OG_EINVAL, "null buffer");
+    OG_ALIGN(best);
     if (h->pend_B) return fail(OG_EINVAL, "og_yolo_detect_resized_u8: a begin / end call is in flight on this handle");
     const size_t net1 = (size_t)g.net_h * g.net_w * 3, src1 = (size_t)H * W * channels;
     if (B <= h->latency_batch) {
@@ -1409,6 +1423,8 @@ int og_yolo_sync(og_yolo* h) {
 int og_yolo_get_activation(og_yolo* h, const char* name, int B, float* out, size_t cap, int* dims) {
     if (!h || !h->finalized || !h->arena) return fail(OG_ESTATE, "no detect call has run yet");
     if (!name || !out || !dims || B < 1 || B > h->lastB) return fail(OG_EINVAL, "bad argument");
+    OG_ALIGN(out);
+    OG_ALIGN(dims);
     auto it = h->acts.find(name);
     if (it == h->acts.end()) return fail(OG_EINVAL, std::string("unknown activation ") + name);
     const YView& v = it->second.v;

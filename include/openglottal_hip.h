@@ -228,7 +228,9 @@ int og_unet_set_graphs(og_unet* h, int enable);
  * buffers directly instead of through H2D / D2H / memset commands, each of which costs a ~5 us launch floor on the one stream:
  * 0.370 -> 0.358 ms per unet_segment_frame; results identical),
  * "inject_fault" n (TEST HOOK: the n-th conv launch from now on fails with OG_EHIP after scribbling over the arrival counters of the
- * fused reduces; every error path restores them -- tests/test_gpu_recovery.py).
+ * fused reduces; every error path restores them -- tests/test_gpu_recovery.py),
+ * "entry_f32" 0|1 [0] (DIAGNOSTIC: og_unet_profile and og_unet_plan walk the chain of og_unet_forward_f32 -- `gray_dev` then holds
+ * B x H x W floats -- so that the first-layer kernel of the NCHW-float entry point can be named; no other call reads it).
  *
  * The two options that DO change the arithmetic:
  * "wino" 0|1 [1]: the form of the HANDLE.  1 = every 3x3 conv whose map tiles (H, W multiples of 16; 32 rows for 32-column layers)
@@ -277,8 +279,9 @@ double og_unet_flops_per_frame(og_unet* h, int H, int W);
  * handle with every launch recorded instead of issued.  `options` = "name=value,name=value" (og_unet_set_option names), `lanes` =
  * lanes of the call the micro-batch belongs to (1..3: a scheduling hint of the under-filled launches).  `out` receives one line per
  * launch, "kernel|grid.x|grid.y|grid.z|block|lds_bytes|workspace_bytes|arrival_counters"; returns the number of launches or a
- * negative error code.  `kernel` is the launch site's text; an f16-mode conv (precision 2) is named by its instantiation and the K
- * walk it is given, "(k_conv_mfma_f<2, 0, 16, 2, false, true>) chunks=3 k_half=1" (64-channel chunks; k_half: the last one holds 32).  Nothing here has a counterpart in the reference (it launches nothing by hand); it exists so that the bounds
+ * negative error code.  `kernel` is the instantiation that would run, every template argument resolved, with what is decided
+ * at run time behind it ("k_conv_mfma_o<1, 0, 8, 3, false, false> ksplit=4": K parts; "k_conv_wino_w<1> nt=2": the layer's canonical
+ * column tiling, i.e. its weight pack); an f16-mode conv (precision 2) is named by its instantiation and the K walk it is given, "(k_conv_mfma_f<2, 0, 16, 2, false, true>) chunks=3 k_half=1" (64-channel chunks; k_half: the last one holds 32).  Nothing here has a counterpart in the reference (it launches nothing by hand); it exists so that the bounds
  * every launch must respect -- og_workspace_limit() -- can be checked for every micro-batch size, layer shape and forced option on a
  * machine without a GPU (tests/test_launch_plan.py), instead of being found by a faulting kernel. */
 int og_unet_plan(const int* features, int n_levels, int B, int H, int W, int lanes, const char* options, char* out, size_t cap,

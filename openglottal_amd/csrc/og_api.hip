@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -112,6 +113,17 @@ inline void plan_write(const char* name, const void* p, long long bytes) {
 inline void plan_label_f(const char* inst, int n_chunks, int k_half) {
     if (!g_plan || g_plan->recs.empty()) return;
     g_plan->recs.back().kernel = std::string(inst) + " chunks=" + std::to_string(n_chunks) + " k_half=" + std::to_string(k_half);
+}
+// og_unet_plan only: name the launch just recorded by the instantiation that would run, every template argument resolved (the
+// launch site's text has template parameters in it), with what is decided at run time behind it (" ksplit=3", " nt=2")
+inline void plan_inst(const char* fmt, ...) {
+    if (!g_plan || g_plan->recs.empty()) return;
+    char inst[96];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(inst, sizeof inst, fmt, ap);
+    va_end(ap);
+    g_plan->recs.back().kernel = inst;
 }
 // every launch of the chain goes through here: a failed launch is reported as OG_EHIP by THIS call (not by a later one)
 #define OG_LAUNCH(kern, grid, block, lds, stream, ...)                                                    \
@@ -241,6 +253,8 @@ struct og_unet {
     int fuse_first = 1;  // compute the first layer inside downs.0's second conv (u8 path, full launches only)
     int fuse_head = 1;   // compute the 1x1 head + threshold + area inside the last conv's epilogue (Cout_p == 32 only)
     int keep_taps = 0;   // fused head: still store the last activation tensor (og_unet_get_activation("ups.N.b"))
+    int entry_f32 = 0;   // DIAGNOSTIC ("entry_f32" 1): og_unet_profile / og_unet_plan walk the chain of the NCHW-float entry point
+                         // (og_unet_forward_f32: k_conv_first<float>, never the fused first layer); gray_dev then holds B x H x W floats
     struct {
         bool active = false;
         float thr = 0.5f;
@@ -647,6 +661,7 @@ int launch_conv_t(og_unet* h, const ConvArgs& a, int n_ntiles) {
     constexpr int lds = 2 * (16 + 2 * PAD) * (TH + 2 * PAD) * 128 + 2 * 32 * NT * 128;
     const unsigned grid = (unsigned)(a.n_spatial * n_ntiles);
     OG_LAUNCH((k_conv_mfma<NT, MODE, TH>), dim3(grid), dim3(256), lds, h->stream, a);
+    plan_inst("k_conv_mfma<%d, %d, %d>", NT, MODE, TH);
     return OG_OK;
 }
 
@@ -711,9 +726,11 @@ int launch_conv_o(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {
         plan_need((long long)a.n_spatial * n_ntiles * a.ksplit * 4 * (((TH / 2) / (4 / NT)) * 16 * 64) * 4,
                   a.tile_counter ? (long long)a.n_spatial * n_ntiles : 0);
     OG_LAUNCH((k_conv_mfma_o<NT, MODE, TH, OCC, false, VS>), dim3(a.tiles_x, a.tiles_y, groups * G * a.zdiv), dim3(256), lds, c.stream, a);
+    plan_inst("k_conv_mfma_o<%d, %d, %d, %d, false, %s> ksplit=%d", NT, MODE, TH, OCC, VS ? "true" : "false", a.ksplit);
     if constexpr (MODE == 0 || MODE == 1) {
         if (a.ksplit > 1 && a.tile_counter == nullptr) {
             OG_LAUNCH((k_splitk_epilogue<NT, MODE, TH>), dim3(a.n_spatial * n_ntiles), dim3(256), 4 * 5120, c.stream, a);
+            plan_inst("k_splitk_epilogue<%d, %d, %d>", NT, MODE, TH);
         }
     }
     return OG_OK;
@@ -741,6 +758,7 @@ int launch_conv_wino(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {  
     a.zrcp = 1.0f / (float)(a.zdiv * G);
     if ((long long)groups * G * a.zdiv > 65535) return fail(OG_EINVAL, "micro-batch too large for one launch (grid.z): lower the chunk size");
     OG_LAUNCH(k_conv_wino<NT>, dim3(a.tiles_x, a.tiles_y, groups * G * a.zdiv), dim3(256), wino_lds<NT>(), c.stream, a);
+    plan_inst("k_conv_wino<%d>", NT);
     return OG_OK;
 }
 
@@ -765,6 +783,7 @@ int launch_conv_wino_ps(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) 
     constexpr int lds = wino_ps_lds<NT, PN>();
     plan_need((long long)a.n_spatial * n_ntiles * (16 * 4 * 1024 * 4), (long long)a.n_spatial * n_ntiles);
     OG_LAUNCH((k_conv_wino_ps<NT, PN>), dim3(a.tiles_x, a.tiles_y, frames * a.zdiv * (16 / PN)), dim3(256), lds, c.stream, a);
+    plan_inst("k_conv_wino_ps<%d, %d>", NT, PN);
     return OG_OK;
 }
 
@@ -837,6 +856,7 @@ int launch_conv_h(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {   //
     a.zrcp = 1.0f / (float)(a.zdiv * G);
     if ((long long)groups * G * a.zdiv > 65535) return fail(OG_EINVAL, "micro-batch too large for one launch (grid.z): lower the chunk size");
     OG_LAUNCH((k_conv_mfma_h<NT, MODE, TH, OCC, false, SQ>), dim3(a.tiles_x, a.tiles_y, groups * G * a.zdiv), dim3(256), lds, c.stream, a);
+    plan_inst("k_conv_mfma_h<%d, %d, %d, %d, false, %s> ksplit=%d", NT, MODE, TH, OCC, SQ ? "true" : "false", a.ksplit);
     return OG_OK;
 }
 
@@ -878,8 +898,10 @@ int launch_conv_p(const LaunchCtx& c, const ConvArgs& a, int n_ntiles) {
     const int grid = (n_items + rounds - 1) / rounds;  // <= slots, balanced: every workgroup gets rounds or rounds-1 items
     if (a.ksplit > 1) plan_need((long long)n_items * 4 * (((TH / 2) / (4 / NT)) * 16 * 64) * 4, 0);
     OG_LAUNCH((k_conv_mfma_p<NT, MODE, TH, TPS>), dim3(grid), dim3(256), lds, c.stream, a, n_items);
+    plan_inst("k_conv_mfma_p<%d, %d, %d, %d> ksplit=%d", NT, MODE, TH, TPS, a.ksplit);
     if (a.ksplit > 1) {
         OG_LAUNCH((k_splitk_epilogue<NT, MODE, TH>), dim3(a.n_spatial * n_ntiles), dim3(256), 4 * 5120, c.stream, a);
+        plan_inst("k_splitk_epilogue<%d, %d, %d>", NT, MODE, TH);
     }
     return OG_OK;
 }
@@ -1205,6 +1227,7 @@ int launch_conv(og_unet* h, const ConvLayer& L, int B, const Act& in, int in_off
                 } else {
                     rc = (wb == 1) ? launch_conv_wino_w<1>(ctx, a, L.Cout_p / 32) : launch_conv_wino_w<2>(ctx, a, L.Cout_p / 32);
                 }
+                if (rc == OG_OK) plan_inst(wb == 4 ? "k_conv_wino_wp nt=%d" : wb == 1 ? "k_conv_wino_w<1> nt=%d" : "k_conv_wino_w<2> nt=%d", L.NT);   // nt: the layer's canonical form (its weight pack)
                 prof_end(h);
                 return rc;
             }
@@ -2147,6 +2170,7 @@ int og_unet_set_option(og_unet* h, const char* name, int value) {
     else if (n == "fuse_head" && (value == 0 || value == 1)) slot = &h->fuse_head;
     else if (n == "fuse_first" && (value == 0 || value == 1)) slot = &h->fuse_first;
     else if (n == "keep_taps" && (value == 0 || value == 1)) slot = &h->keep_taps;
+    else if (n == "entry_f32" && (value == 0 || value == 1)) slot = &h->entry_f32;
     else if (n == "dual" && (value == 0 || value == 1)) slot = &h->dual;
     else if (n == "lanes" && value >= 0 && value <= kMaxLanes) slot = &h->n_lanes;
     else if (n == "stream" && (value == 0 || value == 1)) slot = &h->stream_host;
@@ -2796,8 +2820,9 @@ int og_unet_profile(og_unet* h, const uint8_t* gray_dev, int B, int H, int W, in
         h->prof = &tr;
         HIPCHK(hipMemsetAsync(h->stage, 0, (size_t)B * 4, h->stream));
         pick_chain_form(h, B, H, W);
-        const bool ff = can_fuse_first(h, KIND_U8, B, H, W);
-        rc = ff ? enqueue_first_fused(h, gray_dev, B, H, W) : enqueue_first(h, KIND_U8, gray_dev, B, H, W);
+        const int kind = h->entry_f32 ? KIND_F32 : KIND_U8;
+        const bool ff = can_fuse_first(h, kind, B, H, W);
+        rc = ff ? enqueue_first_fused(h, gray_dev, B, H, W) : enqueue_first(h, kind, gray_dev, B, H, W);
         const bool fuse = can_fuse_head(h);
         if (!rc) rc = enqueue_body(h, B, fuse, ff);
         if (!rc)
@@ -2910,8 +2935,9 @@ int og_unet_plan(const int* features, int n_levels, int B, int H, int W, int lan
         g_plan = &plan;
         // the product's chain for one micro-batch of u8 frames with areas wanted (run_chunk without the hipGraph plumbing)
         pick_chain_form(h, B, H, W);
-        const bool ff = can_fuse_first(h, KIND_U8, B, H, W), fuse = can_fuse_head(h);
-        rc = ff ? enqueue_first_fused(h, (const uint8_t*)4096, B, H, W) : enqueue_first(h, KIND_U8, (const void*)4096, B, H, W);
+        const int kind = h->entry_f32 ? KIND_F32 : KIND_U8;   // ("entry_f32" 1: the first launch of og_unet_forward_f32's chain)
+        const bool ff = can_fuse_first(h, kind, B, H, W), fuse = can_fuse_head(h);
+        rc = ff ? enqueue_first_fused(h, (const uint8_t*)4096, B, H, W) : enqueue_first(h, kind, (const void*)4096, B, H, W);
         if (!rc) rc = enqueue_body(h, B, fuse, ff);
         if (!rc) rc = fuse ? enqueue_last_with_head(h, B, 0.5f, nullptr, nullptr, (int32_t*)4096, nullptr)
                            : enqueue_head(h, B, H, W, 0.5f, nullptr, nullptr, (int32_t*)4096, nullptr);

@@ -73,6 +73,10 @@ __device__ __forceinline__ og_i32x4 og_make_rsrc(const void* base, unsigned byte
     return r;
 }
 constexpr unsigned OG_OOB = 0x80000000u;  // a lane offset no buffer of < 2 GiB contains
+// (glds16b, glds16b_m0 and glds16b_m0_masked read rsrc / soff SGPRs from inline asm with 1-3 wait states in front of the load: the
+//  "VALU writes an SGPR, VMEM reads it: 5 wait states" hazard of og_buffer_store16 applies to them too if hipcc ever restores those
+//  SGPRs by v_readlane / v_readfirstlane directly in front of the block.  The shipped ISA has no such sequence; the hazard recognizer
+//  does not look inside inline asm, so nothing but the layer-parity matrix would notice.)
 __device__ __forceinline__ void glds16b(unsigned voff, og_i32x4 rsrc, unsigned soff, unsigned lds_wave_base) {
     unsigned keep;
     asm volatile(
@@ -556,12 +560,18 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t og_rsrc(const void* base, unsi
 // hipcc's hazard recognizer waives it for stores that use an SGPR soffset (GCNHazardRecognizer::createsVALUHazard), which
 // is exactly this store -- so the nop has to be ours.  Root cause of round 1's "non-repeatable wrong lanes"
 // (profiles/r02_epilogue_fence_audit.md); tests/test_isa_audit.py scans the shipped ISA for the pattern.
+// The FIVE WAIT STATES in front of it are the second GFX9 hazard an inline-asm store is alone with: "VALU writes an SGPR, VMEM
+// reads that SGPR: 5 wait states".  hipcc's hazard recognizer does not look inside inline asm, so where it restores the resource
+// descriptor from spilled SGPRs (v_readlane_b32 s40..s43 directly in front of the asm block: k_conv_mfma_p<1, 0, 16, 9>, whose
+// SGPRs spill) the store read a stale descriptor and was dropped -- the first 16-B store of a wave's first sub-tile and its pooled
+// tile, on ~87 % of the waves: downs.0.b kept the previous call's values there (found by the layer-parity row
+// persistent-tile16-tps9-96x160).  k_conv_mfma_p<1, 0, 16, 3> had the same sequence and passed by luck.
 #ifndef OG_STORE_NOP
 #define OG_STORE_NOP 1   // -DOG_STORE_NOP=0: audit build that reproduces the failure
 #endif
 __device__ __forceinline__ void og_buffer_store16(f32x4 v, __amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
 #if OG_STORE_NOP
-    asm volatile("buffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 0" : : "v"(v), "v"(voff), "s"(rs), "s"(soff) : "memory");
+    asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 0" : : "v"(v), "v"(voff), "s"(rs), "s"(soff) : "memory");
 #else
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(og_u32x4, v), rs, voff, soff, 0);
 #endif
@@ -4549,6 +4559,7 @@ __global__ __launch_bounds__(256) void k_unletterbox_paste(const uint8_t* __rest
 // Frames are packed back to back in one buffer; frame b starts at offsets[b] and is shapes[b] = {H, W}.
 // geom[b] = {pad_top, pad_left, content_h, content_w} (host: Python round()).
 // =======================================================================================
+// (k_canvas_letterbox<3>: hipcc contracts f into one v_fma_f64; against geometry._linear_taps in exact arithmetic over every length pair a letterbox to 224 / 256 / 320 / 512 / 640 makes of frames up to 1600 a side, 697 079 pairs, floor / fraction differ at 673, always at an integer position where (k, 0) and (k - 1, 2048) weigh the same pixel: no output pixel changes)
 __device__ __forceinline__ void og_linear_tap(int d, int src_len, int dst_len, int& i0, int& i1, int& a0, int& a1) {
     const double f = ((double)d + 0.5) * ((double)src_len / (double)dst_len) - 0.5;
     int k = (int)floor(f);

@@ -355,6 +355,8 @@ class UNet:
     def set_option(self, name: str, value: int) -> None:
         self._require()
         check(lib().og_unet_set_option(self._h, name.encode(), int(value)), f"og_unet_set_option({name})")
+        if name == "entry_f32":
+            self._entry_f32 = bool(value)
 
     def timer_start(self) -> None:
         check(lib().og_timer_start(self._h), "og_timer_start")
@@ -365,8 +367,15 @@ class UNet:
         return float(ms.value)
 
     def profile(self, gray_dev, B: int, H: int, W: int, reps: int = 5) -> list[dict]:
-        """Per-launch HIP-event timings of one chain (bench.py's roofline leg)."""
+        """Per-launch HIP-event timings of one chain (bench.py's roofline leg).  ``gray_dev``: B x H x W u8 frames on the device;
+        with the diagnostic option ``entry_f32`` set, B x H x W float32 (the chain of the NCHW-float entry point)."""
         self._require()
+        if getattr(self, "_entry_f32", False):    # the library then reads 4 bytes per pixel: hold the tensor to that extent
+            ok = (hasattr(gray_dev, "dtype") and str(gray_dev.dtype) == "torch.float32" and gray_dev.is_contiguous()
+                  and gray_dev.numel() >= B * H * W)
+            if not ok:
+                raise OpenGlottalHipError(f"profile with option entry_f32 set expects a contiguous float32 tensor of at least "
+                                          f"{B}x{H}x{W} elements, got {getattr(gray_dev, 'dtype', type(gray_dev))}")
         n_max = 128
         layers = C.create_string_buffer(64 * n_max)
         kernels = C.create_string_buffer(64 * n_max)

@@ -507,52 +507,227 @@ def special_frames(H: int, W: int, seed: int = 0) -> dict:
 FULL = (32, 64, 128, 256)
 
 
-def _case(cid, feats, H, W, B, options=None, families=(), form="wino", nread=2, fused_first=False, fused_head=False, prof=()):
+# Every instantiation the U-Net chain can launch at precision 0 and 1, by a short label -> (its text in og_unet_plan as
+# ``plan_instantiations`` reads it, its label in UNet.profile (None: it runs inside the launch before it), a smallest net / frame
+# shape / micro-batch / option set that reaches it: an edge shape wherever the planner allows one).  tests/test_layer_ref.py closes
+# the list on the CPU: an option sweep finds no instantiation outside it, every entry is reached by its own option set, and the
+# non-f16 rows of GPU_CASES together with F32_ENTRY_CASES run every one of them, on shapes with edges wherever one can be chosen.
+F32_KERNELS = {
+    "convt_w": ("k_convt_w", "k_convt_w<1,1,8>", ((4, 8, 16, 32), 16, 16, 4, "keep_taps=1")),
+    "epilogue<1,0,8>": ("k_splitk_epilogue<1, 0, 8>", None, ((33, 66), 32, 64, 8, "keep_taps=1,wino=0,splitk=1,splitk_fused=0")),
+    "epilogue<2,0,8>": ("k_splitk_epilogue<2, 0, 8>", None, ((33, 66), 32, 64, 8, "keep_taps=1,wino=0,splitk=1,splitk_fused=0")),
+    "epilogue<2,1,8>": ("k_splitk_epilogue<2, 1, 8>", None, ((33, 66), 32, 64, 8, "keep_taps=1,wino=0,splitk=1,splitk_fused=0")),
+    "first<f32,split>": ("k_conv_first<float, true>", "k_conv_first<f32>", ((33, 66), 64, 64, 6, "keep_taps=1,precision=1,entry_f32=1")),
+    "first<f32>": ("k_conv_first<float>", "k_conv_first<f32>", ((33, 66), 64, 64, 6, "keep_taps=1,precision=0,entry_f32=1")),
+    "first<u8,split>": ("k_conv_first<uint8_t, true>", "k_conv_first<u8>", ((4, 8, 16, 32), 16, 16, 4, "keep_taps=1,precision=1")),
+    "first<u8>": ("k_conv_first<uint8_t>", "k_conv_first<u8>", ((4, 8, 16, 32), 16, 16, 4, "keep_taps=1")),
+    "h<1,0,16,2>": ("k_conv_mfma_h<1, 0, 16, 2, false, false>", "k_conv_mfma_h<1,0,16>", ((4, 8, 16, 32), 16, 16, 4, "keep_taps=1,precision=1")),
+    "h<1,0,8,3,FIRST>": ("k_conv_mfma_h<1, 0, 8, 3, true>", "k_conv_mfma_h<1,0,8,FIRST>", ((32, 64), 96, 160, 16, "keep_taps=0,precision=1")),
+    "h<1,0,8,3>": ("k_conv_mfma_h<1, 0, 8, 3, false, false>", "k_conv_mfma_h<1,0,8>", ((4, 8, 16, 32), 16, 16, 4, "keep_taps=1,precision=1")),
+    "h<1,0,8,3>+splitK": ("k_conv_mfma_h<1, 0, 8, 3, false, false>+splitK", "k_conv_mfma_h<1,0,8>", ((32, 64), 96, 160, 1, "keep_taps=1,precision=1,splitk=1")),
+    "h<2,0,16,2,SQ>": ("k_conv_mfma_h<2, 0, 16, 2, false, true>", "k_conv_mfma_h<2,0,16>", ((33, 66), 32, 64, 4, "keep_taps=1,precision=1")),
+    "h<2,0,16,2>": ("k_conv_mfma_h<2, 0, 16, 2, false, false>", "k_conv_mfma_h<2,0,16>", ((32, 64), 96, 160, 4, "keep_taps=1,precision=1,h_square=0")),
+    "h<2,0,8,3>": ("k_conv_mfma_h<2, 0, 8, 3, false, false>", "k_conv_mfma_h<2,0,8>", ((4, 8, 16, 32), 16, 16, 4, "keep_taps=1,precision=1")),
+    "h<2,0,8,3>+splitK": ("k_conv_mfma_h<2, 0, 8, 3, false, false>+splitK", "k_conv_mfma_h<2,0,8>", ((32, 64), 96, 160, 1, "keep_taps=1,precision=1,splitk=1")),
+    "h<2,1,8,3>": ("k_conv_mfma_h<2, 1, 8, 3, false, false>", "k_conv_mfma_h<2,1,8>", ((4, 8, 16, 32), 16, 16, 4, "keep_taps=1,precision=1")),
+    "h<2,1,8,3>+splitK": ("k_conv_mfma_h<2, 1, 8, 3, false, false>+splitK", "k_conv_mfma_h<2,1,8>", ((32, 64), 96, 160, 1, "keep_taps=1,precision=1,splitk=1")),
+    "head": ("k_head<false>", "k_head", ((33, 66), 32, 64, 1, "keep_taps=1,wino=0,splitk=1,splitk_nt1=0")),
+    "head<split>": ("k_head<true>", "k_head", ((4, 8, 16, 32), 16, 16, 4, "keep_taps=1,precision=1")),
+    "mfma<1,0,8>": ("k_conv_mfma<1, 0, 8>", "k_conv_mfma<1,0,8>", ((32, 64), 96, 160, 4, "keep_taps=1,wino=0,conv_impl=0")),
+    "mfma<2,0,8>": ("k_conv_mfma<2, 0, 8>", "k_conv_mfma<2,0,8>", ((32, 64), 96, 160, 4, "keep_taps=1,wino=0,conv_impl=0")),
+    "mfma<2,1,8>": ("k_conv_mfma<2, 1, 8>", "k_conv_mfma<2,1,8>", ((32, 64), 96, 160, 4, "keep_taps=1,wino=0,conv_impl=0")),
+    "o<1,0,16,2>": ("k_conv_mfma_o<1, 0, 16, 2, false, false>", "k_conv_mfma_o<1,0,16>", ((33, 66), 32, 64, 64, "keep_taps=1,wino=0,tile_h=16")),
+    "o<1,0,8,3,FIRST>": ("k_conv_mfma_o<1, 0, 8, 3, true>", "k_conv_mfma_o<1,0,8,FIRST>", ((32, 64), 96, 160, 16, "keep_taps=0,wino=0")),
+    "o<1,0,8,3>": ("k_conv_mfma_o<1, 0, 8, 3, false, false>", "k_conv_mfma_o<1,0,8>", ((33, 66), 32, 64, 64, "keep_taps=1,wino=0,tile_h=16")),
+    "o<1,0,8,3>+splitK": ("k_conv_mfma_o<1, 0, 8, 3, false, false>+splitK", "k_conv_mfma_o<1,0,8>+splitK", ((33, 66), 32, 64, 8, "keep_taps=1,wino=0,splitk=1,splitk_fused=0")),
+    "o<1,0,8,3>+splitK+reduce": ("k_conv_mfma_o<1, 0, 8, 3, false, false>+splitK+reduce", "k_conv_mfma_o<1,0,8>+splitK", ((33, 66), 32, 64, 1, "keep_taps=1,wino=0,splitk=1,splitk_nt1=0")),
+    "o<1,0,8,4>": ("k_conv_mfma_o<1, 0, 8, 4, false, false>", "k_conv_mfma_o<1,0,8>", ((32, 64), 96, 160, 16, "keep_taps=1,wino=0,conv_impl=3")),
+    "o<2,0,16,2>": ("k_conv_mfma_o<2, 0, 16, 2, false, false>", "k_conv_mfma_o<2,0,16>", ((33, 66), 32, 64, 64, "keep_taps=1,wino=0,tile_h=16")),
+    "o<2,0,8,3>": ("k_conv_mfma_o<2, 0, 8, 3, false, false>", "k_conv_mfma_o<2,0,8>", ((32, 64), 96, 160, 16, "keep_taps=1")),
+    "o<2,0,8,3>+splitK": ("k_conv_mfma_o<2, 0, 8, 3, false, false>+splitK", "k_conv_mfma_o<2,0,8>+splitK", ((33, 66), 32, 64, 8, "keep_taps=1,wino=0,splitk=1,splitk_fused=0")),
+    "o<2,0,8,3>+splitK+reduce": ("k_conv_mfma_o<2, 0, 8, 3, false, false>+splitK+reduce", "k_conv_mfma_o<2,0,8>+splitK", ((33, 66), 32, 64, 1, "keep_taps=1,wino=0,splitk=1,splitk_nt1=0")),
+    "o<2,0,8,4>": ("k_conv_mfma_o<2, 0, 8, 4, false, false>", "k_conv_mfma_o<2,0,8>", ((32, 64), 96, 160, 16, "keep_taps=1,wino=0,conv_impl=3")),
+    "o<2,1,8,3>": ("k_conv_mfma_o<2, 1, 8, 3, false, false>", "k_conv_mfma_o<2,1,8>", ((40, 80), 64, 64, 8, "keep_taps=1")),
+    "o<2,1,8,3>+splitK": ("k_conv_mfma_o<2, 1, 8, 3, false, false>+splitK", "k_conv_mfma_o<2,1,8>+splitK", ((33, 66), 32, 64, 8, "keep_taps=1,wino=0,splitk=1,splitk_fused=0")),
+    "o<2,1,8,3>+splitK+reduce": ("k_conv_mfma_o<2, 1, 8, 3, false, false>+splitK+reduce", "k_conv_mfma_o<2,1,8>+splitK", ((33, 66), 32, 64, 1, "keep_taps=1,wino=0,splitk=1,splitk_nt1=0")),
+    "p<1,0,16,3>": ("k_conv_mfma_p<1, 0, 16, 3>", "k_conv_mfma_p<1,0,16,3>", ((32, 64), 96, 160, 4, "keep_taps=1,wino=0,conv_impl=1,tile_h=16")),
+    "p<1,0,16,9>": ("k_conv_mfma_p<1, 0, 16, 9>", "k_conv_mfma_p<1,0,16,9>", ((32, 64), 96, 160, 4, "keep_taps=1,wino=0,conv_impl=1,tile_h=16,tps_nt1=9,tps_nt2=3")),
+    "p<1,0,8,1>": ("k_conv_mfma_p<1, 0, 8, 1>", "k_conv_mfma_p<1,0,8,1>", ((33, 66), 32, 64, 4, "keep_taps=1,wino=0,conv_impl=1,tps_nt1=1")),
+    "p<1,0,8,1>+splitK": ("k_conv_mfma_p<1, 0, 8, 1>+splitK", "k_conv_mfma_p<1,0,8,1>", ((33, 66), 32, 64, 2, "keep_taps=1,wino=0,conv_impl=1,splitk=1,tps_nt1=1")),
+    "p<1,0,8,3>": ("k_conv_mfma_p<1, 0, 8, 3>", "k_conv_mfma_p<1,0,8,3>", ((4, 8, 16, 32), 16, 16, 4, "keep_taps=1")),
+    "p<1,0,8,3>+splitK": ("k_conv_mfma_p<1, 0, 8, 3>+splitK", "k_conv_mfma_p<1,0,8,3>", ((32, 64), 96, 160, 1, "keep_taps=1,wino=0,conv_impl=1,splitk=1")),
+    "p<1,0,8,9>": ("k_conv_mfma_p<1, 0, 8, 9>", "k_conv_mfma_p<1,0,8,9>", ((33, 66), 32, 64, 4, "keep_taps=1,wino=0,conv_impl=1,tps_nt1=9,tps_nt2=3")),
+    "p<1,0,8,9>+splitK": ("k_conv_mfma_p<1, 0, 8, 9>+splitK", "k_conv_mfma_p<1,0,8,9>", ((33, 66), 32, 64, 2, "keep_taps=1,wino=0,conv_impl=1,splitk=1,tps_nt1=9,tps_nt2=3")),
+    "p<2,0,16,1>": ("k_conv_mfma_p<2, 0, 16, 1>", "k_conv_mfma_p<2,0,16,1>", ((32, 64), 96, 160, 4, "keep_taps=1,wino=0,conv_impl=1,tile_h=16")),
+    "p<2,0,16,3>": ("k_conv_mfma_p<2, 0, 16, 3>", "k_conv_mfma_p<2,0,16,3>", ((32, 64), 96, 160, 4, "keep_taps=1,wino=0,conv_impl=1,tile_h=16,tps_nt1=9,tps_nt2=3")),
+    "p<2,0,8,1>": ("k_conv_mfma_p<2, 0, 8, 1>", "k_conv_mfma_p<2,0,8,1>", ((4, 8, 16, 32), 16, 16, 4, "keep_taps=1")),
+    "p<2,0,8,1>+splitK": ("k_conv_mfma_p<2, 0, 8, 1>+splitK", "k_conv_mfma_p<2,0,8,1>", ((32, 64), 96, 160, 1, "keep_taps=1,wino=0,conv_impl=1,splitk=1")),
+    "p<2,0,8,3>": ("k_conv_mfma_p<2, 0, 8, 3>", "k_conv_mfma_p<2,0,8,3>", ((33, 66), 32, 64, 4, "keep_taps=1,wino=0,conv_impl=1,tps_nt1=9,tps_nt2=3")),
+    "p<2,0,8,3>+splitK": ("k_conv_mfma_p<2, 0, 8, 3>+splitK", "k_conv_mfma_p<2,0,8,3>", ((33, 66), 32, 64, 2, "keep_taps=1,wino=0,conv_impl=1,splitk=1,tps_nt1=9,tps_nt2=3")),
+    "p<2,1,8,1>": ("k_conv_mfma_p<2, 1, 8, 1>", "k_conv_mfma_p<2,1,8,1>", ((33, 66), 32, 64, 4, "keep_taps=1,wino=0,conv_impl=1,tps_nt1=9,tps_nt2=3")),
+    "p<2,1,8,1>+splitK": ("k_conv_mfma_p<2, 1, 8, 1>+splitK", "k_conv_mfma_p<2,1,8,1>", ((32, 64), 96, 160, 1, "keep_taps=1,wino=0,conv_impl=1,splitk=1")),
+    "ps<1,1>": ("k_conv_wino_ps<1, 1>", "k_conv_wino_ps<1,1>", ((32, 64), 64, 64, 1, "keep_taps=1,wino_w=0,wino_ps=4")),
+    "ps<1,2>": ("k_conv_wino_ps<1, 2>", "k_conv_wino_ps<1,2>", ((32, 64), 64, 64, 1, "keep_taps=1,wino_w=0,wino_ps=3")),
+    "ps<1,4>": ("k_conv_wino_ps<1, 4>", "k_conv_wino_ps<1,4>", ((32, 64), 64, 64, 1, "keep_taps=1,wino_w=0,wino_ps=2")),
+    "ps<2,1>": ("k_conv_wino_ps<2, 1>", "k_conv_wino_ps<2,1>", ((32, 64), 64, 64, 1, "keep_taps=1,wino_w=0,wino_ps=4")),
+    "ps<2,2>": ("k_conv_wino_ps<2, 2>", "k_conv_wino_ps<2,2>", ((32, 64), 64, 64, 1, "keep_taps=1,wino_w=0,wino_ps=3")),
+    "ps<2,4>": ("k_conv_wino_ps<2, 4>", "k_conv_wino_ps<2,4>", ((32, 64), 64, 64, 1, "keep_taps=1,wino_w=0,wino_ps=2")),
+    "w<1> nt=1": ("k_conv_wino_w<1> nt=1", "k_conv_wino_w<1,1>", ((3, 6, 12, 24, 48), 64, 96, 4, "keep_taps=1")),
+    "w<1> nt=2": ("k_conv_wino_w<1> nt=2", "k_conv_wino_w<2,1>", ((33, 66), 32, 64, 4, "keep_taps=1")),
+    "w<2> nt=1": ("k_conv_wino_w<2> nt=1", "k_conv_wino_w<1,2>", ((32, 64), 64, 64, 1, "keep_taps=1,wino_w=3")),
+    "w<2> nt=2": ("k_conv_wino_w<2> nt=2", "k_conv_wino_w<2,2>", ((32, 64), 64, 64, 1, "keep_taps=1,wino_w=3")),
+    "wino<1>": ("k_conv_wino<1>", "k_conv_wino<1>", ((32, 64), 96, 160, 16, "keep_taps=1")),
+    "wino<2>": ("k_conv_wino<2>", "k_conv_wino<2>", ((32, 64), 96, 160, 16, "keep_taps=1")),
+    "wp nt=1": ("k_conv_wino_wp nt=1", "k_conv_wino_wp<1>", ((3, 6, 12, 24, 48), 64, 96, 4, "keep_taps=1")),
+    "wp nt=2": ("k_conv_wino_wp nt=2", "k_conv_wino_wp<2>", ((33, 66), 32, 64, 1, "keep_taps=1")),
+}
+
+# instantiations the planner chooses at the full-width net on 256 x 256 only -> the rule in og_api.hip that excludes them elsewhere
+EDGE_EXEMPT = {}
+
+
+def is_edge_case(case) -> bool:
+    """A row whose tiles have borders, whose channels are padded or whose maps are small: anything but the full-width net at 256 x 256."""
+    return not (tuple(case["feats"]) == FULL and case["H"] == 256 and case["W"] == 256)
+
+
+def _case(cid, feats, H, W, B, options=None, families=(), form="wino", nread=2, fused_first=False, fused_head=False, prof=(), kernels=()):
     opts = {"keep_taps": 1}
     opts.update(options or {})
     if not prof:   # every kernel family of the plan check is asserted through UNet.profile as well
         prof = [f for f in families if f.startswith("k_") and f not in ("k_splitk_epilogue", "k_sum_counts")]
+    # kernels (non-f16 rows): the row's plan by instantiation, EXACTLY (F32_KERNELS labels); prof_inst: their UNet.profile labels
+    prof_inst = sorted({F32_KERNELS[k][1] for k in kernels} - {None})
     return dict(id=cid, feats=tuple(feats), H=H, W=W, B=B, options=opts, families=tuple(families), form=form, nread=min(nread, B),
-                fused_first=fused_first, fused_head=fused_head, prof=tuple(prof))
+                fused_first=fused_first, fused_head=fused_head, prof=tuple(prof), kernels=tuple(kernels), prof_inst=tuple(prof_inst))
 
 
 # families: what og_unet_plan must list for the case (``plan_families``); prof: what UNet.profile must list (``profile_families``)
 GPU_CASES = [
-    _case("default-64", FULL, 256, 256, 64, {}, ["k_conv_wino", "k_conv_mfma_o"], prof=["k_conv_wino", "k_conv_mfma_o"]),
+    _case("default-64", FULL, 256, 256, 64, {}, ["k_conv_wino", "k_conv_mfma_o"], prof=["k_conv_wino", "k_conv_mfma_o"],
+          kernels=["first<u8>", "o<2,1,8,3>", "wino<1>", "wino<2>"]),
     _case("default-1", FULL, 256, 256, 1, {}, ["k_conv_wino_w", "k_conv_wino_wp", "k_convt_w"], nread=1,
-          prof=["k_conv_wino_w", "k_conv_wino_wp", "k_convt_w"]),
-    _case("position-split-1", FULL, 256, 256, 1, {"wino_w": 0}, ["k_conv_wino_ps"], nread=1, prof=["k_conv_wino_ps"]),
-    _case("direct-64", FULL, 256, 256, 64, {"wino": 0}, ["k_conv_mfma_o"], form="direct", prof=["k_conv_mfma_o"]),
+          prof=["k_conv_wino_w", "k_conv_wino_wp", "k_convt_w"],
+          kernels=["convt_w", "first<u8>", "o<2,1,8,3>", "w<1> nt=2", "w<2> nt=1", "wp nt=2"]),
+    _case("position-split-1", FULL, 256, 256, 1, {"wino_w": 0}, ["k_conv_wino_ps"], nread=1, prof=["k_conv_wino_ps"],
+          kernels=["convt_w", "first<u8>", "o<2,1,8,3>", "ps<2,1>", "ps<2,2>", "ps<2,4>", "wino<1>"]),
+    _case("direct-64", FULL, 256, 256, 64, {"wino": 0}, ["k_conv_mfma_o"], form="direct", prof=["k_conv_mfma_o"],
+          kernels=["first<u8>", "o<1,0,8,3>", "o<2,0,16,2>", "o<2,0,8,3>", "o<2,1,8,3>"]),
     _case("direct-impl0-2", FULL, 256, 256, 2, {"wino": 0, "conv_impl": 0}, ["k_conv_mfma", "k_head"], form="direct",
-          prof=["k_conv_mfma", "k_head"]),
-    _case("direct-impl1-2", FULL, 256, 256, 2, {"wino": 0, "conv_impl": 1}, ["k_conv_mfma_p"], form="direct", prof=["k_conv_mfma_p"]),
+          prof=["k_conv_mfma", "k_head"],
+          kernels=["first<u8>", "head", "mfma<1,0,8>", "mfma<2,0,8>", "mfma<2,1,8>"]),
+    _case("direct-impl1-2", FULL, 256, 256, 2, {"wino": 0, "conv_impl": 1}, ["k_conv_mfma_p"], form="direct", prof=["k_conv_mfma_p"],
+          kernels=["first<u8>", "p<1,0,8,3>", "p<2,0,8,1>", "p<2,1,8,1>"]),
     _case("splitk-fused-1", FULL, 256, 256, 1, {"wino": 0, "splitk": 1}, ["k_conv_mfma_o", "splitk-parts", "splitk-fused-reduce"], form="direct", nread=1,
-          prof=["splitK"]),
+          prof=["splitK"],
+          kernels=["first<u8>", "o<1,0,8,3>", "o<1,0,8,3>+splitK+reduce", "o<2,0,8,3>+splitK+reduce", "o<2,1,8,3>", "o<2,1,8,3>+splitK+reduce"]),
     _case("splitk-fused-2", FULL, 256, 256, 2, {"wino": 0, "splitk": 1}, ["k_conv_mfma_o", "splitk-parts", "splitk-fused-reduce"], form="direct",
-          prof=["splitK"]),
+          prof=["splitK"],
+          kernels=["first<u8>", "o<1,0,8,3>", "o<1,0,8,3>+splitK+reduce", "o<2,0,8,3>", "o<2,0,8,3>+splitK+reduce", "o<2,1,8,3>", "o<2,1,8,3>+splitK+reduce"]),
     _case("splitk-epilogue-2", FULL, 256, 256, 2, {"wino": 0, "splitk": 1, "splitk_fused": 0}, ["splitk-parts", "k_splitk_epilogue"], form="direct",
-          prof=["splitK"]),
+          prof=["splitK"],
+          kernels=["epilogue<1,0,8>", "epilogue<2,0,8>", "epilogue<2,1,8>", "first<u8>", "o<1,0,8,3>", "o<1,0,8,3>+splitK", "o<2,0,8,3>", "o<2,0,8,3>+splitK", "o<2,1,8,3>", "o<2,1,8,3>+splitK"]),
     _case("splitk-nt1-0-steps9-1", FULL, 256, 256, 1, {"wino": 0, "splitk": 1, "splitk_nt1": 0, "splitk_min_steps": 9},
-          ["splitk-parts", "splitk-fused-reduce"], form="direct", nread=1, prof=["splitK"]),
-    _case("split-precision-64", FULL, 256, 256, 64, {"precision": 1}, ["k_conv_mfma_h"], form="split", prof=["k_conv_mfma_h"]),
-    _case("split-precision-1", FULL, 256, 256, 1, {"precision": 1}, ["k_conv_mfma_h"], form="split", nread=1, prof=["k_conv_mfma_h"]),
+          ["splitk-parts", "splitk-fused-reduce"], form="direct", nread=1, prof=["splitK"],
+          kernels=["first<u8>", "o<1,0,8,3>", "o<2,0,8,3>+splitK+reduce", "o<2,1,8,3>", "o<2,1,8,3>+splitK+reduce", "p<2,0,8,1>"]),
+    _case("split-precision-64", FULL, 256, 256, 64, {"precision": 1}, ["k_conv_mfma_h"], form="split", prof=["k_conv_mfma_h"],
+          kernels=["first<u8,split>", "h<1,0,16,2>", "h<2,0,16,2,SQ>", "h<2,1,8,3>", "head<split>"]),
+    _case("split-precision-1", FULL, 256, 256, 1, {"precision": 1}, ["k_conv_mfma_h"], form="split", nread=1, prof=["k_conv_mfma_h"],
+          kernels=["first<u8,split>", "h<1,0,16,2>", "h<2,0,16,2,SQ>", "h<2,1,8,3>", "head<split>"]),
     _case("split-precision-splitk-1", FULL, 256, 256, 1, {"precision": 1, "splitk": 1}, ["k_conv_mfma_h", "splitk-parts"],
-          form="split", nread=1, prof=["k_conv_mfma_h"]),
+          form="split", nread=1, prof=["k_conv_mfma_h"],
+          kernels=["first<u8,split>", "h<1,0,16,2>", "h<2,0,16,2,SQ>", "h<2,0,8,3>+splitK", "h<2,1,8,3>", "h<2,1,8,3>+splitK", "head<split>"]),
     _case("fused-first-and-head-64", FULL, 256, 256, 64, {"wino": 0, "keep_taps": 0}, ["first-fused", "k_sum_counts"], form="direct",
-          fused_first=True, fused_head=True, prof=["first-fused"]),
+          fused_first=True, fused_head=True, prof=["first-fused"],
+          kernels=["o<1,0,8,3,FIRST>", "o<1,0,8,3>", "o<2,0,16,2>", "o<2,0,8,3>", "o<2,1,8,3>"]),
     _case("fused-head-wino-64", FULL, 256, 256, 64, {"keep_taps": 0}, ["k_conv_wino", "k_sum_counts"], fused_head=True,
-          prof=["k_conv_wino"]),
-    _case("unfused-head-2", FULL, 256, 256, 2, {"fuse_head": 0}, ["k_head"], prof=["k_head"]),
-    _case("tiles-128x256", (32, 64), 128, 256, 64, {}, ["k_conv_wino"], prof=["k_conv_wino"]),
-    _case("tiles-96x160", (32, 64), 96, 160, 16, {}, ["k_conv_wino"], nread=4, prof=["k_conv_wino"]),
-    _case("tiles-96x160-direct", (32, 64), 96, 160, 16, {"wino": 0}, ["k_conv_mfma_o"], form="direct", nread=4),
-    _case("padded-40x80-64x64", (40, 80), 64, 64, 8, {}, ["k_conv_wino_w", "k_head"], nread=6),
-    _case("padded-33x66-32x64", (33, 66), 32, 64, 4, {}, ["k_conv_wino_w", "k_conv_mfma_p", "k_head"], nread=4),
-    _case("padded-33x66-32x64-direct", (33, 66), 32, 64, 4, {"wino": 0}, ["k_conv_mfma_p"], form="direct", nread=4),
-    _case("bottleneck-1x1-16x16", (4, 8, 16, 32), 16, 16, 4, {}, ["k_conv_mfma_p", "k_convt_w"], nread=4),
-    _case("maps-1x16-16x256", (4, 8, 16, 32), 16, 256, 2, {}, ["k_conv_mfma_p"], nread=2),
-    _case("five-levels-64x96", (3, 6, 12, 24, 48), 64, 96, 4, {}, ["k_conv_wino_w", "k_conv_wino_wp", "k_conv_mfma_p"], nread=4),
-    _case("large-512x512", (32, 64), 512, 512, 8, {}, ["k_conv_wino"], nread=1),
+          prof=["k_conv_wino"],
+          kernels=["first<u8>", "o<2,1,8,3>", "wino<1>", "wino<2>"]),
+    _case("unfused-head-2", FULL, 256, 256, 2, {"fuse_head": 0}, ["k_head"], prof=["k_head"],
+          kernels=["convt_w", "first<u8>", "head", "o<2,1,8,3>", "w<1> nt=2", "w<2> nt=2", "wino<1>", "wp nt=2"]),
+    _case("tiles-128x256", (32, 64), 128, 256, 64, {}, ["k_conv_wino"], prof=["k_conv_wino"],
+          kernels=["first<u8>", "o<2,1,8,3>", "wino<1>", "wino<2>"]),
+    _case("tiles-96x160", (32, 64), 96, 160, 16, {}, ["k_conv_wino"], nread=4, prof=["k_conv_wino"],
+          kernels=["first<u8>", "o<2,0,8,3>", "o<2,1,8,3>", "wino<1>", "wino<2>"]),
+    _case("tiles-96x160-direct", (32, 64), 96, 160, 16, {"wino": 0}, ["k_conv_mfma_o"], form="direct", nread=4,
+          kernels=["first<u8>", "o<1,0,8,3>", "o<2,0,8,3>", "o<2,1,8,3>"]),
+    _case("padded-40x80-64x64", (40, 80), 64, 64, 8, {}, ["k_conv_wino_w", "k_head"], nread=6,
+          kernels=["convt_w", "first<u8>", "head", "o<2,1,8,3>", "p<1,0,8,3>", "w<1> nt=1", "w<2> nt=2"]),
+    _case("padded-33x66-32x64", (33, 66), 32, 64, 4, {}, ["k_conv_wino_w", "k_conv_mfma_p", "k_head"], nread=4,
+          kernels=["convt_w", "first<u8>", "head", "p<1,0,8,3>", "w<1> nt=2"]),
+    _case("padded-33x66-32x64-direct", (33, 66), 32, 64, 4, {"wino": 0}, ["k_conv_mfma_p"], form="direct", nread=4,
+          kernels=["convt_w", "first<u8>", "head", "p<1,0,8,3>", "p<2,0,8,1>"]),
+    _case("bottleneck-1x1-16x16", (4, 8, 16, 32), 16, 16, 4, {}, ["k_conv_mfma_p", "k_convt_w"], nread=4,
+          kernels=["convt_w", "first<u8>", "p<1,0,8,3>", "p<2,0,8,1>"]),
+    _case("maps-1x16-16x256", (4, 8, 16, 32), 16, 256, 2, {}, ["k_conv_mfma_p"], nread=2,
+          kernels=["convt_w", "first<u8>", "p<1,0,8,3>", "p<2,0,8,1>"]),
+    _case("five-levels-64x96", (3, 6, 12, 24, 48), 64, 96, 4, {}, ["k_conv_wino_w", "k_conv_wino_wp", "k_conv_mfma_p"], nread=4,
+          kernels=["convt_w", "first<u8>", "p<1,0,8,3>", "p<2,0,8,1>", "w<1> nt=1", "wp nt=1"]),
+    _case("large-512x512", (32, 64), 512, 512, 8, {}, ["k_conv_wino"], nread=1,
+          kernels=["first<u8>", "o<2,1,8,3>", "wino<1>", "wino<2>"]),
+    # every remaining instantiation of the f32 chains (F32_KERNELS), on the smallest shapes that still have edges.  Ten of these
+    # rows (REDUNDANT_FOR_COVERAGE below) are the only cover of no instantiation: they judge kernels other rows run on a second
+    # shape (padded K, 1 x 1 maps, five levels, partial tiles, forced PN), so dropping one of them fails no coverage test.
+    _case("persistent-tps9-33x66", (33, 66), 32, 64, 4, {"wino": 0, "conv_impl": 1, "tps_nt1": 9, "tps_nt2": 3}, form="direct", nread=4,
+          kernels=["first<u8>", "head", "p<1,0,8,9>", "p<2,0,8,3>", "p<2,1,8,1>"]),
+    _case("persistent-tps1-33x66", (33, 66), 32, 64, 4, {"wino": 0, "conv_impl": 1, "tps_nt1": 1}, form="direct", nread=4,
+          kernels=["first<u8>", "head", "p<1,0,8,1>", "p<2,0,8,1>", "p<2,1,8,1>"]),
+    _case("persistent-tile16-96x160", (32, 64), 96, 160, 4, {"wino": 0, "conv_impl": 1, "tile_h": 16}, form="direct", nread=4,
+          kernels=["first<u8>", "p<1,0,16,3>", "p<1,0,8,3>", "p<2,0,16,1>", "p<2,0,8,1>", "p<2,1,8,1>"]),
+    _case("persistent-tile16-tps9-96x160", (32, 64), 96, 160, 4, {"wino": 0, "conv_impl": 1, "tile_h": 16, "tps_nt1": 9, "tps_nt2": 3}, form="direct", nread=4,
+          kernels=["first<u8>", "p<1,0,16,9>", "p<1,0,8,9>", "p<2,0,16,3>", "p<2,0,8,3>", "p<2,1,8,1>"]),
+    _case("occupancy-tile16-33x66-64", (33, 66), 32, 64, 64, {"wino": 0, "tile_h": 16}, form="direct", nread=4,
+          kernels=["first<u8>", "head", "o<1,0,16,2>", "o<1,0,8,3>", "o<2,0,16,2>", "o<2,1,8,3>"]),
+    _case("occupancy-occ4-96x160", (32, 64), 96, 160, 16, {"wino": 0, "conv_impl": 3}, form="direct", nread=4,
+          kernels=["first<u8>", "o<1,0,8,4>", "o<2,0,8,4>", "o<2,1,8,3>"]),
+    _case("position-split-pn4-64x64", (32, 64), 64, 64, 1, {"wino_w": 0, "wino_ps": 2}, form="wino", nread=1,
+          kernels=["convt_w", "first<u8>", "ps<1,4>", "ps<2,4>"]),
+    _case("position-split-pn2-64x64", (32, 64), 64, 64, 1, {"wino_w": 0, "wino_ps": 3}, form="wino", nread=1,
+          kernels=["convt_w", "first<u8>", "ps<1,2>", "ps<2,2>"]),
+    _case("position-split-pn1-64x64", (32, 64), 64, 64, 1, {"wino_w": 0, "wino_ps": 4}, form="wino", nread=1,
+          kernels=["convt_w", "first<u8>", "ps<1,1>", "ps<2,1>"]),
+    _case("position-split-96x160-1", (32, 64), 96, 160, 1, {"wino_w": 0}, form="wino", nread=1,
+          kernels=["convt_w", "first<u8>", "p<2,0,8,1>", "ps<1,1>", "ps<2,1>"]),
+    _case("position-split-96x160-2", (32, 64), 96, 160, 2, {"wino_w": 0}, form="wino", nread=2,
+          kernels=["convt_w", "first<u8>", "p<2,0,8,1>", "ps<1,2>", "ps<2,1>"]),
+    _case("split-tiles-96x160", (32, 64), 96, 160, 4, {"precision": 1}, form="split", nread=4,
+          kernels=["first<u8,split>", "h<1,0,16,2>", "h<2,0,16,2,SQ>", "h<2,0,8,3>", "h<2,1,8,3>", "head<split>"]),
+    _case("split-padded-33x66-32x64", (33, 66), 32, 64, 4, {"precision": 1}, form="split", nread=4,
+          kernels=["first<u8,split>", "h<1,0,16,2>", "h<1,0,8,3>", "h<2,0,16,2,SQ>", "h<2,1,8,3>", "head<split>"]),
+    _case("split-tile-h8-96x160", (32, 64), 96, 160, 4, {"precision": 1, "tile_h": 8}, form="split", nread=4,
+          kernels=["first<u8,split>", "h<1,0,8,3>", "h<2,0,8,3>", "h<2,1,8,3>", "head<split>"]),
+    _case("split-h-square0-96x160", (32, 64), 96, 160, 4, {"precision": 1, "h_square": 0}, form="split", nread=4,
+          kernels=["first<u8,split>", "h<1,0,16,2>", "h<2,0,16,2>", "h<2,0,8,3>", "h<2,1,8,3>", "head<split>"]),
+    _case("split-bottleneck-1x1-16x16", (4, 8, 16, 32), 16, 16, 4, {"precision": 1}, form="split", nread=4,
+          kernels=["first<u8,split>", "h<1,0,16,2>", "h<1,0,8,3>", "h<2,0,8,3>", "h<2,1,8,3>", "head<split>"]),
+    _case("split-five-levels-64x96", (3, 6, 12, 24, 48), 64, 96, 4, {"precision": 1}, form="split", nread=4,
+          kernels=["first<u8,split>", "h<1,0,16,2>", "h<1,0,8,3>", "h<2,0,8,3>", "h<2,1,8,3>", "head<split>"]),
+    _case("split-fused-first-and-head-96x160", (32, 64), 96, 160, 16, {"precision": 1, "keep_taps": 0}, form="split", nread=4, fused_first=True, fused_head=True,
+          kernels=["h<1,0,16,2>", "h<1,0,8,3,FIRST>", "h<1,0,8,3>", "h<2,0,16,2,SQ>", "h<2,0,8,3>", "h<2,1,8,3>"]),
+    _case("direct-impl0-96x160", (32, 64), 96, 160, 4, {"wino": 0, "conv_impl": 0}, form="direct", nread=4,
+          kernels=["first<u8>", "head", "mfma<1,0,8>", "mfma<2,0,8>", "mfma<2,1,8>"]),
+    _case("fused-first-and-head-96x160", (32, 64), 96, 160, 16, {"wino": 0, "keep_taps": 0}, form="direct", nread=4, fused_first=True, fused_head=True,
+          kernels=["o<1,0,8,3,FIRST>", "o<1,0,8,3>", "o<2,0,8,3>", "o<2,1,8,3>"]),
+    _case("split-splitk-96x160-1", (32, 64), 96, 160, 1, {"precision": 1, "splitk": 1}, form="split", nread=1,
+          kernels=["first<u8,split>", "h<1,0,16,2>", "h<1,0,8,3>+splitK", "h<2,0,16,2,SQ>", "h<2,0,8,3>+splitK", "h<2,1,8,3>+splitK", "head<split>"]),
+    _case("splitk-nt1-0-33x66-1", (33, 66), 32, 64, 1, {"wino": 0, "splitk": 1, "splitk_nt1": 0}, form="direct", nread=1,
+          kernels=["first<u8>", "head", "o<1,0,8,3>+splitK+reduce", "o<2,0,8,3>+splitK+reduce", "o<2,1,8,3>+splitK+reduce"]),
+    _case("wave-split-wb2-64x64-1", (32, 64), 64, 64, 1, {"wino_w": 3}, form="wino", nread=1,
+          kernels=["convt_w", "first<u8>", "w<2> nt=1", "w<2> nt=2"]),
+    _case("wave-split-wp-33x66-1", (33, 66), 32, 64, 1, {}, form="wino", nread=1,
+          kernels=["convt_w", "first<u8>", "head", "p<1,0,8,3>", "wp nt=2"]),
+    _case("splitk-epilogue-33x66-8", (33, 66), 32, 64, 8, {"wino": 0, "splitk": 1, "splitk_fused": 0}, form="direct", nread=4,
+          kernels=["epilogue<1,0,8>", "epilogue<2,0,8>", "epilogue<2,1,8>", "first<u8>", "head", "o<1,0,8,3>+splitK", "o<2,0,8,3>+splitK", "o<2,1,8,3>+splitK"]),
+    # split K on the persistent kernel (conv_impl 1, or splitk_occ 0): raw accumulators of every K part, summed by k_splitk_epilogue
+    _case("persistent-splitk-96x160-1", (32, 64), 96, 160, 1, {"wino": 0, "conv_impl": 1, "splitk": 1}, form="direct", nread=1,
+          kernels=["epilogue<1,0,8>", "epilogue<2,0,8>", "epilogue<2,1,8>", "first<u8>", "p<1,0,8,3>", "p<1,0,8,3>+splitK", "p<2,0,8,1>",
+                   "p<2,0,8,1>+splitK", "p<2,1,8,1>+splitK"]),
+    _case("persistent-splitk-tps1-33x66-2", (33, 66), 32, 64, 2, {"wino": 0, "conv_impl": 1, "splitk": 1, "tps_nt1": 1}, form="direct", nread=2,
+          kernels=["epilogue<1,0,8>", "epilogue<2,0,8>", "epilogue<2,1,8>", "first<u8>", "head", "p<1,0,8,1>+splitK", "p<2,0,8,1>+splitK",
+                   "p<2,1,8,1>+splitK"]),
+    _case("persistent-splitk-tps9-33x66-2", (33, 66), 32, 64, 2, {"wino": 0, "conv_impl": 1, "splitk": 1, "tps_nt1": 9, "tps_nt2": 3}, form="direct",
+          nread=2, kernels=["epilogue<1,0,8>", "epilogue<2,0,8>", "epilogue<2,1,8>", "first<u8>", "head", "p<1,0,8,9>+splitK", "p<2,0,8,3>+splitK",
+                            "p<2,1,8,1>+splitK"]),
 ]
 
 # every kernel the f16 mode can launch, by the short label of its instantiation -> its text in og_unet_plan / in UNet.profile
@@ -597,6 +772,36 @@ GPU_CASES += [
 ]
 
 
+# new rows that are the only cover of no instantiation, overall or among the edge rows (tests/test_layer_ref.py checks that this list
+# is exact: every other row added with the registry is the only cover of something) -> what the row adds instead
+REDUNDANT_FOR_COVERAGE = {
+    "persistent-tps9-33x66": "p<1,0,8,9> / p<2,0,8,3> on padded channels (33 -> 64, 66 -> 96) and every layer, not only 8-row tails",
+    "position-split-pn1-64x64": "ps<1,1> / ps<2,1> forced on every layer of the 64 x 64 net (auto picks them on deep layers only)",
+    "position-split-96x160-1": "the auto position split beside direct launches on maps that do not tile (24 x 40)",
+    "position-split-96x160-2": "the same at two frames: ps<1,2>",
+    "split-tiles-96x160": "the split-precision default on partial tiles",
+    "split-tile-h8-96x160": "h<1,0,8,3> / h<2,0,8,3> on every layer of a net with partial tiles",
+    "wave-split-wp-33x66-1": "wp nt=2 on padded channels, one frame per chain",
+    "split-padded-33x66-32x64": "split precision with padded K",
+    "split-bottleneck-1x1-16x16": "split precision down to a 1 x 1 bottleneck",
+    "split-five-levels-64x96": "split precision on five levels and 3-channel layers",
+}
+
+# The NCHW-float entry point (``m(x)``: k_conv_first<float> / <float, true>) at precision 0 and 1: the six special frames at
+# 64 x 64 (tests/test_gpu_layer_parity.py::test_f32_entry_point_in_f32_and_split_precision); ``entry_f32`` makes og_unet_plan and
+# UNet.profile walk that entry point's chain
+F32_ENTRY_CASES = [
+    _case("entry-f32-33x66", (33, 66), 64, 64, 6, {"precision": 0, "entry_f32": 1}, form="wino", nread=6,
+          kernels=["convt_w", "first<f32>", "head", "p<1,0,8,3>", "p<2,1,8,1>", "w<1> nt=1", "w<1> nt=2"]),
+    _case("entry-f32-full", FULL, 64, 64, 6, {"precision": 0, "entry_f32": 1}, form="wino", nread=6,
+          kernels=["convt_w", "first<f32>", "p<2,0,8,1>", "w<1> nt=1", "w<1> nt=2", "wp nt=2"]),
+    _case("entry-f32-split-33x66", (33, 66), 64, 64, 6, {"precision": 1, "entry_f32": 1}, form="split", nread=6,
+          kernels=["first<f32,split>", "h<1,0,16,2>", "h<2,0,16,2,SQ>", "h<2,1,8,3>", "head<split>"]),
+    _case("entry-f32-split-full", FULL, 64, 64, 6, {"precision": 1, "entry_f32": 1}, form="split", nread=6,
+          kernels=["first<f32,split>", "h<1,0,16,2>", "h<2,0,16,2,SQ>", "h<2,0,8,3>", "h<2,1,8,3>", "head<split>"]),
+]
+
+
 def kappa_of(form: str) -> dict:
     """kappa per op kind for a chain of the given form (the first layer, the transposed convs and the heads are direct in every
     f32 chain; split precision runs every op through the hi / lo arithmetic, the f16 mode through its own kernels)."""
@@ -632,15 +837,31 @@ def plan_families(recs, B: int) -> set:
 
 
 def plan_instantiations(recs) -> set:
-    """Kernels of an f16-mode og_unet_plan record list by instantiation: the record's text without its parentheses and its K-walk
-    suffix (``k_conv_mfma_f<2, 0, 16, 2, false, true>``), ``k_conv_first_f`` and ``k_head_f`` without their arguments."""
+    """Kernels of an og_unet_plan record list by instantiation, for all three arithmetic forms: every conv, transposed-conv,
+    first-layer, head and split-K epilogue launch by the text the plan records for it, without parentheses.  What the record
+    carries behind the instantiation is folded in where it names another code path, dropped where it does not: ``ksplit=N``
+    becomes ``+splitK`` for N > 1 (as in ``UNet.profile``) and ``+splitK+reduce`` where the launch also has arrival counters (the
+    last workgroup of a tile reduces the parts inside the kernel; without them ``k_splitk_epilogue`` follows), `` nt=N`` (the weight pack k_conv_wino_w / k_conv_wino_wp read: that
+    of a 32- or of a 64-column layer) stays, the K walk of an f16 launch (`` chunks=N k_half=N``) goes.  The f16 mode's first-layer
+    and head kernels stay without their arguments (``k_conv_first_f``, ``k_head_f``).  ``k_sum_counts`` (an exact integer sum
+    behind the fused head, held by ``area == popcount(mask)``) is no layer kernel and is left out."""
     import re
 
     out = set()
     for r in recs:
-        m = re.match(r"\(?\s*(k_conv_mfma_f<[^>]*>)", r["kernel"]) or re.match(r"\(?\s*(k_conv_first_f|k_head_f)\b", r["kernel"])
+        k = r["kernel"]
+        m = re.match(r"\(?\s*(k_conv_first_f|k_head_f)\b", k)
         if m:
             out.add(m.group(1))
+            continue
+        m = re.match(r"\(?\s*(k_\w+(?:<[^>]*>)?)\)?(.*)$", k)
+        if not m or m.group(1) == "k_sum_counts":
+            continue
+        inst, rest = m.group(1), m.group(2)
+        nt = re.search(r" nt=(\d+)", rest)
+        ks = re.search(r" ksplit=(\d+)", rest)
+        split = "" if not ks or int(ks.group(1)) == 1 else "+splitK+reduce" if r["ws"] > 0 and r["cnt"] > 0 else "+splitK"
+        out.add(inst + (f" nt={nt.group(1)}" if nt else "") + split)
     return out
 
 

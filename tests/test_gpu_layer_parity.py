@@ -15,6 +15,14 @@ nets).  Which kernels ran is asserted through
 The f16 rows (``form`` "f16", precision 2) are judged by the interval test of ``layer_ref.check_f16``: every stored f16 value must
 lie between the roundings of ``ref -+ kappa * 2^-24 * M``, a condition on its bits; their print line shows the smallest kappa each
 layer needs.  ``test_f32_entry_point_in_f16_mode`` runs the same check on ``m(x)`` (NCHW floats in: ``k_conv_first_f<f32>``).
+
+The f32 and split-precision rows cover every instantiation those two precisions can launch (``layer_ref.F32_KERNELS``, closed on
+the CPU by tests/test_layer_ref.py), each on a shape with edges wherever the planner allows one; a row asserts the ``UNet.profile``
+label of every kernel it claims.  That GPU assertion is weaker than the CPU one: ``UNet.profile`` gives ``OCC`` 3 and 4, ``SQ`` true
+and false, split K with the fused reduce and with the epilogue, and a split and an unsplit ``k_conv_mfma_h`` / ``k_conv_mfma_p`` the
+same label, so for those the evidence that the instantiation ran is that the row's plan (``og_unet_plan``, the product's own launch
+decisions, claimed exactly on the CPU) is the chain the product runs.  ``test_f32_entry_point_in_f32_and_split_precision`` does for ``k_conv_first<float>`` /
+``<float, true>`` what the f16 entry-point test does for its kernel.
 """
 import numpy as np
 import pytest
@@ -71,6 +79,8 @@ def test_every_layer_against_float64(case):
         return
     fams = R.profile_families(prof)
     assert set(case["prof"]) <= fams, (case["id"], sorted(set(case["prof"]) - fams), sorted(fams))
+    labels = R.profile_instantiations(prof)    # and by instantiation: the labels of every kernel the row's plan claims (F32_KERNELS)
+    assert case["prof_inst"] and set(case["prof_inst"]) <= labels, (case["id"], sorted(set(case["prof_inst"]) - labels), sorted(labels))
     print(f"{case['id']} [{case['form']} kappa {R.KAPPA[case['form']]:g}] worst |err|/bound per layer: "
           + " ".join(f"{k}={v:.3f}" for k, v in worst.items() if not k.startswith("pool")) + f"  (max {max(worst.values()):.3f})")
 
@@ -101,3 +111,40 @@ def test_f32_entry_point_in_f16_mode(feats):
     for name, t in taps.items():
         assert np.array_equal(m.activation(name, B), t), name
 
+
+
+@pytest.mark.parametrize("case", R.F32_ENTRY_CASES, ids=[c["id"] for c in R.F32_ENTRY_CASES])
+def test_f32_entry_point_in_f32_and_split_precision(case):
+    """``m(x)``, NCHW floats in, at precision 0 and 1: the first layer is ``k_conv_first<float>`` / ``<float, true>``, which the
+    u8 product path never launches.  The six special frames at 64 x 64 through the per-layer check at the form's kappa, every tap
+    and logit bit for bit what the u8 entry point (``segment``) gives for the same frames, and ``UNet.profile`` walking the float
+    entry point's chain (option ``entry_f32``) names ``k_conv_first<f32>`` and the other kernels the case claims."""
+    import torch
+
+    feats, H, W = case["feats"], case["H"], case["W"]
+    sd = synth.make_unet_state_dict(feats, seed=11, head_scale=3.0, head_bias=-0.5)
+    m = og.UNet(1, 1, feats)
+    m.load_state_dict(sd)
+    m.to("cuda:0").eval()
+    m.set_option("precision", case["options"]["precision"])
+    gray = batch(H, W, len(ORDER))
+    B = len(gray)
+    assert B == case["B"]
+    m.set_chunk(B)
+    x = np.ascontiguousarray((gray.astype(np.float32) / 255.0)[:, None])
+    logits = np.asarray(m(x))[:, 0]
+    taps = {name: m.activation(name, B) for name in R.layer_names(len(feats))}
+    worst = R.check_net(sd, gray, taps.__getitem__, logits, R.kappa_of(case["form"]), frames=ORDER, form=case["form"])
+    print(f"{case['id']} [{case['form']} kappa {R.KAPPA[case['form']]:g}] worst |err|/bound per layer: "
+          + " ".join(f"{k}={v:.3f}" for k, v in worst.items() if not k.startswith("pool")) + f"  (max {max(worst.values()):.3f})")
+    m.set_option("keep_taps", 1)
+    _, _, lg_u8 = m.segment(gray, want_logits=True)
+    assert np.array_equal(lg_u8, logits)
+    for name, t in taps.items():
+        assert np.array_equal(m.activation(name, B), t), name
+    m.set_option("entry_f32", 1)
+    labels = R.profile_instantiations(m.profile(torch.from_numpy(x).cuda(), B, H, W, reps=1))
+    assert "k_conv_first<f32>" in labels and "k_conv_first<u8>" not in labels, sorted(labels)
+    assert set(case["prof_inst"]) <= labels, (case["id"], sorted(set(case["prof_inst"]) - labels), sorted(labels))
+    with pytest.raises(og.OpenGlottalHipError, match="float32"):      # the option changes what profile reads: a u8 buffer is refused
+        m.profile(torch.from_numpy(gray).cuda(), B, H, W, reps=1)

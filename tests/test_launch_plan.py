@@ -71,7 +71,8 @@ def test_other_nets_and_frame_shapes(feats, shape):
 
 def test_the_plan_is_the_chain_the_product_runs():
     """Shape of the record list: one first layer, 17 3x3 convs and 4 transposed convs of the full-width net, the per-frame count
-    reduction behind the fused head; the one-frame chain takes the wave-split kernels, the 64-frame chain k_conv_wino."""
+    reduction behind the fused head; the one-frame chain takes the wave-split kernels, the 64-frame chain k_conv_wino: 14 launches
+    of <2> (64-column tiles) and 3 of <1> (the layers with 32 output channels)."""
     r1, _ = plan(FULL, 1, 256, 256)
     k1 = [r["kernel"] for r in r1]
     assert len(k1) == 23 and k1[0].startswith("k_conv_first") and k1[-1] == "k_sum_counts", k1
@@ -81,7 +82,12 @@ def test_the_plan_is_the_chain_the_product_runs():
     assert not any("k_conv_wino_wp" in r["kernel"] for r in r3)          # several lanes in flight: the unsplit kernel (occupancy)
     r64, _ = plan(FULL, 64, 256, 256, lanes=2)
     k64 = [r["kernel"] for r in r64]
-    assert sum(k == "k_conv_wino<NT>" for k in k64) == 17 and k64[-1] == "k_sum_counts", k64      # (the recorder keeps the launch site's text)
+    # (the recorder names the instantiation) 32-column layers -- 32 output channels: downs.0.b, ups.7.a, ups.7.b -- on <1>, the rest on <2>
+    assert sum(k == "k_conv_wino<2>" for k in k64) == 14 and sum(k == "k_conv_wino<1>" for k in k64) == 3 and k64[-1] == "k_sum_counts", k64
+    assert k64[1] == k64[-3] == k64[-2] == "k_conv_wino<1>", k64
+    # the one-frame chain by instantiation: which weight pack each wave-split launch reads (nt), all four transposed convs
+    assert sum(k.startswith("k_conv_wino_w<") or k.startswith("k_conv_wino_wp nt=") for k in k1) == 17, k1
+    assert sum(k.endswith(" nt=1") for k in k1) == 3 and sum(k.endswith(" nt=2") for k in k1) == 14, k1
     assert all(r["ws"] == 0 for r in r64)
 
 

@@ -6,7 +6,10 @@
 * every case of tests/test_gpu_layer_parity.py runs the kernel families it is meant to exercise (og_unet_plan, no GPU needed);
 * the f16 mode's form ("f16": an interval of f16 values per element, not a tolerance): its torch-CPU emulation passes at kappa 16,
   eleven mutants planted into one element each are flagged there, and the f16 rows of the matrix run, by instantiation, every
-  kernel the mode can launch, with a half last chunk (ConvArgs::k_half) both alone and after full chunks.
+  kernel the mode can launch, with a half last chunk (ConvArgs::k_half) both alone and after full chunks;
+* the f32 and split-precision chains likewise: layer_ref.F32_KERNELS lists every instantiation precision 0 and 1 can launch; an
+  option sweep over og_unet_plan finds none outside it, every entry is reached, the non-f16 rows of the matrix run all of them, and
+  whatever can run on a shape with edges is run on one.
 """
 import numpy as np
 import pytest
@@ -432,7 +435,10 @@ def test_check_f16_refuses_values_that_are_not_f16_and_non_finite_ones():
 # ───────────────────────────── coverage of the GPU matrix ─────────────────────────────
 
 
-@pytest.mark.parametrize("case", R.GPU_CASES, ids=[c["id"] for c in R.GPU_CASES])
+_MATRIX = R.GPU_CASES + R.F32_ENTRY_CASES
+
+
+@pytest.mark.parametrize("case", _MATRIX, ids=[c["id"] for c in _MATRIX])
 def test_gpu_matrix_case_runs_the_kernels_it_claims(case):
     from test_launch_plan import check, plan
 
@@ -459,6 +465,145 @@ def test_gpu_matrix_case_runs_the_kernels_it_claims(case):
         assert "first-fused" not in fams
     if case["fused_head"]:
         assert "k_head" not in fams and case["options"]["keep_taps"] == 0
+    # by instantiation, exactly: the row claims every kernel its plan shows and no other
+    assert case["kernels"], case["id"]
+    claimed = {R.F32_KERNELS[k][0] for k in case["kernels"]}
+    insts = R.plan_instantiations(recs)
+    assert claimed == insts, (case["id"], "claimed, not planned:", sorted(claimed - insts), "planned, not claimed:", sorted(insts - claimed))
+    assert set(case["prof_inst"]) == {R.F32_KERNELS[k][1] for k in case["kernels"]} - {None}
+    assert (case["form"] == "split") == (case["options"].get("precision", 0) == 1)
+
+
+# ───────────────────────────── the f32 and split-precision instantiations: a closed list ─────────────────────────────
+
+SWEEP_BATCHES = (1, 2, 3, 8, 64)
+# test_launch_plan.py's shapes (the full-width net at 256 x 256 first), then the other edge shapes of the GPU matrix
+SWEEP_SHAPES = [(R.FULL, (256, 256)), ((32, 64), (128, 256)), ((32, 64), (96, 160)), ((64, 128), (48, 64)), ((40, 80), (64, 64)),
+                ((32, 64, 128), (64, 32)), ((4, 8, 16, 32), (256, 256)), ((32, 64, 128, 256), (512, 512)),
+                ((16, 32, 64, 128, 256), (256, 256)), ((96, 192), (64, 128)),
+                ((33, 66), (32, 64)), ((4, 8, 16, 32), (16, 16)), ((4, 8, 16, 32), (16, 256)), ((3, 6, 12, 24, 48), (64, 96)),
+                ((32, 64), (64, 64)), ((32, 64), (512, 512)), ((33, 66), (64, 64)), (R.FULL, (64, 64))]
+SWEEP_SINGLE = ([f"conv_impl={v}" for v in (0, 1, 2, 3)] + [f"tps_nt1={v}" for v in (1, 3, 9)] + [f"tps_nt2={v}" for v in (1, 3)]
+                + [f"tile_h={v}" for v in (0, 8, 16)] + [f"{n}={v}" for n in ("h_square", "convt_occ", "convt_w", "splitk_occ", "fuse_head",
+                                                                              "fuse_first", "wino_first") for v in (0, 1)]
+                + [f"occ_min_pct={v}" for v in (0, 400)] + [f"wg_per_cu={v}" for v in (1, 2)])
+# each single value alone (the default Winograd chain) and on top of the other three chains
+SWEEP_BASES = ["", "wino=0", "wino=0,conv_impl=1", "precision=1"]
+_sweep_cache = {}
+
+
+def sweep_option_sets():
+    from test_launch_plan import OPTION_SETS
+
+    out = list(OPTION_SETS)
+    for base in SWEEP_BASES:
+        out += [(base + "," if base else "") + s for s in SWEEP_SINGLE if s.split("=")[0] + "=" not in base]
+    # split K on the persistent kernel: conv_impl 1, or the occupancy kernel's K parts switched off, and the tap groups under it
+    out += ["conv_impl=1,splitk=1", "wino=0,conv_impl=1,splitk=1", "splitk=1,splitk_occ=0", "wino=0,splitk=1,splitk_occ=0",
+            "wino=0,conv_impl=1,splitk=1,tps_nt1=1", "wino=0,conv_impl=1,splitk=1,tps_nt1=9,tps_nt2=3", "wino=0,conv_impl=1,splitk=1,tile_h=16",
+            "precision=1,conv_impl=1,splitk=1", "wino=0,conv_impl=0,splitk=1", "wino=0,conv_impl=3,splitk=1"]
+    out += ["entry_f32=1", "precision=1,entry_f32=1"]
+    return list(dict.fromkeys(out))
+
+
+def sweep():
+    """{instantiation: [(is_edge, feats, H, W, B, options), ...]} over SWEEP_SHAPES x sweep_option_sets() x SWEEP_BATCHES (computed once)."""
+    from test_launch_plan import plan
+
+    if not _sweep_cache:
+        for feats, (H, W) in SWEEP_SHAPES:
+            edge = R.is_edge_case(dict(feats=feats, H=H, W=W))
+            for options in sweep_option_sets():
+                for B in SWEEP_BATCHES:
+                    recs, _ = plan(feats, B, H, W, 1, options)
+                    for inst in R.plan_instantiations(recs):
+                        _sweep_cache.setdefault(inst, []).append((edge, feats, H, W, B, options))
+    return _sweep_cache
+
+
+def matrix_cover():
+    """({instantiation: [row ids]}, the same over the edge rows only) from the PLANS of the non-f16 rows and the float entry cases."""
+    from test_launch_plan import plan
+
+    every, edges = {}, {}
+    for c in _MATRIX:
+        if c["form"] == "f16":
+            continue
+        recs, _ = plan(c["feats"], c["B"], c["H"], c["W"], 1, R.option_string(c["options"]))
+        for inst in R.plan_instantiations(recs):
+            every.setdefault(inst, []).append(c["id"])
+            if R.is_edge_case(c):
+                edges.setdefault(inst, []).append(c["id"])
+    return every, edges
+
+
+def test_f32_registry_is_closed_under_the_option_sweep():
+    """No plan of the sweep shows an f32 or split-precision instantiation F32_KERNELS does not know, and no entry is dead: each is
+    reached by the net, shape, micro-batch and option set it names."""
+    from test_launch_plan import plan
+
+    texts = {v[0] for v in R.F32_KERNELS.values()}
+    assert len(texts) == len(R.F32_KERNELS) == 67
+    assert not any(t.startswith(("k_conv_mfma_f<", "k_conv_first_f", "k_head_f")) for t in texts)
+    seen = sweep()
+    unknown = {i: w[0][1:] for i, w in seen.items() if i not in texts}
+    assert not unknown, ("instantiations the registry does not know, and a plan that shows each", unknown)
+    for short, (text, label, (feats, H, W, B, options)) in R.F32_KERNELS.items():
+        assert "precision=2" not in options
+        recs, _ = plan(feats, B, H, W, 1, options)
+        assert text in R.plan_instantiations(recs), (short, text, "is not reached by", (feats, H, W, B, options))
+        assert (label is None) == text.startswith("k_splitk_epilogue"), short
+    # the sweep alone reaches all but the two that need three options at once (16-row persistent tiles with other tap groups)
+    # -- those are reached by their own entries above
+    assert texts - set(seen) <= {R.F32_KERNELS[k][0] for k in ("p<1,0,16,9>", "p<2,0,16,3>")}, sorted(texts - set(seen))
+
+
+def test_f32_matrix_runs_every_registered_instantiation():
+    """The union of instantiations over the plans of the non-f16 rows (and the float entry cases) IS the registry: dropping a row
+    that is the only cover of an instantiation fails here and names it."""
+    every, _ = matrix_cover()
+    texts = {v[0] for v in R.F32_KERNELS.values()}
+    assert set(every) == texts, ("never compared with float64:", sorted(texts - set(every)), "unregistered:", sorted(set(every) - texts))
+    # and each is claimed, so that the GPU test asserts its UNet.profile label
+    claimed = {k for c in _MATRIX for k in c["kernels"]}
+    assert claimed == set(R.F32_KERNELS), sorted(set(R.F32_KERNELS) ^ claimed)
+    for k in ("h<1,0,8,3,FIRST>", "h<1,0,8,3>", "o<1,0,16,2>", "p<1,0,16,3>", "p<2,0,16,1>", "p<1,0,16,9>", "p<2,0,16,3>", "p<1,0,8,9>",
+              "p<2,0,8,3>", "p<1,0,8,1>", "ps<1,1>", "ps<1,2>", "ps<1,4>", "o<1,0,8,4>", "o<2,0,8,4>", "h<2,0,16,2>", "first<f32>",
+              "first<f32,split>"):
+        assert any(R.F32_KERNELS[k][1] in c["prof_inst"] for c in _MATRIX if k in c["kernels"]), k
+
+
+def test_rows_redundant_for_coverage_are_exactly_the_listed_ones():
+    """Every row added with the registry is the only cover of some instantiation -- overall or among the edge rows -- so that dropping
+    it fails one of the two tests around this one by name; the exceptions are listed, with what each adds, in REDUNDANT_FOR_COVERAGE."""
+    every, edges = matrix_cover()
+    ids = [c["id"] for c in R.GPU_CASES if c["form"] != "f16"]
+    new_rows = ids[ids.index("persistent-tps9-33x66"):]
+    sole = {rows[0] for rows in list(every.values()) + list(edges.values()) if len(rows) == 1}
+    redundant = {r for r in new_rows if r not in sole}
+    assert redundant == set(R.REDUNDANT_FOR_COVERAGE), (sorted(redundant - set(R.REDUNDANT_FOR_COVERAGE)), sorted(set(R.REDUNDANT_FOR_COVERAGE) - redundant))
+    assert all(R.REDUNDANT_FOR_COVERAGE.values())
+
+
+def test_f32_matrix_covers_every_instantiation_on_an_edge_shape():
+    """Whatever the planner can choose on a shape with edges (anything but the full-width net at 256 x 256: tiles with borders,
+    padded channels, small maps) is judged on one: every instantiation the sweep -- or a registry entry's own option set -- reaches
+    on an edge shape is run by at least one edge row.  EDGE_EXEMPT may list what the planner picks at 256 x 256 full width only."""
+    _, edges = matrix_cover()
+    on_edges = {i: next(w[1:] for w in where if w[0]) for i, where in sweep().items() if any(w[0] for w in where)}
+    for text, _, (feats, H, W, B, options) in R.F32_KERNELS.values():
+        if R.is_edge_case(dict(feats=feats, H=H, W=W)):
+            on_edges.setdefault(text, (feats, H, W, B, options))
+    for text, rule in R.EDGE_EXEMPT.items():
+        assert text not in on_edges, (text, "is exempt but reachable on an edge shape:", on_edges[text])
+        assert rule
+    lost = {i: w for i, w in on_edges.items() if i not in edges}
+    assert not lost, ("reachable on an edge shape but judged by no edge row (instantiation: a plan that reaches it)", lost)
+    # every split-precision kernel is among them: partial tiles, padded channels and the 1 x 1 bottleneck at kappa * 2^-24 * M
+    assert all(t in edges for t in (v[0] for v in R.F32_KERNELS.values()) if "k_conv_mfma_h" in t)
+    split_edge = [c for c in R.GPU_CASES if c["form"] == "split" and R.is_edge_case(c)]
+    assert {(c["feats"], c["H"], c["W"]) for c in split_edge} >= {((32, 64), 96, 160), ((33, 66), 32, 64), ((4, 8, 16, 32), 16, 16),
+                                                                 ((3, 6, 12, 24, 48), 64, 96)}
 
 
 def test_f16_matrix_covers_every_instantiation_and_both_half_chunks():

@@ -329,8 +329,23 @@ int og_yolo_finalize(og_yolo* h);
  * U-Net's resized path); never lower than one frame -- a larger frame is staged alone; 0 and negative values: OG_EINVAL.  Results are
  * per frame: the setting changes no bit.  "source_mapped" [1]: one-frame resized calls -- k_letterbox_bgr reads the source frame from
  * the handle's mapped pinned buffer (1, the measured choice: one copy command less on the stream) or after an
- * asynchronous copy to the device (0). */
+ * asynchronous copy to the device (0).
+ * "trace_launches" [0] (DIAGNOSTIC): 1 keeps, for the last kernel chain the handle enqueued, the label og_yolo_plan gives each launch
+ * and the module it serves (og_yolo_last_launches); 0 costs a real call nothing. */
 int og_yolo_set_option(og_yolo* h, const char* name, int value);
+/* Dry run of the detector's launch decisions, WITHOUT a device (as og_unet_plan for the U-Net).  `h`: a created handle that has its
+ * tensors (og_yolo_set_tensor; only their shapes are read) and is NOT finalized (finalized: OG_ESTATE); it is left untouched.  A
+ * host-only copy is finalized (no stream, no device allocation, placeholder pointers), takes the handle's options and then
+ * `options` ("name=value,name=value", og_yolo_set_option names), `n_cu` compute units (0: 256, an MI355X) and walks the chain of
+ * og_yolo_detect_u8_dev for B frames of H x W (B > 512: its first 512-frame chain).  `out` receives one line per launch,
+ *   label|grid.x|grid.y|grid.z|block|lds_bytes|splitk_workspace_bytes|arrival_counters|module
+ * label: the kernel with every template argument resolved, then what is decided at run time ("k_conv_mfma_o<1, 3, 8, 3, false, true>
+ * vsplit=4", "k_conv_mfma_o<1, 2, 8, 3, false, false> ksplit=8", "k_conv_direct<true, 1> cq_shift=2", "k_sppf_pools"); module: the
+ * path the launch serves ("model.4.m.1.cv2", "model.22.hd.0.1" for the stacked Detect chain, "model.9.m.1-3" for the one-launch
+ * pools, "model.22" for the decode).  Returns the number of launches (>= 0) or an error code; *arena_bytes (optional): the arena. */
+int og_yolo_plan(og_yolo* h, int B, int H, int W, int n_cu, const char* options, char* out, size_t cap, long long* arena_bytes);
+/* "trace_launches" 1: the launches of the last chain as "label|module" lines, the labels og_yolo_plan writes.  Returns their number. */
+int og_yolo_last_launches(og_yolo* h, char* out, size_t cap);
 int og_yolo_num_anchors(og_yolo* h, int H, int W);    /* (H/8)(W/8)+(H/16)(W/16)+(H/32)(W/32) */
 /* frames [B,H,W,3] u8 BGR at network resolution (H,W multiples of 32; the caller letterboxes).
  *   best [B,5] f32: x1,y1,x2,y2,conf of the arg-max-confidence candidate with conf > conf_thres,

@@ -91,6 +91,8 @@ PROTOTYPES = {
     "og_yolo_set_tensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_int]),
     "og_yolo_finalize": (C.c_int, [C.c_void_p]),
     "og_yolo_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
+    "og_yolo_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
+    "og_yolo_last_launches": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "og_yolo_num_anchors": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "og_yolo_detect_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "og_yolo_detect_u8_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float]),

@@ -82,6 +82,7 @@ struct PlanRec {
     long long partial_bytes;
     long long counters;
     std::string writes;   // og_unet_plan_resized: "buffer=end" per caller-owned buffer the launch writes (end = bytes from its base)
+    std::string mod;      // og_yolo_plan: the module path the launch serves
 };
 struct Plan {
     std::vector<PlanRec> recs;
@@ -89,6 +90,12 @@ struct Plan {
     std::map<std::string, const void*> bases;   // og_unet_plan_resized: placeholder base of each caller-owned buffer
 };
 thread_local Plan* g_plan = nullptr;
+// the detector's chain: the module path the launches being enqueued serve (og_yolo_plan records, "trace_launches" 1 traces)
+thread_local const char* g_launch_mod = nullptr;
+// og_yolo option "trace_launches" 1: while a real chain is enqueued, the labels og_yolo_plan would give its launches, with their modules
+thread_local std::vector<std::pair<std::string, std::string>>* g_trace = nullptr;
+// og_yolo_plan: upload() hands out placeholder pointers (no device)
+thread_local bool g_upload_placeholder = false;
 inline void plan_need(long long partial_bytes, long long counters) {
     if (g_plan) {
         g_plan->need_partial = partial_bytes;
@@ -96,7 +103,8 @@ inline void plan_need(long long partial_bytes, long long counters) {
     }
 }
 inline void plan_record(const char* kernel, dim3 grid, dim3 block, size_t lds) {
-    g_plan->recs.push_back({kernel, grid.x, grid.y, grid.z, block.x, (unsigned)lds, g_plan->need_partial, g_plan->need_counters, ""});
+    g_plan->recs.push_back({kernel, grid.x, grid.y, grid.z, block.x, (unsigned)lds, g_plan->need_partial, g_plan->need_counters, "",
+                            g_launch_mod ? g_launch_mod : ""});
     g_plan->need_partial = g_plan->need_counters = 0;
 }
 // the last recorded launch writes `bytes` into caller-owned buffer `name` starting at `p`: note where that ends, from the buffer's base
@@ -117,13 +125,16 @@ inline void plan_label_f(const char* inst, int n_chunks, int k_half) {
 // og_unet_plan only: name the launch just recorded by the instantiation that would run, every template argument resolved (the
 // launch site's text has template parameters in it), with what is decided at run time behind it (" ksplit=3", " nt=2")
 inline void plan_inst(const char* fmt, ...) {
-    if (!g_plan || g_plan->recs.empty()) return;
+    std::string* slot = nullptr;
+    if (g_plan && !g_plan->recs.empty()) slot = &g_plan->recs.back().kernel;
+    else if (g_trace && !g_trace->empty()) slot = &g_trace->back().first;
+    if (!slot) return;
     char inst[96];
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(inst, sizeof inst, fmt, ap);
     va_end(ap);
-    g_plan->recs.back().kernel = inst;
+    *slot = inst;
 }
 // every launch of the chain goes through here: a failed launch is reported as OG_EHIP by THIS call (not by a later one)
 #define OG_LAUNCH(kern, grid, block, lds, stream, ...)                                                    \
@@ -134,6 +145,7 @@ inline void plan_inst(const char* fmt, ...) {
             hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__);                              \
             hipError_t le_ = hipGetLastError();                                                           \
             if (le_ != hipSuccess) return fail(OG_EHIP, std::string(#kern) + ": " + hipGetErrorString(le_)); \
+            if (g_trace) g_trace->push_back({#kern, g_launch_mod ? g_launch_mod : ""});                   \
         }                                                                                                 \
     } while (0)
 
@@ -449,6 +461,10 @@ std::vector<float> pack_gemm_b_f(int Ncols_p, int Kp, int taps, int NT, F&& weig
 }
 
 int upload(const std::vector<float>& v, float** d) {
+    if (g_upload_placeholder) {
+        *d = (float*)8;
+        return OG_OK;
+    }
     HIPCHK(hipMalloc((void**)d, v.size() * sizeof(float)));
     HIPCHK(hipMemcpy(*d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
     return OG_OK;
@@ -726,7 +742,8 @@ int launch_conv_o(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {
         plan_need((long long)a.n_spatial * n_ntiles * a.ksplit * 4 * (((TH / 2) / (4 / NT)) * 16 * 64) * 4,
                   a.tile_counter ? (long long)a.n_spatial * n_ntiles : 0);
     OG_LAUNCH((k_conv_mfma_o<NT, MODE, TH, OCC, false, VS>), dim3(a.tiles_x, a.tiles_y, groups * G * a.zdiv), dim3(256), lds, c.stream, a);
-    plan_inst("k_conv_mfma_o<%d, %d, %d, %d, false, %s> ksplit=%d", NT, MODE, TH, OCC, VS ? "true" : "false", a.ksplit);
+    plan_inst(VS ? "k_conv_mfma_o<%d, %d, %d, %d, false, true> vsplit=%d" : "k_conv_mfma_o<%d, %d, %d, %d, false, false> ksplit=%d", NT, MODE,
+              TH, OCC, VS ? a.vsplit : a.ksplit);
     if constexpr (MODE == 0 || MODE == 1) {
         if (a.ksplit > 1 && a.tile_counter == nullptr) {
             OG_LAUNCH((k_splitk_epilogue<NT, MODE, TH>), dim3(a.n_spatial * n_ntiles), dim3(256), 4 * 5120, c.stream, a);

@@ -55,7 +55,10 @@ struct og_yolo {
     bool finalized = false;
     int device = 0;   // as og_unet::device
     int nc = 1, reg_max = 16;
-    int s2_mfma = 1;                    // stride-2 convs on the MFMA kernel (0: VALU k_conv_direct; fixed at finalize)
+    bool host_only = false;             // og_yolo_plan's copy: layer shapes and launch decisions only -- no device, no stream, placeholder pointers
+    int trace_launches = 0;             // DIAGNOSTIC ("trace_launches" 1): keep the (label, module) of every launch of the last chain (og_yolo_last_launches)
+    std::vector<std::pair<std::string, std::string>> last_launches;
+    og_yolo* plan_copy = nullptr;       // og_yolo_plan: the finalized host-only copy of this (unfinalized) handle, kept between calls; a new tensor drops it
     int n_c2f[8] = {0};                 // bottleneck counts of the eight C2f blocks (2,4,6,8,12,15,18,21)
     std::map<std::string, YConv> convs; // by module path, e.g. "model.4.m.1.cv2"
     hipStream_t stream = nullptr;
@@ -103,7 +106,7 @@ struct og_yolo {
     bool pend_scale = false;
 };
 
-inline bool og_skip_device(const og_yolo* h) { return !h || !h->finalized; }
+inline bool og_skip_device(const og_yolo* h) { return !h || h->host_only || !h->finalized; }
 
 namespace {
 
@@ -164,12 +167,12 @@ bool y_synth_head(og_yolo* h) {
             const int cin = (j == 0) ? ib : ib + ic;
             HostTensor w;
             w.shape = {ob + oc, cin, wb->shape[2], wb->shape[3]};
-            w.data.assign((size_t)(ob + oc) * cin * kk, 0.f);
-            for (int o = 0; o < ob; ++o)
+            if (!h->host_only) w.data.assign((size_t)(ob + oc) * cin * kk, 0.f);
+            for (int o = 0; !h->host_only && o < ob; ++o)
                 for (int i = 0; i < ib; ++i)
                     for (int t = 0; t < kk; ++t) w.data[((size_t)o * cin + i) * kk + t] = wb->data[((size_t)o * ib + i) * kk + t];
             const int ioff = (j == 0) ? 0 : ib;
-            for (int o = 0; o < oc; ++o)
+            for (int o = 0; !h->host_only && o < oc; ++o)
                 for (int i = 0; i < ic; ++i)
                     for (int t = 0; t < kk; ++t) w.data[((size_t)(ob + o) * cin + ioff + i) * kk + t] = wc->data[((size_t)o * ic + i) * kk + t];
             add[ph + sj + wk] = std::move(w);
@@ -180,12 +183,15 @@ bool y_synth_head(og_yolo* h) {
                 const HostTensor *vb = get(pb + sj + f), *vc = get(pc + sj + f);
                 if (!vb && !vc) continue;
                 if (j != 2 && (!vb || !vc)) return false;   // one branch folded, the other not: keep the per-branch chain
-                if ((vb && (int)vb->data.size() != ob) || (vc && (int)vc->data.size() != oc)) return false;
+                auto numel = [](const HostTensor* t) { long long n = 1; for (auto d : t->shape) n *= d; return n; };
+                if ((vb && numel(vb) != ob) || (vc && numel(vc) != oc)) return false;
                 HostTensor v;
                 v.shape = {ob + oc};
-                v.data.assign(ob + oc, 0.f);
-                if (vb) std::copy(vb->data.begin(), vb->data.end(), v.data.begin());
-                if (vc) std::copy(vc->data.begin(), vc->data.end(), v.data.begin() + ob);
+                if (!h->host_only) {
+                    v.data.assign(ob + oc, 0.f);
+                    if (vb) std::copy(vb->data.begin(), vb->data.end(), v.data.begin());
+                    if (vc) std::copy(vc->data.begin(), vc->data.end(), v.data.begin() + ob);
+                }
                 add[ph + sj + f] = std::move(v);
             }
         }
@@ -219,6 +225,18 @@ int y_build_conv(og_yolo* h, const std::string& mod, bool plain_conv2d, int kind
     const int in_base = in_segs.front().off, out_base = out_segs.front().off;
     L.Cin_p = in_segs.back().off + cp32(in_segs.back().C) - in_base;
     L.Cout_p = out_segs.back().off + cp32(out_segs.back().C) - out_base;
+    if (h->host_only) {   // shapes only: every image a launch decision asks for "exists"
+        if (kind == 3 && in_segs.size() != 1) return fail(OG_EINVAL, "direct conv with concatenated input");
+        if (kind == 4 && (L.ks != 3 || stride != 2)) return fail(OG_EINVAL, "kind 4 is the 3x3 stride-2 conv: " + mod);
+        if ((kind == 0 && L.ks != 3) || (kind == 2 && L.ks != 1)) return fail(OG_EINVAL, "kernel size mismatch at " + mod);
+        if (kind != 3) L.NT = (L.Cout_p % 64 == 0) ? 2 : 1;
+        L.d_w = L.d_scale = L.d_shift = (float*)8;
+        L.d_w1 = (L.NT == 2) ? (float*)8 : nullptr;
+        L.d_wf = (kind != 3) ? (float*)8 : nullptr;
+        L.f32out = plain_conv2d;
+        h->convs[mod] = L;
+        return OG_OK;
+    }
     std::vector<int> cin_map(L.Cin_p, -1), cout_map(L.Cout_p, -1);
     int lc = 0;
     for (auto& s_ : in_segs)
@@ -344,6 +362,7 @@ int launch_conv_fy(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {
     a.zrcp = 1.0f / (float)(a.zdiv * G);
     if ((long long)groups * G * a.zdiv > 65535) return fail(OG_EINVAL, "micro-batch too large for one launch (grid.z): lower the chunk size");
     OG_LAUNCH((k_conv_mfma_fy<NT, MODE, 3, F32OUT>), dim3(a.tiles_x, a.tiles_y, groups * G * a.zdiv), dim3(256), lds, c.stream, a);
+    plan_inst("k_conv_mfma_fy<%d, %d, 3, %s> chunks=%d k_half=%d", NT, MODE, F32OUT ? "true" : "false", a.n_chunks, a.k_half);
     return OG_OK;
 }
 
@@ -364,10 +383,10 @@ int y_launch_f(og_yolo* h, const YConv& L, int B, const void* in_u8, const YView
         // layout -- f32 logits -- can read as f16 NaN, and 0 x NaN would poison the next conv
         const int cq_shift = 3;
         const unsigned gx = (unsigned)(((long long)total * (1 << cq_shift) + 255) / 256);
-        hipLaunchKernelGGL(k_conv_direct_u8h, dim3(gx, L.Cout_p / 32), dim3(256), 0, h->stream, (const uint8_t*)in_u8, in.H, in.W, L.d_w,
-                           L.d_scale, L.d_shift, L.Cout_p, out.base, out.fs4(), out.ps4(), out.off4(), Hout, Wout, L.ks, L.stride, L.ks / 2,
-                           L.act, total, cq_shift, h->d_range);
-        HIPCHK(hipGetLastError());
+        OG_LAUNCH(k_conv_direct_u8h, dim3(gx, L.Cout_p / 32), dim3(256), 0, h->stream, (const uint8_t*)in_u8, in.H, in.W, L.d_w,
+                  L.d_scale, L.d_shift, L.Cout_p, out.base, out.fs4(), out.ps4(), out.off4(), Hout, Wout, L.ks, L.stride, L.ks / 2,
+                  L.act, total, cq_shift, h->d_range);
+        plan_inst("k_conv_direct_u8h cq_shift=%d", cq_shift);
         return OG_OK;
     }
     if (!L.d_wf) return fail(OG_ESTATE, "no f16 weight image for " + L.name);
@@ -428,23 +447,17 @@ int y_launch(og_yolo* h, const std::string& mod, int B, const void* in_u8, const
         int cq_shift = 3;
         if (L.Cout_p == 32 && L.Cout <= 16) cq_shift = (L.Cout <= 4) ? 0 : (L.Cout <= 8) ? 1 : 2;
         const unsigned gx = (unsigned)(((long long)total * (1 << cq_shift) + 255) / 256);
-        if (in_u8 && px1)
-            hipLaunchKernelGGL((k_conv_direct<true, 1>), dim3(gx, L.Cout_p / 32), dim3(256), 0, h->stream, in_u8, 0LL, 0, 0, in.H, in.W, 3,
-                               L.d_w, L.d_scale, L.d_shift, L.Cout_p, out.base, out.frame_stride(), out.Ctot, out.off, Hout, Wout,
-                               L.ks, L.stride, pad, L.act, total, cq_shift);
-        else if (in_u8)
-            hipLaunchKernelGGL(k_conv_direct<true>, dim3(gx, L.Cout_p / 32), dim3(256), 0, h->stream, in_u8, 0LL, 0, 0, in.H, in.W, 3,
-                               L.d_w, L.d_scale, L.d_shift, L.Cout_p, out.base, out.frame_stride(), out.Ctot, out.off, Hout, Wout,
-                               L.ks, L.stride, pad, L.act, total, cq_shift);
-        else if (px1)
-            hipLaunchKernelGGL((k_conv_direct<false, 1>), dim3(gx, L.Cout_p / 32), dim3(256), 0, h->stream, (const void*)in.base,
-                               in.frame_stride(), in.Ctot, in.off, in.H, in.W, L.Cin, L.d_w, L.d_scale, L.d_shift, L.Cout_p, out.base,
-                               out.frame_stride(), out.Ctot, out.off, Hout, Wout, L.ks, L.stride, pad, L.act, total, cq_shift);
+        // (the stride-2 convs behind model.0 run on the MFMA kernel, MODE 3: the only direct conv reads the u8 frame)
+        if (!in_u8) return fail(OG_ESTATE, "the direct conv reads the u8 frame only: " + L.name);
+        if (px1)
+            OG_LAUNCH((k_conv_direct<true, 1>), dim3(gx, L.Cout_p / 32), dim3(256), 0, h->stream, in_u8, 0LL, 0, 0, in.H, in.W, 3,
+                      L.d_w, L.d_scale, L.d_shift, L.Cout_p, out.base, out.frame_stride(), out.Ctot, out.off, Hout, Wout,
+                      L.ks, L.stride, pad, L.act, total, cq_shift);
         else
-            hipLaunchKernelGGL(k_conv_direct<false>, dim3(gx, L.Cout_p / 32), dim3(256), 0, h->stream, (const void*)in.base,
-                               in.frame_stride(), in.Ctot, in.off, in.H, in.W, L.Cin, L.d_w, L.d_scale, L.d_shift, L.Cout_p, out.base,
-                               out.frame_stride(), out.Ctot, out.off, Hout, Wout, L.ks, L.stride, pad, L.act, total, cq_shift);
-        HIPCHK(hipGetLastError());
+            OG_LAUNCH(k_conv_direct<true>, dim3(gx, L.Cout_p / 32), dim3(256), 0, h->stream, in_u8, 0LL, 0, 0, in.H, in.W, 3,
+                      L.d_w, L.d_scale, L.d_shift, L.Cout_p, out.base, out.frame_stride(), out.Ctot, out.off, Hout, Wout,
+                      L.ks, L.stride, pad, L.act, total, cq_shift);
+        plan_inst(px1 ? "k_conv_direct<true, 1> cq_shift=%d" : "k_conv_direct<true, 4> cq_shift=%d", cq_shift);
         return OG_OK;
     }
     ConvArgs a;
@@ -616,12 +629,14 @@ struct YNet {
             i2.off = in_segs.front().off;
             YView o2 = out;
             o2.off = out_segs.front().off;
+            g_launch_mod = mod.c_str();
             rc = y_launch(h, mod, B, first ? in_u8 : nullptr, i2, o2, res);
-            if (mod.compare(0, 12, "model.22.hd.") != 0) h->acts[mod] = YAct{out, out_segs};   // every Conv's output by its module path
+            g_launch_mod = nullptr;
+            if (!h->host_only && mod.compare(0, 12, "model.22.hd.") != 0) h->acts[mod] = YAct{out, out_segs};   // every Conv's output by its module path
         }
     }
     void name(const std::string& n, const YView& v) {
-        if (mode == 2) h->acts[n] = YAct{v, {{v.off, v.C}}};
+        if (mode == 2 && !h->host_only) h->acts[n] = YAct{v, {{v.off, v.C}}};
     }
 
     // C2f (ultralytics nn/modules/block.py): cv1 1x1 -> split in two -> n Bottlenecks(3x3,3x3) chained on the
@@ -644,13 +659,51 @@ struct YNet {
         name(p, seg(out, out_off, c2));
     }
 
-    void upsample(const YView& in, const YView& out, int out_off) {
+    void upsample(const char* mod, const YView& in, const YView& out, int out_off) {
         if (rc || mode != 2) return;
         const int C4 = cp32(in.C) / (4 * in.es);   // 16-byte pieces per pixel: 4 f32 or 8 f16 channels
         const long long total = (long long)B * out.H * out.W * C4;
-        hipLaunchKernelGGL(k_upsample2, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, in.base, in.fs4(),
-                           in.ps4(), in.off4(), out.base, out.fs4(), out.ps4(), out_off / out.es, C4, out.H, out.W, total);
-        if (hipGetLastError() != hipSuccess) rc = fail(OG_EHIP, "k_upsample2 launch failed");
+        g_launch_mod = mod;
+        rc = [&]() -> int {
+            OG_LAUNCH(k_upsample2, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, in.base, in.fs4(),
+                      in.ps4(), in.off4(), out.base, out.fs4(), out.ps4(), out_off / out.es, C4, out.H, out.W, total);
+            return OG_OK;
+        }();
+        g_launch_mod = nullptr;
+    }
+
+    // the three chained 5x5 max-pools of the SPPF, in place in its concat buffer
+    int pools(const YView& sp, int csp, int H5, int W5) {
+        if (h->precision == 2) {   // packed f16 max, 8 channels per thread; one-frame calls take it too
+            const long long total = (long long)B * H5 * W5 * (csp / 8);
+            for (int j = 0; j < 3; ++j) {
+                const std::string m = "model.9.m." + std::to_string(j + 1);
+                g_launch_mod = m.c_str();
+                OG_LAUNCH(k_maxpool5_h, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, sp.base, sp.base,
+                          sp.fs4(), sp.ps4(), j * csp / 2, (j + 1) * csp / 2, csp / 8, H5, W5, total);
+            }
+        } else if (B <= h->latency_batch && H5 * W5 <= 224) {   // one launch: the map's 32-channel slabs pooled in LDS
+            g_launch_mod = "model.9.m.1-3";
+            OG_LAUNCH(k_sppf_pools, dim3(csp / 32, B), dim3(256), (size_t)H5 * W5 * 256, h->stream, sp.base, sp.frame_stride(), sp.Ctot, csp, H5, W5);
+        } else {
+            const long long total = (long long)B * H5 * W5 * (csp / 4);
+            for (int j = 0; j < 3; ++j) {
+                const std::string m = "model.9.m." + std::to_string(j + 1);
+                g_launch_mod = m.c_str();
+                OG_LAUNCH(k_maxpool5, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, sp.base, sp.base,
+                          sp.frame_stride(), sp.Ctot, j * csp, (j + 1) * csp, csp / 4, H5, W5, total);
+            }
+        }
+        return OG_OK;
+    }
+
+    int decode(const YoloDecodeArgs& da) {
+        g_launch_mod = "model.22";
+        if (B <= h->latency_batch && h->d_cand && (da.n_anchors + 63) / 64 <= og_yolo::kDecBlocks)
+            OG_LAUNCH(k_yolo_decode_mb, dim3((da.n_anchors + 63) / 64, B), dim3(256), 0, h->stream, da, h->d_cand, h->d_dec_counter);
+        else
+            OG_LAUNCH(k_yolo_decode, dim3(B), dim3(256), 0, h->stream, da);
+        return OG_OK;
     }
 
     void run() {
@@ -672,25 +725,25 @@ struct YNet {
         conv("model.0", false, 3, 2, 2, in0, {{0, 3}}, t0, {{0, c0}}, nullptr, true);
         name("model.0", seg(t0, 0, c0));
         YView t1 = alloc(cp32(c1), H2, W2);
-        conv("model.1", false, h->s2_mfma ? 4 : 3, 2, 2, t0, {{0, c0}}, t1, {{0, c1}});
+        conv("model.1", false, 4, 2, 2, t0, {{0, c0}}, t1, {{0, c1}});
         name("model.1", seg(t1, 0, c1));
         YView t2 = alloc(cp32(c1), H2, W2);
         c2f(2, h->n_c2f[0], true, t1, {{0, c1}}, c1, t2, 0);
         YView t3 = alloc(cp32(c3), H3, W3);
-        conv("model.3", false, h->s2_mfma ? 4 : 3, 2, 2, t2, {{0, c1}}, t3, {{0, c3}});
+        conv("model.3", false, 4, 2, 2, t2, {{0, c1}}, t3, {{0, c3}});
         name("model.3", seg(t3, 0, c3));
         // concat buffers of the neck, laid out [upsampled | lateral] (Concat([up, backbone]) order)
         YView cat14 = alloc(cp32(c12) + cp32(c3), H3, W3);   // [up(12) , 4]
         c2f(4, h->n_c2f[1], true, t3, {{0, c3}}, c3, cat14, cp32(c12));
         YView t4 = seg(cat14, cp32(c12), c3);
         YView t5 = alloc(cp32(c5), H4, W4);
-        conv("model.5", false, h->s2_mfma ? 4 : 3, 2, 2, t4, {{t4.off, c3}}, t5, {{0, c5}});
+        conv("model.5", false, 4, 2, 2, t4, {{t4.off, c3}}, t5, {{0, c5}});
         name("model.5", seg(t5, 0, c5));
         YView cat11 = alloc(cp32(c7) + cp32(c5), H4, W4);     // [up(9), 6]
         c2f(6, h->n_c2f[2], true, t5, {{0, c5}}, c5, cat11, cp32(c7));
         YView t6 = seg(cat11, cp32(c7), c5);
         YView t7 = alloc(cp32(c7), H5, W5);
-        conv("model.7", false, h->s2_mfma ? 4 : 3, 2, 2, t6, {{t6.off, c5}}, t7, {{0, c7}});
+        conv("model.7", false, 4, 2, 2, t6, {{t6.off, c5}}, t7, {{0, c7}});
         name("model.7", seg(t7, 0, c7));
         YView t8 = alloc(cp32(c7), H5, W5);
         c2f(8, h->n_c2f[3], true, t7, {{0, c7}}, c7, t8, 0);
@@ -698,32 +751,22 @@ struct YNet {
         const int cs = c7 / 2, csp = cp32(cs);
         YView sp = alloc(4 * csp, H5, W5);
         conv("model.9.cv1", false, 2, 1, 2, t8, {{0, c7}}, sp, {{0, cs}});
-        if (!rc && mode == 2 && h->precision == 2) {   // packed f16 max, 8 channels per thread; one-frame calls take it too
-            const long long total = (long long)B * H5 * W5 * (csp / 8);
-            for (int j = 0; j < 3; ++j)
-                hipLaunchKernelGGL(k_maxpool5_h, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, sp.base, sp.base,
-                                   sp.fs4(), sp.ps4(), j * csp / 2, (j + 1) * csp / 2, csp / 8, H5, W5, total);
-        } else if (!rc && mode == 2 && B <= h->latency_batch && H5 * W5 <= 224) {   // one launch: the map's 32-channel slabs pooled in LDS
-            hipLaunchKernelGGL(k_sppf_pools, dim3(csp / 32, B), dim3(256), (size_t)H5 * W5 * 256, h->stream, sp.base, sp.frame_stride(), sp.Ctot, csp, H5, W5);
-        } else if (!rc && mode == 2) {
-            const long long total = (long long)B * H5 * W5 * (csp / 4);
-            for (int j = 0; j < 3; ++j)
-                hipLaunchKernelGGL(k_maxpool5, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, sp.base, sp.base,
-                                   sp.frame_stride(), sp.Ctot, j * csp, (j + 1) * csp, csp / 4, H5, W5, total);
+        if (!rc && mode == 2) {
+            rc = pools(sp, csp, H5, W5);
+            g_launch_mod = nullptr;
         }
-        if (!rc && mode == 2 && hipGetLastError() != hipSuccess) rc = fail(OG_EHIP, "SPPF pool launch failed");
         for (int j = 1; j <= 3; ++j) name("model.9.m." + std::to_string(j), seg(sp, j * csp, cs));   // the three chained pools
         YView cat20 = alloc(cp32(c18) + cp32(c7), H5, W5);    // [19, 9]
         conv("model.9.cv2", false, 2, 1, 2, sp, {{0, cs}, {csp, cs}, {2 * csp, cs}, {3 * csp, cs}}, cat20, {{cp32(c18), c7}});
         YView t9 = seg(cat20, cp32(c18), c7);
         name("model.9", t9);
         // ---- neck ----
-        upsample(t9, cat11, 0);
+        upsample("model.10", t9, cat11, 0);
         name("model.10", seg(cat11, 0, c7));
         YView cat17 = alloc(cp32(c15) + cp32(c12), H4, W4);   // [16, 12]
         c2f(12, h->n_c2f[4], false, cat11, {{0, c7}, {cp32(c7), c5}}, c12, cat17, cp32(c15));
         YView t12 = seg(cat17, cp32(c15), c12);
-        upsample(t12, cat14, 0);
+        upsample("model.13", t12, cat14, 0);
         name("model.13", seg(cat14, 0, c12));
         // ---- Detect (model.22): per level a box branch (-> 4*reg_max DFL logits) and a class branch, three convs each;
         //      one-frame calls run the two branches as one chain of three (y_synth_head)
@@ -786,12 +829,12 @@ struct YNet {
         YView t15 = alloc(cp32(c15), H3, W3);
         c2f(15, h->n_c2f[5], false, cat14, {{0, c12}, {cp32(c12), c3}}, c15, t15, 0);
         head(0, t15, c15);
-        conv("model.16", false, h->s2_mfma ? 4 : 3, 2, 2, t15, {{0, c15}}, cat17, {{0, c16}});
+        conv("model.16", false, 4, 2, 2, t15, {{0, c15}}, cat17, {{0, c16}});
         name("model.16", seg(cat17, 0, c16));
         YView t18 = alloc(cp32(c18), H4, W4);
         c2f(18, h->n_c2f[6], false, cat17, {{0, c16}, {cp32(c15), c12}}, c18, t18, 0);
         head(1, t18, c18);
-        conv("model.19", false, h->s2_mfma ? 4 : 3, 2, 2, t18, {{0, c18}}, cat20, {{0, c19}});
+        conv("model.19", false, 4, 2, 2, t18, {{0, c18}}, cat20, {{0, c19}});
         name("model.19", seg(cat20, 0, c19));
         YView t21 = alloc(cp32(c21), H5, W5);
         c2f(21, h->n_c2f[7], false, cat20, {{0, c19}, {cp32(c18), c7}}, c21, t21, 0);
@@ -803,11 +846,8 @@ struct YNet {
         da.img_h = (float)H;
         da.pred = pred;
         da.best = best;
-        if (B <= h->latency_batch && h->d_cand && (da.n_anchors + 63) / 64 <= og_yolo::kDecBlocks)
-            hipLaunchKernelGGL(k_yolo_decode_mb, dim3((da.n_anchors + 63) / 64, B), dim3(256), 0, h->stream, da, h->d_cand, h->d_dec_counter);
-        else
-            hipLaunchKernelGGL(k_yolo_decode, dim3(B), dim3(256), 0, h->stream, da);
-        if (hipGetLastError() != hipSuccess) rc = fail(OG_EHIP, "k_yolo_decode launch failed");
+        rc = decode(da);
+        g_launch_mod = nullptr;
     }
 };
 
@@ -880,6 +920,11 @@ og_yolo* og_yolo_create(int nc) {
 
 void og_yolo_destroy(og_yolo* h) {
     if (!h) return;
+    if (h->plan_copy) og_yolo_destroy(h->plan_copy);
+    if (h->host_only) {   // placeholders only: nothing to release on any device
+        delete h;
+        return;
+    }
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (auto& kv : h->convs)
         for (float* p : {kv.second.d_w, kv.second.d_w1, kv.second.d_wf, kv.second.d_scale, kv.second.d_shift})
@@ -914,6 +959,10 @@ int og_yolo_set_tensor(og_yolo* h, const char* key, const void* host, const int6
     }
     t.data.assign((const float*)host, (const float*)host + n);
     h->host[k] = std::move(t);
+    if (h->plan_copy) {
+        og_yolo_destroy(h->plan_copy);
+        h->plan_copy = nullptr;
+    }
     return OG_OK;
 }
 
@@ -933,6 +982,23 @@ int og_yolo_finalize(og_yolo* h) {
             if (d.data[i] != (float)i) return fail(OG_EINVAL, "model.22.dfl.conv.weight is not arange(16)");
     }
     int rc;
+    if (h->host_only) {   // og_yolo_plan: no device -- every workspace "exists", upload() hands out placeholders (y_build_conv packs nothing)
+        h->d_zero = (float*)8;
+        h->d_partial = (float*)8;
+        h->d_tile_counter = (int*)8;
+        h->d_cand = (float*)8;
+        h->d_dec_counter = (int*)8;
+        h->d_range = (int*)8;
+        h->head_synth = y_synth_head(h);
+        for (auto& kv : h->host)
+            if (!kv.second.shape.empty()) h->couts[kv.first] = (int)kv.second.shape[0];
+        YNet b{h, 1, 32, 32, 0, nullptr};
+        b.run();
+        if (b.rc) return b.rc;
+        h->host.clear();
+        h->finalized = true;
+        return OG_OK;
+    }
     if ((rc = init_kernel_attrs())) return rc;
     if ((rc = set_conv_fy_attr<1, 0, false>()) || (rc = set_conv_fy_attr<2, 0, false>()) || (rc = set_conv_fy_attr<1, 2, false>()) ||
         (rc = set_conv_fy_attr<2, 2, false>()) || (rc = set_conv_fy_attr<1, 2, true>()) || (rc = set_conv_fy_attr<2, 2, true>()) ||
@@ -984,6 +1050,7 @@ int og_yolo_set_option(og_yolo* h, const char* name, int value) {
     else if (n == "precision" && (value == 0 || value == 2)) slot = &h->precision;   // (no split precision, 1, for the detector)
     else if (n == "source_stage_kib" && value >= 1 && value <= (1 << 24)) slot = &h->source_stage_kib;
     else if (n == "source_mapped" && (value == 0 || value == 1)) slot = &h->source_mapped;
+    else if (n == "trace_launches" && (value == 0 || value == 1)) slot = &h->trace_launches;
     if (!slot) return fail(OG_EINVAL, "unknown detector option or value out of range: " + n);
     if (h->stream) HIPCHK(hipStreamSynchronize(h->stream));
     if (slot == &h->precision && value != h->precision && h->arena) {   // other buffer sizes: the next call plans the arena anew
@@ -994,6 +1061,98 @@ int og_yolo_set_option(og_yolo* h, const char* name, int value) {
     }
     *slot = value;
     return OG_OK;
+}
+
+int og_yolo_plan(og_yolo* h, int B, int H, int W, int n_cu, const char* options, char* out, size_t cap, long long* arena_bytes) {
+    if (!h || !out || cap == 0 || B < 1 || n_cu < 0) return fail(OG_EINVAL, "bad argument");
+    if (h->finalized) return fail(OG_ESTATE, "og_yolo_plan takes a handle that has its tensors and is not finalized");
+    if (H <= 0 || W <= 0 || H % 32 || W % 32) return fail(OG_EINVAL, "H and W must be positive multiples of 32 (letterbox on the host first)");
+    // a host-only copy: the options and the tensors' SHAPES (no launch decision reads a weight)
+    int rc = OG_OK;
+    if (!h->plan_copy) {
+        og_yolo* c0 = new og_yolo();
+        c0->host_only = true;
+        c0->nc = h->nc;
+        c0->reg_max = h->reg_max;
+        for (auto& kv : h->host) {
+            if (kv.first == "model.22.dfl.conv.weight") continue;   // (values, checked by the real finalize)
+            c0->host[kv.first].shape = kv.second.shape;
+        }
+        if ((rc = og_yolo_finalize(c0))) {
+            og_yolo_destroy(c0);
+            return rc;
+        }
+        h->plan_copy = c0;
+    }
+    og_yolo* c = h->plan_copy;
+    c->latency_batch = h->latency_batch;
+    c->zero_copy = h->zero_copy;
+    c->splitk_slots = h->splitk_slots;
+    c->splitk_div = h->splitk_div;
+    c->splitk_max = h->splitk_max;
+    c->splitk_min_steps = h->splitk_min_steps;
+    c->latency_nt1 = h->latency_nt1;
+    c->head_fused = h->head_fused;
+    c->precision = h->precision;
+    c->arena = nullptr;
+    c->acts.clear();
+    c->n_cu = n_cu > 0 ? n_cu : 256;
+    std::string opt = options ? options : "";
+    for (size_t p0 = 0; !rc && p0 < opt.size();) {   // "name=value,name=value"
+        size_t p1 = opt.find(',', p0);
+        if (p1 == std::string::npos) p1 = opt.size();
+        const std::string kv = opt.substr(p0, p1 - p0);
+        const size_t eq = kv.find('=');
+        if (eq == std::string::npos) rc = fail(OG_EINVAL, "option without '=': " + kv);
+        else rc = og_yolo_set_option(c, kv.substr(0, eq).c_str(), atoi(kv.c_str() + eq + 1));
+        p0 = p1 + 1;
+    }
+    Plan plan;
+    if (!rc) {
+        constexpr int kMaxLaunch = 512;   // og_yolo_detect_u8_dev's: the first chain of a larger call
+        const int nb = B < kMaxLaunch ? B : kMaxLaunch;
+        if (arena_bytes) {   // (the sizing pass of y_ensure_arena; the chain below makes the same checks)
+            YNet size{c, nb, H, W, 1, nullptr};
+            size.run();
+            rc = size.rc;
+            *arena_bytes = (long long)size.bump + 256;
+        }
+        if (!rc) {
+            c->arena = (void*)4096;   // a placeholder base: nothing dereferences it in a dry run
+            g_plan = &plan;
+            YNet run{c, nb, H, W, 2, (const uint8_t*)4096};
+            run.best = (float*)4096;
+            run.pred = (float*)4096;
+            run.run();
+            g_plan = nullptr;
+            g_launch_mod = nullptr;
+            rc = run.rc;
+        }
+    }
+    c->arena = nullptr;
+    if (rc) return rc;
+    std::string txt;
+    txt.reserve(plan.recs.size() * 96);
+    for (auto& r : plan.recs) {
+        char num[112];
+        snprintf(num, sizeof num, "|%u|%u|%u|%u|%u|%lld|%lld|", r.gx, r.gy, r.gz, r.block, r.lds, r.partial_bytes, r.counters);
+        txt += r.kernel;
+        txt += num;
+        txt += r.mod;
+        txt += '\n';
+    }
+    if (txt.size() + 1 > cap) return fail(OG_EINVAL, "plan text does not fit the buffer");
+    memcpy(out, txt.c_str(), txt.size() + 1);
+    return (int)plan.recs.size();
+}
+
+int og_yolo_last_launches(og_yolo* h, char* out, size_t cap) {
+    if (!h || !out || cap == 0) return fail(OG_EINVAL, "bad argument");
+    std::string txt;
+    for (auto& r : h->last_launches) txt += r.first + "|" + r.second + "\n";
+    if (txt.size() + 1 > cap) return fail(OG_EINVAL, "launch list does not fit the buffer");
+    memcpy(out, txt.c_str(), txt.size() + 1);
+    return (int)h->last_launches.size();
 }
 
 int og_yolo_num_anchors(og_yolo* h, int H, int W) {
@@ -1021,7 +1180,12 @@ int og_yolo_detect_u8_dev(og_yolo* h, const uint8_t* bgr_dev, int B, int H, int 
         run.conf = conf;
         run.best = best_dev + (size_t)b0 * 5;
         run.pred = pred_dev ? pred_dev + (size_t)b0 * A * 5 : nullptr;
+        if (h->trace_launches) {
+            h->last_launches.clear();
+            g_trace = &h->last_launches;
+        }
         run.run();
+        g_trace = nullptr;
         h->lastB = nb;
         if (run.rc) return run.rc;
     }

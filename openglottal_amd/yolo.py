@@ -151,6 +151,19 @@ class YoloV8Detector:
         check(lib().og_yolo_sync(self._h), "og_yolo_sync")
         return best.cpu().numpy()
 
+    def last_launches(self) -> list:
+        """``[(label, module)]`` of the last kernel chain, the labels ``YoloPlanner.plan`` gives (needs ``set_option("trace_launches", 1)``)."""
+        buf = C.create_string_buffer(1 << 16)
+        n = lib().og_yolo_last_launches(self._h, buf, len(buf))
+        if n < 0:
+            check(n, "og_yolo_last_launches")
+        return [tuple(l.split("|")) for l in buf.value.decode().splitlines()]
+
+    def cu_count(self) -> int:
+        import torch
+
+        return int(torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count)
+
     def launch_count(self, kernel: str) -> int:
         """Launches of ``k_letterbox_bgr`` / ``k_scale_boxes`` issued by this handle so far (for tests)."""
         n = lib().og_yolo_launch_count(self._h, kernel.encode())
@@ -273,6 +286,50 @@ class YoloV8Detector:
         check(lib().og_yolo_get_activation(self._h, name.encode(), B, ptr(buf), cap, dims), f"og_yolo_get_activation({name})")
         c, h, w = dims[0], dims[1], dims[2]
         return buf[: B * c * h * w].reshape(B, c, h, w).copy()
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                lib().og_yolo_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+class YoloPlanner:
+    """Dry runs of the detector's launch decisions without a device (``og_yolo_plan``): an unfinalized handle that holds the
+    tensors of ``weights`` (only their shapes are read)."""
+
+    FIELDS = ("gx", "gy", "gz", "block", "lds", "ws", "cnt")
+
+    def __init__(self, weights, nc: int = 1) -> None:
+        h = lib().og_yolo_create(nc)
+        if not h:
+            check(-1, "og_yolo_create")
+        self._h = h
+        for k, v in weights.items():
+            if k.endswith("num_batches_tracked"):
+                continue
+            v = np.ascontiguousarray(v, dtype=np.float32)
+            shp = (C.c_int64 * max(1, v.ndim))(*v.shape)
+            check(lib().og_yolo_set_tensor(h, k.encode(), ptr(v), shp, v.ndim, _lib.OG_DTYPE_F32), f"set_tensor({k})")
+        self._buf = C.create_string_buffer(1 << 16)
+
+    def plan_text(self, B: int, H: int, W: int, n_cu: int = 0, options: str = "", want_arena: bool = True) -> str:
+        arena = C.c_longlong(0)
+        n = lib().og_yolo_plan(self._h, B, H, W, n_cu, options.encode(), self._buf, len(self._buf), C.byref(arena) if want_arena else None)
+        if n < 0:
+            check(n, "og_yolo_plan")
+        self.arena_bytes = arena.value if want_arena else None
+        return self._buf.value.decode()
+
+    def plan(self, B: int, H: int, W: int, n_cu: int = 0, options: str = "") -> list:
+        """One dict per launch: kernel (the label), gx, gy, gz, block, lds, ws (split-K workspace bytes), cnt (arrival counters), module."""
+        out = []
+        for line in self.plan_text(B, H, W, n_cu, options).splitlines():
+            f = line.split("|")
+            out.append(dict(kernel=f[0], module=f[8], **{k: int(v) for k, v in zip(self.FIELDS, f[1:8])}))
+        return out
 
     def __del__(self):
         try:

@@ -152,6 +152,8 @@ EXEMPT = {
     "og_unet_clock_probe_raw": "diagnostic: a fixed 4 x 1024 table; not on the product path",
     "og_unet_plan": "plan recorder: host text bounded by cap (tests/test_launch_plan.py)",
     "og_unet_plan_resized": "plan recorder: host text bounded by cap (tests/test_resize_host.py)",
+    "og_yolo_plan": "plan recorder: host text bounded by cap (tests/test_yolo_layer_ref_f32.py)",
+    "og_yolo_last_launches": "diagnostic recorder: host text bounded by cap (tests/test_yolo_layer_ref_f32.py); not on the product path",
 }
 HOST_ONLY = {"og_bgr2gray_host", "og_linear_taps_host", "og_yolo_letterbox_host", "og_yolo_letterbox_geometry"}   # above
 

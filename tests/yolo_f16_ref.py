@@ -24,7 +24,8 @@ import numpy as np
 
 from oracle import layer_ref as LR
 from oracle.layer_ref import KAPPA, U
-from oracle.yolo_oracle import BN_EPS
+from oracle.yolo_layer_ref import A, affine, gather, launches, tap_names   # noqa: F401  (the chain's description: shared with the f32 reference)
+from oracle.yolo_layer_ref import wkey as _wkey
 
 KAPPA_F16 = KAPPA["f16"]
 SILU_ULPS = 4.0
@@ -34,71 +35,6 @@ YOLO_F16_EMULATED_MAX = 2.0
 YOLO_F16_SHARP_SHARE = 0.85   # measured 0.868
 
 
-def A(name):
-    return (name, None, None)
-
-
-def launches(sd: dict) -> list:
-    """The launches of one forward pass in execution order.  ``ins`` / ``res``: (tap name, first channel, end channel)."""
-    L = []
-
-    def conv(name, ins, s=1, act=True, res=None, f32out=False, first=False):
-        L.append(dict(name=name, op="conv", ins=ins, s=s, act=act, res=res, f32out=f32out, first=first))
-
-    def c2f(p, ins, shortcut):
-        c = sd[p + ".cv1.conv.weight"].shape[0] // 2
-        conv(p + ".cv1", ins)
-        last = (p + ".cv1", c, 2 * c)
-        cat = [(p + ".cv1", 0, 2 * c)]
-        j = 0
-        while f"{p}.m.{j}.cv1.conv.weight" in sd:
-            conv(f"{p}.m.{j}.cv1", [last])
-            conv(f"{p}.m.{j}.cv2", [A(f"{p}.m.{j}.cv1")], res=last if shortcut else None)
-            last = A(f"{p}.m.{j}.cv2")
-            cat.append(last)
-            j += 1
-        conv(p + ".cv2", cat)
-
-    conv("model.0", [A("input")], 2, first=True)
-    conv("model.1", [A("model.0")], 2)
-    c2f("model.2", [A("model.1")], True)
-    conv("model.3", [A("model.2.cv2")], 2)
-    c2f("model.4", [A("model.3")], True)
-    conv("model.5", [A("model.4.cv2")], 2)
-    c2f("model.6", [A("model.5")], True)
-    conv("model.7", [A("model.6.cv2")], 2)
-    c2f("model.8", [A("model.7")], True)
-    conv("model.9.cv1", [A("model.8.cv2")])
-    prev = "model.9.cv1"
-    for j in (1, 2, 3):
-        L.append(dict(name=f"model.9.m.{j}", op="pool", ins=[A(prev)]))
-        prev = f"model.9.m.{j}"
-    conv("model.9.cv2", [A("model.9.cv1"), A("model.9.m.1"), A("model.9.m.2"), A("model.9.m.3")])
-    L.append(dict(name="model.10", op="up", ins=[A("model.9.cv2")]))
-    c2f("model.12", [A("model.10"), A("model.6.cv2")], False)
-    L.append(dict(name="model.13", op="up", ins=[A("model.12.cv2")]))
-    c2f("model.15", [A("model.13"), A("model.4.cv2")], False)
-    conv("model.16", [A("model.15.cv2")], 2)
-    c2f("model.18", [A("model.16"), A("model.12.cv2")], False)
-    conv("model.19", [A("model.18.cv2")], 2)
-    c2f("model.21", [A("model.19"), A("model.9.cv2")], False)
-    for l, f in enumerate(["model.15.cv2", "model.18.cv2", "model.21.cv2"]):
-        for br in ("cv2", "cv3"):
-            p = f"model.22.{br}.{l}"
-            conv(p + ".0", [A(f)])
-            conv(p + ".1", [A(p + ".0")])
-            conv(p + ".2", [A(p + ".1")], act=False, f32out=True)
-    return L
-
-
-def tap_names(sd: dict) -> list:
-    return [s["name"] for s in launches(sd)]
-
-
-def _wkey(sd, p):
-    return p + ".conv.weight" if p + ".conv.weight" in sd else p + ".weight"
-
-
 def device_weights(sd: dict) -> dict:
     """The tensors an f16-mode detector holds: the weights of every MFMA conv (all but ``model.0``) rounded to f16 once."""
     out = dict(sd)
@@ -106,21 +42,6 @@ def device_weights(sd: dict) -> dict:
         if np.ndim(v) == 4 and k.endswith(".weight") and not k.startswith("model.0.") and ".dfl." not in k:
             out[k] = np.asarray(v, np.float32).astype(np.float16).astype(np.float32)
     return out
-
-
-def affine(sd: dict, p: str):
-    """(scale, shift) as the device folds them (float64 arithmetic, each rounded to f32 once) and |s mu| + |beta|."""
-    if p + ".bn.weight" in sd:
-        g, b, mu, var = (np.asarray(sd[p + ".bn." + f], np.float64) for f in ("weight", "bias", "running_mean", "running_var"))
-        s = g / np.sqrt(var + BN_EPS)
-        return s.astype(np.float32), (b - mu * s).astype(np.float32), np.abs(s * mu) + np.abs(b)
-    bk = p + ".conv.bias" if p + ".conv.bias" in sd else p + ".bias"
-    b = np.asarray(sd[bk], np.float32) if bk in sd else np.zeros(sd[_wkey(sd, p)].shape[0], np.float32)
-    return np.ones_like(b), b, np.abs(b.astype(np.float64))
-
-
-def gather(taps: dict, ins) -> np.ndarray:
-    return np.concatenate([np.asarray(taps[n])[:, lo:hi] for n, lo, hi in ins], 1)
 
 
 def _t64(v):

@@ -1152,6 +1152,165 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_o(ConvArgs a) {
     }
 }
 
+// a + b and a - b on a register pair as ONE packed instruction each (og_add4 / og_sub4 on half the width).  Volatile: the output
+// transform of k_conv_wino needs them in source order, between the pins of its accumulators (see there).
+__device__ __forceinline__ f32x2 og_add2(f32x2 a, f32x2 b) {
+    f32x2 r;
+    asm volatile("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ f32x2 og_sub2(f32x2 a, f32x2 b) {
+    f32x2 r;
+    asm volatile("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+
+// Tile end of k_conv_wino: conv_epilogue_b's arithmetic in the same order (fmaf(acc, scale, shift), ReLU, pool maxima, the fused
+// head; the same LDS transposition, so every 16-byte store stays line-contiguous) on the PAIR layout the output transform leaves:
+// p[mp][g][rr] = element (g, rr) of sub-tiles 2 mp (.x) and 2 mp + 1 (.y) -- the register pair (r, r + 1) of an accumulator slot.
+// Two sub-tiles are finished per step: BN is one v_pk_fma_f32 on the pair, the two images go to two scratch areas of the wave
+// (5 KB apart), so nothing is re-paired on the way.  What a launch wants is a template parameter (ACT, POOL, HEAD: 0 none, 1 fused
+// head, 2 fused head and the activation stored as well), chosen once per tile by the caller -- no feature test inside a step --
+// and every store address is lane offset (fixed for the tile; the 16-byte group q rides in it) + ONE running SGPR offset per
+// stream, bumped by an add per sub-tile.  Optional head outputs (logits, mask) are switched off through a buffer of zero
+// records, whose bounds check drops the store, not through a branch.  No row test: k_conv_wino only runs on maps its tiles cover
+// exactly (H a multiple of the tile height, W of 16: launch_conv, use_wino).
+template <int NT, int ACT, bool POOL, int HEAD>
+__device__ __forceinline__ void wino_tile_end(const ConvArgs& a, const f32x2 (&p)[2][4][4], int n_tile, int b, int ty0, int tx0, int wm, int wn,
+                                              int li, int lh, float sc, float sh, unsigned char* scratch) {
+    static_assert(NT == 1 || HEAD == 0, "the fused head sits on a 32-column layer");
+    constexpr int AREA = 1280;                     // floats between the scratch areas of a pair's two sub-tiles (32 x 32 tile + 8 x 32 pooled)
+    const int lane = li + 32 * lh;
+    const int cbase = n_tile * 32 * NT + wn * 32;
+    const int W = a.W;
+    const int ys = ty0 + 8 * wm;                   // first pixel row of this wave's four sub-tiles (two rows each)
+    // read-back role of this lane: pixel row (rrow + 8q) of the 32-row sub-tile, channels rc4..rc4+3
+    const int rrow = lane >> 3, rc4 = (lane & 7) * 4;
+    const int xl = 2 * (rrow >> 2) + (rrow & 1), yl = (rrow & 3) >> 1;
+
+    const __amdgpu_buffer_rsrc_t out_rs = og_rsrc(a.out + (long long)b * a.out_frame_stride, (unsigned)a.out_frame_stride * 4u);
+    unsigned vq[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        vq[q] = (tx0 + xl + 4 * q < W) ? (unsigned)(((yl * W + xl + 4 * q) * a.out_pix_stride + rc4) * 4) : OG_OOB;
+    unsigned so = (unsigned)(((ys * W + tx0) * a.out_pix_stride + a.out_ch_off + cbase) * 4);
+    const unsigned so_step = (unsigned)(2 * W * a.out_pix_stride * 4);
+
+    // accumulator-layout role: channel li, pixel rows 8g + 4lh + rr
+    float* const fw = (float*)scratch + (128 * lh + li);              // + (8g + rr) * 32
+    const float* const fr = (const float*)scratch + rrow * 32 + rc4;  // + q * 256
+    __amdgpu_buffer_rsrc_t pool_rs = out_rs;
+    unsigned vpool = 0, pso = 0, pso_step = 0;
+    if (POOL) {
+        pool_rs = og_rsrc(a.pool + (long long)b * a.pool_frame_stride, (unsigned)a.pool_frame_stride * 4u);
+        vpool = (tx0 + 2 * rrow < W) ? (unsigned)((rrow * a.pool_pix_stride + rc4) * 4) : OG_OOB;
+        pso = (unsigned)((((ys >> 1) * (W >> 1) + (tx0 >> 1)) * a.pool_pix_stride + a.pool_ch_off + cbase) * 4);
+        pso_step = (unsigned)((W >> 1) * a.pool_pix_stride * 4);
+    }
+    // fused head: weights of this lane's 4 channels, loaded once ahead of every store; one pixel per lane k < 4
+    f32x4 wv = {0.f, 0.f, 0.f, 0.f};
+    int hbx1 = 0, hby1 = 0, hbx2 = 1 << 30, hby2 = 1 << 30, head_cnt = 0;
+    const int hk = lane & 7;
+    unsigned vh = OG_OOB;      // pixel offset (elements) of this lane's head pixel inside the frame, relative to the sub-tile origin
+    unsigned hso = 0;          // the sub-tile origin (elements)
+    __amdgpu_buffer_rsrc_t lrs = out_rs, mrs = out_rs;
+    if (HEAD) {
+        wv = *(const f32x4*)(a.head_w + rc4);
+        if (a.head_boxes != nullptr) {
+            hbx1 = a.head_boxes[b * 4 + 0];
+            hby1 = a.head_boxes[b * 4 + 1];
+            hbx2 = a.head_boxes[b * 4 + 2];
+            hby2 = a.head_boxes[b * 4 + 3];
+            if (hbx1 < 0) { hbx1 = hby1 = hbx2 = hby2 = 0; }  // "no detection" -> area 0 (features.py:241-242)
+        }
+        if (hk < 4 && tx0 + xl + 4 * hk < W) vh = (unsigned)(yl * W + xl + 4 * hk);
+        hso = (unsigned)(ys * W + tx0);
+        const unsigned long long hfo = (unsigned long long)((long long)b * a.H * W);
+        lrs = og_rsrc((const void*)((unsigned long long)a.head_logits + hfo * 4ull), a.head_logits ? (unsigned)(a.H * W) * 4u : 0u);
+        mrs = og_rsrc((const void*)((unsigned long long)a.head_mask + hfo), a.head_mask ? (unsigned)(a.H * W) : 0u);
+    }
+
+    const f32x2 sc2 = {sc, sc}, sh2 = {sh, sh};
+#pragma unroll
+    for (int mp = 0; mp < 2; ++mp) {
+        f32x2 vmaxs[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+                f32x2 v = og_fma2(p[mp][g][rr], sc2, sh2);
+                if (ACT == 1) v = f32x2{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f)};
+                fw[(8 * g + rr) * 32] = v.x;
+                fw[AREA + (8 * g + rr) * 32] = v.y;
+                if (POOL) vmaxs[g] = (rr == 0) ? v : f32x2{fmaxf(vmaxs[g].x, v.x), fmaxf(vmaxs[g].y, v.y)};
+            }
+        }
+        if (POOL) {   // pooled tiles: 8 windows x 32 channels each, behind their sub-tile's image: fs[1024 + (2g + lh) * 32 + li]
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                fw[1024 - 96 * lh + g * 64] = vmaxs[g].x;
+                fw[AREA + 1024 - 96 * lh + g * 64] = vmaxs[g].y;
+            }
+        }
+        f32x4 v4[2][4], p4[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) v4[s][q] = *(const f32x4*)(fr + s * AREA + q * 256);
+            if (POOL) p4[s] = *(const f32x4*)(fr + s * AREA + 1024);
+        }
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            if (HEAD != 1) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) og_buffer_store16(v4[s][q], out_rs, vq[q], so);
+                so += so_step;
+            }
+            if (HEAD) {
+                float sd[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    float sdot = 0.f;
+                    sdot = fmaf(v4[s][q].x, wv.x, sdot);
+                    sdot = fmaf(v4[s][q].y, wv.y, sdot);
+                    sdot = fmaf(v4[s][q].z, wv.z, sdot);
+                    sdot = fmaf(v4[s][q].w, wv.w, sdot);
+                    sdot += __shfl_xor(sdot, 1);
+                    sdot += __shfl_xor(sdot, 2);
+                    sdot += __shfl_xor(sdot, 4);
+                    sd[q] = sdot;   // every lane of the 8-lane group holds the pixel's sum
+                }
+                // lane k < 4: pixel row rrow + 8k.  Three selects on finished sums: written as one nested conditional hipcc turns this
+                // into a divergent if / else chain with the sums' last additions inside -- branches in the middle of a step
+                float mine = sd[3];
+                mine = (hk == 2) ? sd[2] : mine;
+                mine = (hk == 1) ? sd[1] : mine;
+                mine = (hk == 0) ? sd[0] : mine;
+                const float lg = mine + a.head_bias;
+                const float prob = 1.0f / (1.0f + expf(-lg));
+                const bool on = prob > a.head_thr;
+                const int x = tx0 + xl + 4 * hk, y = ys + 2 * (2 * mp + s) + yl;
+                const bool counted = on && vh != OG_OOB && x >= hbx1 && x < hbx2 && y >= hby1 && y < hby2;
+                head_cnt += __builtin_popcountll(__ballot(counted));
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, lg), lrs, (vh == OG_OOB) ? OG_OOB : vh * 4u, hso * 4u, 0);
+                __builtin_amdgcn_raw_buffer_store_b8((unsigned char)(on ? 255 : 0), mrs, vh, hso, 0);
+                hso += 2u * (unsigned)W;
+            }
+            if (POOL) {
+                og_buffer_store16(p4[s], pool_rs, vpool, pso);
+                pso += pso_step;
+            }
+        }
+    }
+    if (HEAD && a.head_area != nullptr) {
+        // one plain store per wave into a per-(frame, tile, wave) slot; k_sum_counts adds them up per frame
+        if (lane == 0) {
+            const int tile = (ty0 / 32) * a.tiles_x + (tx0 >> 4);
+            a.head_area[((long long)b * a.tiles_x * a.tiles_y + tile) * 4 + wm] = head_cnt;
+        }
+    }
+}
+
 // Winograd F(2x2, 3x3) form of the 3x3 conv for the 64-column layers, all arithmetic in f32: per 2x2 output window the
 // 4x4 input patch d becomes V = B^T d B (adds only), the 16 entries of V meet the pre-transformed weights U = G g G^T in 16
 // independent GEMMs over the input channels (MFMA), and the window's outputs are Y = A^T M A (adds only): 16 multiplies per
@@ -1163,8 +1322,9 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_o(ConvArgs a) {
 //            U ring: 2 groups of 8 positions x [64 cout][16 ch] (2 x 32 KB, LDS-DMA)
 //   per chunk  each thread transforms one (window, 4-channel) item: 16 x ds_read_b128 -> 32 vector adds -> 16 x
 //            ds_write_b128, its reads taken under the MFMAs of the chunk before; 128 MFMAs per wave
-//   epilogue the output transform runs in registers (a lane's 16 positions of one accumulator slot are one window) and
-//            hands conv_epilogue_b the direct kernel's accumulator layout: window (m = r & 3, 2 (r >> 2) + lh) of a wave
+//   tile end the output transform runs in registers (a lane's 16 positions of one accumulator slot are one window) on the
+//            register pairs (r, r + 1) = window (m = r & 3, 2 (r >> 2) + lh) of sub-tiles m and m + 1 in the direct kernel's
+//            accumulator layout, and wino_tile_end finishes two sub-tiles per step from those pairs
 // NT = 1 (the 32-column layers): the same kernel on a 32x16-pixel tile = 128 windows x 32 channels, wave wm = 32 windows x all
 //   16 positions, 8-channel chunks (V stays 64 KB: [16][128 windows][8 ch]); one K step per position instead of two, so the
 //   same side work is issued in half the MFMA steps.
@@ -1430,26 +1590,61 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino(ConvArgs a) {
     group(og_const<1>{}, og_const<0>{});
 
     if (st != nullptr && tid == 0) st[4] = __builtin_amdgcn_s_memtime();   // main loop done
-    // ---- output transform Y = A^T M A, A^T = [1 1 1 0; 0 1 -1 -1], in registers; then the shared epilogue ----
-    f32x16 o[4];
+    // ---- output transform Y = A^T M A, A^T = [1 1 1 0; 0 1 -1 -1], in registers; then the tile end ----
+    // Registers r and r + 1 (r even) of an accumulator slot are an aligned register pair = the same window element of sub-tiles
+    // m = r & 3 and m + 1, so the whole transform runs on pairs: two reads per pair and position, 24 packed adds per pair, and
+    // the pair goes to wino_tile_end as it stands (a transform per register -- what this replaces -- left hipcc 220 | 226 moves to
+    // pair registers up for its own packing, and again for conv_epilogue_b's packed BN).  The association is the canonical one
+    // (DESIGN 4.0): rows first, (m0 + m1) + m2 and (m1 - m2) - m3, then the same over columns.
+    f32x2 o[2][4][4];   // [sub-tile pair][g][2 y + x]
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        float tm[2][4];
+    for (int mp = 0; mp < 2; ++mp) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            tm[0][j] = acc[0 + j][r] + acc[4 + j][r] + acc[8 + j][r];
-            tm[1][j] = acc[4 + j][r] - acc[8 + j][r] - acc[12 + j][r];
-        }
+        for (int g = 0; g < 4; ++g) {
+            const int r = 4 * g + 2 * mp;
+            // The accumulators are pinned in front of every pair, and the packed adds are volatile statements: the 32 reads of a
+            // pair then stand between its pin and its adds.  Left alone hipcc starts the 256 reads inside the peeled last chunk,
+            // between its MFMAs, or issues them all ahead of the first add -- either way ~250 VGPRs where the loop needs 145
+            // (tools/isa_wino_loop.py, tools/isa_wino_tail.py).
 #pragma unroll
-        for (int y = 0; y < 2; ++y) {
-            o[r & 3][4 * (r >> 2) + 2 * y + 0] = tm[y][0] + tm[y][1] + tm[y][2];
-            o[r & 3][4 * (r >> 2) + 2 * y + 1] = tm[y][1] - tm[y][2] - tm[y][3];
+            for (int k = 0; k < 16; ++k) asm volatile("" : "+a"(acc[k]));
+            f32x2 tm[2][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f32x2 m0 = {acc[0 + j][r], acc[0 + j][r + 1]}, m1 = {acc[4 + j][r], acc[4 + j][r + 1]};
+                const f32x2 m2 = {acc[8 + j][r], acc[8 + j][r + 1]}, m3 = {acc[12 + j][r], acc[12 + j][r + 1]};
+                tm[0][j] = og_add2(og_add2(m0, m1), m2);
+                tm[1][j] = og_sub2(og_sub2(m1, m2), m3);
+            }
+#pragma unroll
+            for (int y = 0; y < 2; ++y) {
+                o[mp][g][2 * y + 0] = og_add2(og_add2(tm[y][0], tm[y][1]), tm[y][2]);
+                o[mp][g][2 * y + 1] = og_sub2(og_sub2(tm[y][1], tm[y][2]), tm[y][3]);
+            }
         }
     }
     if (st != nullptr && tid == 0) st[5] = __builtin_amdgcn_s_memtime();   // output transform done (wave 0)
-    unsigned char* const scr = smem + wave * 5120;   // the raw buffer is dead (>= 19 KB; the epilogue's scratch runs into V, dead too)
-    if (a.act == 1) conv_epilogue_b<NT, 0, TH, 1, false>(a, o, n_tile, b, ty0, tx0, wm, wn, li, lh, esc, esh, scr);
-    else conv_epilogue_b<NT, 0, TH, 0, false>(a, o, n_tile, b, ty0, tx0, wm, wn, li, lh, esc, esh, scr);
+    unsigned char* const scr = smem + wave * 10240;   // two 5 KB areas per wave; the raw buffer is dead (>= 19 KB) and so is V, which they run into
+    {   // the ONE choice of a tile end: what the launch wants (activation, pooled output, fused head with / without the activation stored)
+        const bool pool = a.pool != nullptr;
+        const int head = (NT == 1 && a.head_w != nullptr) ? (a.head_store_act ? 2 : 1) : 0;
+        auto end = [&](auto act_, auto pool_, auto head_) {
+            wino_tile_end<NT, decltype(act_)::value, decltype(pool_)::value != 0, decltype(head_)::value>(a, o, n_tile, b, ty0, tx0, wm, wn, li, lh, esc, esh, scr);
+        };
+        auto by_head = [&](auto act_, auto pool_) {
+            if constexpr (NT == 1) {
+                if (head == 1) end(act_, pool_, og_const<1>{});
+                else if (head == 2) end(act_, pool_, og_const<2>{});
+                else end(act_, pool_, og_const<0>{});
+            } else end(act_, pool_, og_const<0>{});
+        };
+        auto by_pool = [&](auto act_) {
+            if (pool) by_head(act_, og_const<1>{});
+            else by_head(act_, og_const<0>{});
+        };
+        if (a.act == 1) by_pool(og_const<1>{});
+        else by_pool(og_const<0>{});
+    }
     if (st != nullptr && tid == 0) {
         st[6] = __builtin_amdgcn_s_memtime();                               // epilogue issued
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

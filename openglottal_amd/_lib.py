@@ -1,4 +1,4 @@
-"""ctypes binding of ``libopenglottal_hip.so`` (include/openglottal_hip.h).
+"""ctypes binding of ``libopenglottal_hip.so`` (include/openglottal_hip.h, include/openglottal_hip_crops.h).
 
 cffi is not installed in the build image, so the thin C-ABI layer
 the north-star asks for is bound with ctypes; the declarations below are the
@@ -110,6 +110,21 @@ PROTOTYPES = {
     "og_yolo_get_activation": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
 }
 
+# name -> (restype, argtypes); the complete export list of openglottal_hip_crops.h (the YOLO-Crop+UNet video pipeline)
+CROP_PROTOTYPES = {
+    "og_crop_geometry_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "og_crop_tile_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "og_crop_project_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "og_unet_stream_crops_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_float,
+                                          C.c_void_p, C.c_void_p]),
+    "og_unet_stream_frames_crops_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                 C.c_float, C.c_void_p, C.c_void_p]),
+    "og_unet_segment_crops_area_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                    C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "og_unet_plan_crops": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                     C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
+}
+
 
 def lib() -> C.CDLL:
     """Load the HIP library once; fail loudly if it is not built."""
@@ -131,7 +146,7 @@ def lib() -> C.CDLL:
             l = C.CDLL(LIB_PATH)
         except OSError as e:  # missing libamdhip64 etc.
             raise OpenGlottalHipError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in PROTOTYPES.items():
+        for name, (res, args) in list(PROTOTYPES.items()) + list(CROP_PROTOTYPES.items()):
             fn = getattr(l, name)  # AttributeError if a symbol is missing: also loud
             fn.restype = res
             fn.argtypes = args

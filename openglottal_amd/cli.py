@@ -1,6 +1,7 @@
-"""``python -m openglottal_amd.cli run <video> --pipeline {unet,unet-only}``.
+"""``python -m openglottal_amd.cli run <video> --pipeline {unet,unet-only,yolo-crop+unet}``.
 
-Counterpart of the two U-Net branches of `openglottal/cli.py:46-103` (`_cmd_run`): same flags, same
+Counterpart of the two U-Net branches of `openglottal/cli.py:46-103` (`_cmd_run`), plus the ``yolo-crop+unet`` pipeline of
+`scripts/infer.py:222-248` (``--crop-weights``: the crop-trained U-Net checkpoint, `infer.py --crop-weights`): same flags, same
 `features.json` payload (every key of the feature dict incl. the ``_area`` waveform as a list, `cli.py:97`), same
 messages; ``--annotate`` additionally records ``pipeline``/``video`` in the file.  ``<video>`` may be a ``.npy``/``.npz`` frame stack (or an AVI when OpenCV
 is importable); weights are a torch ``state_dict`` file (U-Net, `weights_only=True`) and a flat
@@ -19,9 +20,10 @@ def main(argv=None) -> int:
     sub = ap.add_subparsers(dest="cmd", required=True)
     r = sub.add_parser("run")
     r.add_argument("video")
-    r.add_argument("--pipeline", choices=["unet", "unet-only"], default="unet-only")
-    r.add_argument("--unet-weights", required=True)
+    r.add_argument("--pipeline", choices=["unet", "unet-only", "yolo-crop+unet"], default="unet-only")
+    r.add_argument("--unet-weights", default=None, help="U-Net checkpoint (required for --pipeline unet / unet-only)")
     r.add_argument("--yolo-weights", default=None)
+    r.add_argument("--crop-weights", default=None, help="crop-trained U-Net checkpoint (required for --pipeline yolo-crop+unet)")
     r.add_argument("--device", default="cuda")
     r.add_argument("-o", "--output", default="output")
     r.add_argument("--annotate", action="store_true", help="also write the pipeline and video names into features.json")
@@ -35,20 +37,25 @@ def main(argv=None) -> int:
                         "f32 (default) or the opt-in f16 mode (f16 weights and activations, f32 accumulation, f32 logits; the "
                         "throughput mode of batched calls)")
     a = ap.parse_args(argv)
+    crop = a.pipeline == "yolo-crop+unet"
+    if crop and not a.crop_weights:
+        ap.error("--crop-weights is required for --pipeline yolo-crop+unet")
+    if not crop and not a.unet_weights:
+        r.error("the following arguments are required: --unet-weights")   # (argparse's own message: required unless yolo-crop+unet)
 
     import torch
 
-    from . import TemporalDetector, UNet, extract_features_unet
+    from . import TemporalDetector, UNet, extract_features_unet, extract_features_unet_crop
 
-    if a.pipeline == "unet" and not a.yolo_weights:
-        ap.error("--yolo-weights is required for --pipeline unet")
-    model = UNet(1, 1, (32, 64, 128, 256)).to(a.device)
-    model.load_state_dict(torch.load(a.unet_weights, map_location="cpu", weights_only=True))
+    if (a.pipeline == "unet" or crop) and not a.yolo_weights:
+        ap.error(f"--yolo-weights is required for --pipeline {a.pipeline}")
+    model = UNet(1, 1, (32, 64, 128, 256)).to(a.device)   # (yolo-crop+unet: the crop model; --precision applies to it)
+    model.load_state_dict(torch.load(a.crop_weights if crop else a.unet_weights, map_location="cpu", weights_only=True))
     model.eval()
     if a.precision != "f32":
         model.set_option("precision", {"split": 1, "f16": 2}[a.precision])
-    detector = TemporalDetector(a.yolo_weights, precision=a.detector_precision) if a.pipeline == "unet" else None
-    feats = extract_features_unet(a.video, detector, model, a.device)
+    detector = TemporalDetector(a.yolo_weights, precision=a.detector_precision) if (a.pipeline == "unet" or crop) else None
+    feats = extract_features_unet_crop(a.video, detector, model, a.device) if crop else extract_features_unet(a.video, detector, model, a.device)
     if feats is None:
         print("No glottis detected — check your weights or input video.")
         return 1

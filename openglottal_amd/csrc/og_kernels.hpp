@@ -4698,14 +4698,14 @@ __global__ __launch_bounds__(256) void k_yolo_decode_mb(YoloDecodeArgs a, float*
 // geom[b] = {pad_top, pad_left, content_h, content_w} is computed on the host (Python's round()).
 // A box with x2 <= x1 or y2 <= y1 (or x1 < 0) yields an all-zero tile / frame.
 // =======================================================================================
-__device__ __forceinline__ int og_nearest(int d, int src_len, int dst_len) {
+__host__ __device__ __forceinline__ int og_nearest(int d, int src_len, int dst_len) {
     const int s = (int)floor((double)d * ((double)src_len / (double)dst_len));
     return s < src_len - 1 ? s : src_len - 1;
 }
 
 // A box / geometry record a kernel may index with: box inside the frame, content rectangle inside the tile.  Anything
 // else (a raw TemporalDetector box passed without clamping, a stale geom) yields zeros instead of an out-of-bounds access.
-__device__ __forceinline__ bool og_crop_ok(int x1, int y1, int x2, int y2, int top, int left, int ch, int cw, int H, int W, int size) {
+__host__ __device__ __forceinline__ bool og_crop_ok(int x1, int y1, int x2, int y2, int top, int left, int ch, int cw, int H, int W, int size) {
     return x1 >= 0 && y1 >= 0 && x2 > x1 && y2 > y1 && x2 <= W && y2 <= H && top >= 0 && left >= 0 && ch > 0 && cw > 0 &&
            top + ch <= size && left + cw <= size;
 }
@@ -4871,7 +4871,7 @@ __host__ __device__ inline void og_linear_pos(int d, int src_len, int dst_len, i
 __host__ __device__ inline int og_linear_coef(float frac) { return (int)rintf(frac * 2048.0f); }
 
 template <int C>
-__device__ __forceinline__ int og_gray_at(const uint8_t* __restrict__ s, long long i) {
+__host__ __device__ __forceinline__ int og_gray_at(const uint8_t* __restrict__ s, long long i) {
     if (C == 1) return s[i];
     return (s[3 * i] * 3735 + s[3 * i + 1] * 19235 + s[3 * i + 2] * 9798 + (1 << 14)) >> 15;   // k_bgr2gray
 }
@@ -4935,6 +4935,116 @@ __global__ __launch_bounds__(256) void k_resize_out(const float* __restrict__ lo
         }
     }
     if (area) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+        if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&area[b], cnt);
+    }
+}
+
+// =======================================================================================
+// YOLO-Crop+UNet over a video (scripts/infer.py:222-248), the crop leg of the streaming engine.  Unlike k_crop_letterbox /
+// k_unletterbox_paste above, nothing is computed in Python: the letterbox scalars, the tile pixel and the projection are the
+// inline functions below, called by the kernels AND by the host twins (og_crop_*_host, tests/test_crop_host.py), so the
+// arithmetic is stated once.
+//   * og_crop_geometry = letterbox_with_info's scalars (utils.py:114-122): scale = size / max(h, w) in f64, new sides
+//     rint(side * scale) -- half to even, as Python's round() --, the odd padding pixel to the bottom / right.
+//     geom = {pad_top, pad_left, content_h, content_w}.
+//   * A USABLE box: 0 <= x1 < x2 <= W, 0 <= y1 < y2 <= H and both content sides >= 1.  A 1 x 64 box at size 32 gives
+//     round(0.5) = 0: cv2.resize raises on it and geometry.letterbox_with_info divides by zero, so in a video pass such a
+//     sliver is "no detection" (area 0, all-zero mask) instead of the end of the call.  TemporalDetector cannot produce one
+//     with padding = 8 (every side of its boxes is >= 2 * padding = 16 pixels, and a 16-pixel side rounds to 0 only against
+//     a long side > 32 * size), but boxes are a caller's input here.
+//   * Tile pixel: gray(frame[y1 + og_nearest(ty - top, y2 - y1, nh)][x1 + og_nearest(tx - left, x2 - x1, nw)]) inside the
+//     content rectangle, 0 outside.  NEAREST picks single source pixels, so BGR2GRAY per tap (og_gray_at<3>) gives the byte
+//     that "convert the frame, then crop" (infer.py:226,232) gives.
+//   * Projection: k_unletterbox_paste's rule, identity shortcut included; area = #{box pixels whose projected tile mask > 0}
+//     = np.sum(mask_orig > 0) of infer.py:246.
+// A kernel indexes the frame or the tile only behind og_crop_usable.
+// =======================================================================================
+__host__ __device__ inline void og_crop_geometry(int h, int w, int size, int geom[4]) {
+    const double scale = (double)size / (double)(h > w ? h : w);
+    const int nh = (int)rint((double)h * scale), nw = (int)rint((double)w * scale);
+    geom[0] = (size - nh) / 2;
+    geom[1] = (size - nw) / 2;
+    geom[2] = nh;
+    geom[3] = nw;
+}
+
+// the usable-box rule; fills geom when the box lies inside the frame (content sides may then still be 0: not usable)
+__host__ __device__ inline bool og_crop_usable(int x1, int y1, int x2, int y2, int H, int W, int size, int geom[4]) {
+    geom[0] = geom[1] = geom[2] = geom[3] = 0;
+    if (!(x1 >= 0 && y1 >= 0 && x2 > x1 && y2 > y1 && x2 <= W && y2 <= H)) return false;
+    og_crop_geometry(y2 - y1, x2 - x1, size, geom);
+    return og_crop_ok(x1, y1, x2, y2, geom[0], geom[1], geom[2], geom[3], H, W, size);
+}
+
+// pixel (ty, tx) of the tile of a USABLE box; frame: [H,W,C] u8
+template <int C>
+__host__ __device__ inline uint8_t og_crop_tile_px(const uint8_t* __restrict__ frame, int W, int x1, int y1, int x2, int y2,
+                                                   const int geom[4], int ty, int tx) {
+    const int cy = ty - geom[0], cx = tx - geom[1];
+    if (cy < 0 || cy >= geom[2] || cx < 0 || cx >= geom[3]) return 0;
+    const int sy = og_nearest(cy, y2 - y1, geom[2]), sx = og_nearest(cx, x2 - x1, geom[3]);
+    return (uint8_t)og_gray_at<C>(frame, (long long)(y1 + sy) * W + x1 + sx);
+}
+
+// tile-mask byte that frame pixel (x, y) INSIDE a usable box takes (k_unletterbox_paste's rule)
+__host__ __device__ inline uint8_t og_crop_project_px(const uint8_t* __restrict__ tile_mask, int size, int x1, int y1, int x2, int y2,
+                                                      const int geom[4], int y, int x) {
+    const int hh = y2 - y1, ww = x2 - x1, ch = geom[2], cw = geom[3];
+    const int sy = (ch == hh) ? (y - y1) : og_nearest(y - y1, ch, hh);
+    const int sx = (cw == ww) ? (x - x1) : og_nearest(x - x1, cw, ww);
+    return tile_mask[(long long)(geom[0] + sy) * size + geom[1] + sx];
+}
+
+// grid (ceil(size^2 / 256), nb): one thread per tile pixel; an unusable box gives an all-zero tile
+template <int C>
+__global__ __launch_bounds__(256) void k_crop_tiles(const uint8_t* __restrict__ src, int H, int W, const int32_t* __restrict__ boxes, int size,
+                                                    uint8_t* __restrict__ tiles) {
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= size * size) return;
+    const int x1 = boxes[b * 4], y1 = boxes[b * 4 + 1], x2 = boxes[b * 4 + 2], y2 = boxes[b * 4 + 3];
+    int geom[4];
+    uint8_t v = 0;
+    if (og_crop_usable(x1, y1, x2, y2, H, W, size, geom)) {
+        const int ty = t / size;
+        v = og_crop_tile_px<C>(src + (long long)b * H * W * C, W, x1, y1, x2, y2, geom, ty, t - ty * size);
+    }
+    tiles[(long long)b * size * size + t] = v;
+}
+
+// Project the tile masks back and count.  MASK = false: grid (kCropProjectBlocks, nb), grid-stride over the BOX's hh x ww pixels
+// only; MASK = true: grid (ceil(H*W / 256), nb), one pass over the frame that also writes the full-frame mask [nb,H,W] (the
+// paste value inside the box, 0 outside: the buffer is not pre-zeroed).  The count goes up by one 64-lane reduction and one
+// atomicAdd per wave, as in k_mask_area; area (may be null) must be zero on entry.  An unusable box: nothing counted, zero frame.
+constexpr int kCropProjectBlocks = 8;
+template <bool MASK>
+__global__ __launch_bounds__(256) void k_crop_project(const uint8_t* __restrict__ tile_masks, int size, const int32_t* __restrict__ boxes,
+                                                      int H, int W, uint8_t* __restrict__ mask, int32_t* __restrict__ area) {
+    const int b = blockIdx.y;
+    const int x1 = boxes[b * 4], y1 = boxes[b * 4 + 1], x2 = boxes[b * 4 + 2], y2 = boxes[b * 4 + 3];
+    int geom[4];
+    const bool ok = og_crop_usable(x1, y1, x2, y2, H, W, size, geom);
+    const uint8_t* tm = tile_masks + (long long)b * size * size;
+    int cnt = 0;
+    if (MASK) {
+        const int p = blockIdx.x * 256 + threadIdx.x;
+        if (p < H * W) {
+            const int y = p / W, x = p - y * W;
+            uint8_t v = 0;
+            if (ok && x >= x1 && x < x2 && y >= y1 && y < y2) v = og_crop_project_px(tm, size, x1, y1, x2, y2, geom, y, x);
+            mask[(long long)b * H * W + p] = v;
+            cnt = v > 0 ? 1 : 0;
+        }
+    } else if (ok) {
+        const int ww = x2 - x1, n = (y2 - y1) * ww;
+        for (int p = blockIdx.x * 256 + threadIdx.x; p < n; p += gridDim.x * 256) {
+            const int yy = p / ww;
+            cnt += og_crop_project_px(tm, size, x1, y1, x2, y2, geom, y1 + yy, x1 + p - yy * ww) > 0 ? 1 : 0;
+        }
+    }
+    if (area != nullptr) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
         if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&area[b], cnt);

@@ -225,3 +225,40 @@ def extract_features_unet(avi_path, detector, model, device=None) -> dict | None
     if len(wave) == 0:
         return None   # features.py:227-228
     return _kinematic_features([float(v) for v in wave])
+
+
+def crop_area_waveform(frames, detector, crop_model, device=None, threshold: float = 0.5, crop_size: int = NET_SIZE) -> np.ndarray:
+    """The ``yolo-crop+unet`` frame loop of `scripts/infer.py:222-248` as batched device passes: per frame the detector's box
+    is cropped out of the gray frame, letterboxed to ``crop_size``, segmented by the crop-trained U-Net and projected back;
+    ``area = sum(mask_orig > 0)``, 0 for a frame without a box or with an empty crop.
+
+    The blocks and their boxes come from ``_blocks_with_boxes``, unchanged: with the native detector backend the detector
+    network and the temporal state machine of block k + 1 run on the worker thread under the crop pass of block k.  Each run of
+    equal-shape u8 frames of a block (gray or BGR, any size) goes to ``UNet.segment_crops_stream``, which uploads and segments
+    only the frames that have a usable box; device memory does not grow with the video.
+    """
+    if device is not None and getattr(crop_model, "_device", None) is None:
+        crop_model.to(device)
+    detector.reset()
+    out = []
+    for blk, boxes in _blocks_with_boxes(frames, detector, crop_model):
+        a = np.zeros(len(blk), np.float64)
+        for lo, hi in _shape_runs(blk):
+            run = blk[lo:hi]
+            f0 = run[0]
+            if not (getattr(f0, "dtype", None) == np.uint8 and (f0.ndim == 2 or (f0.ndim == 3 and f0.shape[2] == 3))):
+                run = [bgr_to_gray(f) for f in run]   # any other dtype / layout: the host conversion of infer.py:226
+            _, ar = crop_model.segment_crops_stream(run if isinstance(run, np.ndarray) else list(run), boxes[lo:hi],
+                                                    crop_size=crop_size, threshold=threshold)
+            a[lo:hi] = ar
+        out.append(a)
+    return np.concatenate(out) if out else np.zeros(0, np.float64)
+
+
+def extract_features_unet_crop(avi_path, detector, crop_model, device=None) -> dict | None:
+    """`extract_features_unet` for the YOLO-Crop+UNet pipeline: the area waveform of `scripts/infer.py:222-248` into
+    ``_kinematic_features``; ``None`` for an empty video or one without detections (an all-zero waveform)."""
+    wave = crop_area_waveform(avi_path, detector, crop_model, device)
+    if len(wave) == 0:
+        return None
+    return _kinematic_features([float(v) for v in wave])

@@ -297,6 +297,59 @@ class UNet:
               "og_unet_segment_crops_u8")
         return out
 
+    def segment_crops_stream(self, frames, boxes, crop_size: int = 256, threshold: float = 0.5, want_mask: bool = False):
+        """The YOLO-Crop+UNet loop body of `scripts/infer.py:222-248` over a whole video, streamed on the device in bounded
+        memory (``og_unet_stream_crops_u8``): per frame crop the box → letterbox (NEAREST) to ``crop_size`` → U-Net →
+        project back → ``area = sum(mask_orig > 0)``.  ``frames``: ``[B,H,W]`` gray or ``[B,H,W,3]`` BGR u8 (converted per
+        tap on the device) as an array or a list of frames of one shape; ``boxes``: per frame ``(x1,y1,x2,y2)`` with the
+        Python-slice semantics of ``gray[y1:y2, x1:x2]`` (``utils.normalize_box``), or ``None``.  Only frames with a usable
+        box reach the device; a frame without one -- no detection, an empty crop, a sliver whose short side rounds to 0 at
+        ``crop_size`` -- has area 0 and an all-zero mask.  Returns ``(mask [B,H,W] u8 {0,255} | None, area int32 [B])``."""
+        from .utils import normalize_box
+
+        self._require()
+        keep = None
+        if isinstance(frames, (list, tuple)):
+            keep = [f if (isinstance(f, np.ndarray) and f.dtype == np.uint8 and f.flags.c_contiguous) else np.ascontiguousarray(f, dtype=np.uint8)
+                    for f in frames]
+            if keep and any(f.shape != keep[0].shape for f in keep):
+                raise OpenGlottalHipError("segment_crops_stream(list): frames must share one [H,W] or [H,W,3] shape")
+            shape = (len(keep),) + (keep[0].shape if keep else (0, 0))
+        else:
+            f = np.ascontiguousarray(frames, dtype=np.uint8)
+            shape = f.shape
+        if len(shape) == 4 and shape[-1] == 3:
+            ch = 3
+        elif len(shape) == 3:
+            ch = 1
+        else:
+            raise OpenGlottalHipError(f"expected [B,H,W] or [B,H,W,3] frames, got {shape}")
+        B, H, W = (int(v) for v in shape[:3])
+        if len(boxes) != B:
+            raise OpenGlottalHipError(f"{len(boxes)} boxes for {B} frames")
+        mask = np.empty((B, H, W), np.uint8) if want_mask else None
+        area = np.zeros(B, np.int32)
+        if B == 0:
+            return mask, area
+        bx = np.array([normalize_box(b, W, H) for b in boxes], np.int32).reshape(B, 4)
+        if keep is not None:
+            ptrs = (C.c_void_p * B)(*[k.ctypes.data for k in keep])
+            check(lib().og_unet_stream_frames_crops_u8(self._h, ptrs, B, H, W, ch, ptr(bx), int(crop_size), float(threshold), ptr(mask),
+                                                       ptr(area)), "og_unet_stream_frames_crops_u8")
+        else:
+            check(lib().og_unet_stream_crops_u8(self._h, ptr(f), B, H, W, ch, ptr(bx), int(crop_size), float(threshold), ptr(mask),
+                                                ptr(area)), "og_unet_stream_crops_u8")
+        return mask, area
+
+    def segment_crops_dev(self, src_dev, B: int, H: int, W: int, channels: int, boxes_dev, crop_size: int, tiles_dev, tile_masks_dev,
+                          area_dev=None, mask_dev=None, threshold: float = 0.5) -> None:
+        """Device-pointer, asynchronous variant of ``segment_crops_stream`` for resident frames (torch CUDA tensors or raw
+        ints); ``tiles_dev`` / ``tile_masks_dev``: ``[B,crop_size,crop_size]`` u8 scratch."""
+        self._require()
+        check(lib().og_unet_segment_crops_area_u8_dev(self._h, ptr(src_dev), B, H, W, channels, ptr(boxes_dev), int(crop_size),
+                                                      float(threshold), ptr(tiles_dev), ptr(tile_masks_dev), ptr(mask_dev),
+                                                      ptr(area_dev)), "og_unet_segment_crops_area_u8_dev")
+
     def bgr2gray_dev(self, bgr_dev, B: int, H: int, W: int, gray_dev) -> None:
         """``cv2.cvtColor(BGR2GRAY)`` (features.py:235) on device buffers ``[B,H,W,3]`` u8 → ``[B,H,W]`` u8, asynchronous."""
         self._require()

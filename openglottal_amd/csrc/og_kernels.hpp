@@ -75,8 +75,10 @@ __device__ __forceinline__ og_i32x4 og_make_rsrc(const void* base, unsigned byte
 constexpr unsigned OG_OOB = 0x80000000u;  // a lane offset no buffer of < 2 GiB contains
 // (glds16b, glds16b_m0 and glds16b_m0_masked read rsrc / soff SGPRs from inline asm with 1-3 wait states in front of the load: the
 //  "VALU writes an SGPR, VMEM reads it: 5 wait states" hazard of og_buffer_store16 applies to them too if hipcc ever restores those
-//  SGPRs by v_readlane / v_readfirstlane directly in front of the block.  The shipped ISA has no such sequence; the hazard recognizer
-//  does not look inside inline asm, so nothing but the layer-parity matrix would notice.)
+//  SGPRs by v_readlane / v_readfirstlane directly in front of the block, and the hazard recognizer does not look inside inline asm.
+//  tools/isa_hazards.py holds these sequences: it walks back from every VMEM instruction of every asm block of the shipped ISA over
+//  all predecessors (rule R1; R2 = the M0 wait state, R4 = an operand overwritten behind the transfer), and
+//  tests/test_isa_hazards.py fails on the first such restore closer than 5 states -- before any GPU run.)
 __device__ __forceinline__ void glds16b(unsigned voff, og_i32x4 rsrc, unsigned soff, unsigned lds_wave_base) {
     unsigned keep;
     asm volatile(
@@ -554,12 +556,17 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t og_rsrc(const void* base, unsi
     return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
 }
 // 16-byte store through a raw buffer resource with the wave-uniform part of the address in an SGPR (soffset), followed
-// by ONE WAIT STATE.  The wait state is required on gfx950: a buffer_store_dwordx4 whose data VGPRs are overwritten by
+// by TWO WAIT STATES (`s_nop 1`).  A wait state is required on gfx950: a buffer_store_dwordx4 whose data VGPRs are overwritten by
 // the very next instruction (here: the next sub-tile's v_pk_fma_f32) stores garbage in one 16-lane beat of one dword.
 // It is the GFX9 "VMEM store of more than 64 bits, then a VALU write of the write-data VGPRs: 1 wait state" hazard;
 // hipcc's hazard recognizer waives it for stores that use an SGPR soffset (GCNHazardRecognizer::createsVALUHazard), which
 // is exactly this store -- so the nop has to be ours.  Root cause of round 1's "non-repeatable wrong lanes"
 // (profiles/r02_epilogue_fence_audit.md); tests/test_isa_audit.py scans the shipped ISA for the pattern.
+// The string ended with `s_nop 0` (one state) until the listing audit: on the gfx940 family the recognizer keeps TWO states for
+// this hazard where it does see the store, and with one state 46 stores of 16 kernels had their data registers written by the
+// instruction directly behind the nop (42 v_pk_fma_f32, 3 v_ldexp_f32, 1 v_cndmask_b32).  No wrong result was
+// ever traced to them, and a passing suite is no evidence either way; a hazard pad is not a tuning option.
+// tests/test_isa_hazards.py (rule R3) asserts that no 12/16-byte store of the shipped ISA, ours or hipcc's, has fewer than two.
 // The FIVE WAIT STATES in front of it are the second GFX9 hazard an inline-asm store is alone with: "VALU writes an SGPR, VMEM
 // reads that SGPR: 5 wait states".  hipcc's hazard recognizer does not look inside inline asm, so where it restores the resource
 // descriptor from spilled SGPRs (v_readlane_b32 s40..s43 directly in front of the asm block: k_conv_mfma_p<1, 0, 16, 9>, whose
@@ -571,7 +578,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t og_rsrc(const void* base, unsi
 #endif
 __device__ __forceinline__ void og_buffer_store16(f32x4 v, __amdgpu_buffer_rsrc_t rs, unsigned voff, unsigned soff) {
 #if OG_STORE_NOP
-    asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 0" : : "v"(v), "v"(voff), "s"(rs), "s"(soff) : "memory");
+    asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop 1" : : "v"(v), "v"(voff), "s"(rs), "s"(soff) : "memory");
 #else
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(og_u32x4, v), rs, voff, soff, 0);
 #endif
@@ -1654,10 +1661,10 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino(ConvArgs a) {
 
 // 16-byte device-scope (sc1: written through / read past this XCD's L2) store and load for the exchange of raw accumulators
 // between workgroups that may sit on different XCDs -- the 128-bit form of what __hip_atomic_store / __hip_atomic_load at agent
-// scope compile to (global_store_dword ... sc1).  The store is followed by one wait state for the same reason as
+// scope compile to (global_store_dword ... sc1).  The store is followed by two wait states for the same reason as
 // og_buffer_store16 (hipcc cannot see the data registers of an inline-asm store being reused).
 __device__ __forceinline__ void og_store16_dev(float* p, f32x4 v) {
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 0" : : "v"(p), "v"(v) : "memory");
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
 }
 // The matching load goes through the compiler's own buffer-load builtin with the sc1 cache-policy bit (aux 16 on gfx94x/95x):
 // hipcc then tracks the outstanding load itself (an inline-asm load returns "immediately" as far as the register allocator

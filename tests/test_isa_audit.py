@@ -17,16 +17,15 @@ import sys
 
 import pytest
 
+import isa_listing
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_conv_main_loops_have_no_vector_alu_and_no_scratch(tmp_path):
-    asm = tmp_path / "og_api.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                    os.path.join(ROOT, "openglottal_amd", "csrc", "og_api.hip"), "-o", str(asm)],
-                   check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+def test_conv_main_loops_have_no_vector_alu_and_no_scratch():
+    asm = isa_listing.listing()     # compiled once for all tests/test_isa_*.py modules
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_audit.py"), str(asm)],
                          check=True, capture_output=True, text=True).stdout
     hz = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_store_hazard.py"), str(asm)], capture_output=True, text=True)

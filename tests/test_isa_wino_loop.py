@@ -28,6 +28,8 @@ import sys
 
 import pytest
 
+import isa_listing
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
@@ -37,11 +39,8 @@ GAP_MAX = 12
 
 
 @pytest.fixture(scope="module")
-def rows(tmp_path_factory):
-    asm = tmp_path_factory.mktemp("isa_wino") / "og_api.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                    os.path.join(ROOT, "openglottal_amd", "csrc", "og_api.hip"), "-o", str(asm)],
-                   check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+def rows():
+    asm = isa_listing.listing()     # compiled once for all tests/test_isa_*.py modules
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_wino_loop.py"), str(asm), "--json"],
                          check=True, capture_output=True, text=True).stdout
     txt = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_wino_loop.py"), str(asm)],

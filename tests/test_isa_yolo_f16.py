@@ -9,17 +9,17 @@ import sys
 
 import pytest
 
+import isa_listing
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
-def test_detector_f16_conv_kernels_have_no_scratch_and_use_the_f16_mfma(tmp_path):
-    asm = tmp_path / "og_api.s"
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                    os.path.join(ROOT, "openglottal_amd", "csrc", "og_api.hip"), "-o", str(asm)],
-                   check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    s = asm.read_text()
+def test_detector_f16_conv_kernels_have_no_scratch_and_use_the_f16_mfma():
+    asm = isa_listing.listing()     # compiled once for all tests/test_isa_*.py modules
+    with open(asm) as f:
+        s = f.read()
     names = sorted(set(re.findall(r"^(_Z14k_conv_mfma_fyI\w+):", s, re.M)))
     assert len(names) == 8, names   # <1|2, MODE 0> <1|2, MODE 2> <1|2, MODE 2, F32OUT> <1|2, MODE 3>
     for n in names + ["_Z17k_conv_direct_u8hPKhiiPKfS2_S2_iPfxiiiiiiiiiiPi", "_Z12k_maxpool5_hPKfPfxiiiiiix"]:

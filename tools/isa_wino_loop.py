@@ -4,7 +4,10 @@ For each instantiation it finds the loop whose body holds 64 * NT MFMAs (the ste
 straight-line copy behind it (the peeled last chunk), and prints one table row + the histogram of the MFMA gaps.
 usage: hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only openglottal_amd/csrc/og_api.hip -o /tmp/api.s
        python tools/isa_wino_loop.py /tmp/api.s [--json]"""
-import collections, json, re, sys
+import collections, json, os, re, sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from isa_hazards import dma_operand_overwrites, operands   # noqa: E402  (the rule lives there, judged over every kernel)
 
 BRANCH = ("s_cbranch", "s_branch")
 M0_IMPLICIT = ("s_movrel", "v_movrel", "ds_gws", "v_interp", "s_sendmsg", "ds_add_gs", "ds_sub_gs", "ds_append", "ds_consume")
@@ -39,11 +42,6 @@ def kind(op):
     return "other"
 
 
-def operands(op):
-    p = op.split(None, 1)
-    return [x.strip() for x in p[1].split(",")] if len(p) > 1 else []
-
-
 def reads_m0(op):
     m = op.split()[0]
     if m.startswith(M0_IMPLICIT) or " gds" in op:
@@ -57,32 +55,6 @@ def writes_m0(op):
     m = op.split()[0]
     ops = operands(op)
     return bool(ops) and ops[0] == "m0" and m.startswith("s_") and not m.startswith(("s_cmp", "s_bitcmp", "s_cbranch", "s_setreg"))
-
-
-def regs(text):
-    out = set()
-    for m in re.finditer(r"\b([vs])(\d+)\b|\b([vs])\[(\d+):(\d+)\]", text):
-        if m.group(1):
-            out.add((m.group(1), int(m.group(2))))
-        else:
-            out |= {(m.group(3), i) for i in range(int(m.group(4)), int(m.group(5)) + 1)}
-    return out
-
-
-def dma_operand_overwrites(ins):
-    """LDS-DMA instructions directly followed by an instruction that writes one of their operand registers (hipcc does not see
-    inside the asm statement and keeps no distance of its own; glds16b's M0 restore used to stand there)"""
-    n = 0
-    for a, b in zip(ins, ins[1:]):
-        if kind(a) != "dma":
-            continue
-        m = b.split()[0]
-        if m.startswith(("s_cmp", "s_bitcmp", "s_cbranch", "s_branch", "s_waitcnt", "s_nop", "s_barrier", "buffer_store", "global_store", "ds_write", "ds_store")):
-            continue
-        ops = operands(b)
-        if ops and regs(ops[0]) & regs(a.split(None, 1)[1]):
-            n += 1
-    return n
 
 
 def function(src, label):

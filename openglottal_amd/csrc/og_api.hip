@@ -116,12 +116,6 @@ inline void plan_write(const char* name, const void* p, long long bytes) {
     std::string& w = g_plan->recs.back().writes;
     w += (w.empty() ? "" : ";") + std::string(name) + "=" + std::to_string(end);
 }
-// og_unet_plan only: give the f16-mode conv launch just recorded its instantiation (the launch site's text has template
-// parameters in it) and the K walk it was given: 64-channel chunks, and whether the last one is a half (ConvArgs::k_half)
-inline void plan_label_f(const char* inst, int n_chunks, int k_half) {
-    if (!g_plan || g_plan->recs.empty()) return;
-    g_plan->recs.back().kernel = std::string(inst) + " chunks=" + std::to_string(n_chunks) + " k_half=" + std::to_string(k_half);
-}
 // og_unet_plan only: name the launch just recorded by the instantiation that would run, every template argument resolved (the
 // launch site's text has template parameters in it), with what is decided at run time behind it (" ksplit=3", " nt=2")
 inline void plan_inst(const char* fmt, ...) {
@@ -148,6 +142,33 @@ inline void plan_inst(const char* fmt, ...) {
             if (g_trace) g_trace->push_back({#kern, g_launch_mod ? g_launch_mod : ""});                   \
         }                                                                                                 \
     } while (0)
+
+// Dynamic LDS above the default limit has to be permitted per kernel before the first launch.  A launch site that goes through
+// OG_LAUNCH_LDS instantiates one KernelLds per (kernel, LDS size): the node links itself into g_kernel_lds while the library is
+// loaded, and init_kernel_attrs() walks the list at handle initialisation (never inside a stream capture).  So the size a kernel is
+// launched with and the size it is permitted are the same constant, and a launcher that exists has its permission.
+struct KernelLds {
+    const void* kern;
+    int lds;
+    KernelLds* next;
+    KernelLds(const void* k, int l);
+};
+KernelLds* g_kernel_lds = nullptr;
+inline KernelLds::KernelLds(const void* k, int l) : kern(k), lds(l), next(g_kernel_lds) { g_kernel_lds = this; }
+template <auto KERN, int LDS>
+struct KernelLdsOf {
+    static inline KernelLds node{(const void*)KERN, LDS};
+};
+#define OG_LAUNCH_LDS(kern, grid, block, lds, stream, ...)                                                \
+    do {                                                                                                  \
+        (void)&KernelLdsOf<(kern), (lds)>::node;                                                          \
+        OG_LAUNCH(kern, grid, block, lds, stream, __VA_ARGS__);                                           \
+    } while (0)
+int init_kernel_attrs() {  // must not run inside a stream capture
+    for (const KernelLds* k = g_kernel_lds; k; k = k->next)
+        HIPCHK(hipFuncSetAttribute(k->kern, hipFuncAttributeMaxDynamicSharedMemorySize, k->lds));
+    return OG_OK;
+}
 
 struct HostTensor {
     std::vector<int64_t> shape;
@@ -659,24 +680,134 @@ int ensure_arena(og_unet* h, int B, int H, int W) {
     return OG_OK;
 }
 
-void prof_begin(og_unet* h, const std::string& layer, const std::string& kernel, double flops) {
-    if (!h->prof) return;
-    og_unet::ProfEntry e{layer, kernel, flops, nullptr, nullptr};
-    (void)hipEventCreate(&e.e0);
-    (void)hipEventCreate(&e.e1);
-    (void)hipEventRecord(e.e0, h->stream);
-    h->prof->push_back(e);
+struct LaunchCtx {
+    hipStream_t stream;
+    int n_cu;
+    int wg_per_cu;
+    int xcd_group = 1;   // occupancy kernel: frame-interleaved grid.z so that a tile's column tiles share an XCD
+    // og_unet_profile: the handle whose profile gets an entry per launch (nullptr: the detector's chain), the layer and its algorithmic FLOPs
+    og_unet* prof = nullptr;
+    const std::string* layer = nullptr;
+    double flops = 0;
+};
+
+// One entry of og_unet_profile (kernel label + algorithmic FLOPs between two events): the constructor begins it, the destructor
+// records its end -- OG_LAUNCH returns from the enclosing function when a launch fails, and no return can leave an entry open.
+// The launchers format the label from their own template arguments, the ones that pick the kernel (nothing is formatted unless a
+// profile is being taken).
+struct ProfScope {
+    og_unet* h;
+    ProfScope(og_unet* h_, const char* layer, const char* kernel, double flops) : h(h_) { begin(layer, kernel, flops); }
+    __attribute__((format(printf, 3, 4))) ProfScope(const LaunchCtx& c, const char* fmt, ...) : h(c.prof) {
+        if (!h || !h->prof) return;
+        char kernel[48];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(kernel, sizeof kernel, fmt, ap);
+        va_end(ap);
+        begin(c.layer->c_str(), kernel, c.flops);
+    }
+    ProfScope(const ProfScope&) = delete;
+    ProfScope& operator=(const ProfScope&) = delete;
+    ~ProfScope() {
+        if (h && h->prof) (void)hipEventRecord(h->prof->back().e1, h->stream);
+    }
+
+private:
+    void begin(const char* layer, const char* kernel, double flops) {
+        if (!h || !h->prof) return;
+        og_unet::ProfEntry e{layer, kernel, flops, nullptr, nullptr};
+        (void)hipEventCreate(&e.e0);
+        (void)hipEventCreate(&e.e1);
+        (void)hipEventRecord(e.e0, h->stream);
+        h->prof->push_back(e);
+    }
+};
+
+// Runtime value -> template argument: f(og_const<V>{}) for the V of the list that equals v, the LAST one when none does (the
+// launch sites list an option's special values first and its default last).  Every V listed is an instantiation that exists in the
+// library, so a site lists exactly the values its kernel is shipped for.
+template <int V0, int... Vs, typename F>
+int og_pick(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) return f(og_const<V0>{});
+    else return (v == V0) ? f(og_const<V0>{}) : og_pick<Vs...>(v, f);
 }
-void prof_end(og_unet* h) {
-    if (h->prof) (void)hipEventRecord(h->prof->back().e1, h->stream);
+
+// One operand of a conv launch as the kernels address it: base, frame stride, pixel stride and first channel, in 4-byte units
+struct ConvView {
+    float* p = nullptr;
+    long long frame_stride = 0;
+    int pix_stride = 0, ch_off = 0;
+};
+
+// What a conv launch of either net starts from: its operands, weights and affine, the zero page, and the neutral values of the
+// rest (threshold 0.5, no split).  Every other field is zero / null until a path sets it, so nothing reaches a kernel uninitialised.
+ConvArgs conv_args(const ConvView& in, const ConvView& out, const ConvView& pool, const ConvView& res, const float* wpk, const float* scale,
+                   const float* shift, int aff_mod, const float* zero_page, int act) {
+    ConvArgs a{};
+    a.in = in.p;
+    a.in_frame_stride = in.frame_stride;
+    a.in_pix_stride = in.pix_stride;
+    a.in_ch_off = in.ch_off;
+    a.out = out.p;
+    a.out_frame_stride = out.frame_stride;
+    a.out_pix_stride = out.pix_stride;
+    a.out_ch_off = out.ch_off;
+    a.pool = pool.p;
+    a.pool_frame_stride = pool.frame_stride;
+    a.pool_pix_stride = pool.pix_stride;
+    a.pool_ch_off = pool.ch_off;
+    a.res = res.p;
+    a.res_frame_stride = res.frame_stride;
+    a.res_pix_stride = res.pix_stride;
+    a.res_ch_off = res.ch_off;
+    a.wpk = wpk;
+    a.scale = scale;
+    a.shift = shift;
+    a.aff_mod = aff_mod;
+    a.zero_page = zero_page;
+    a.act = act;
+    a.head_thr = 0.5f;
+    a.ksplit = 1;
+    a.vsplit = 1;
+    return a;
+}
+
+// grid.z of every kernel that decodes blockIdx.z with ConvArgs::zdiv / zrcp / zgroup_shift: (frame group, column tile x K part, frame
+// in group).  `zdiv` = column tiles (x K parts) per spatial tile, `grid_tiles` = the GRID's tiles per frame (k_conv_wino_w<2> has half
+// as many rows as a.tiles_y counts).  With "xcd_group" the frames are interleaved in groups of G = 8 / gcd(8, grid_tiles) so that
+// the column tiles of one spatial tile land on one XCD (8 XCDs, blocks dealt round-robin).  `wgs` > 0: the ungrouped forms, `wgs`
+// workgroups per (frame, column tile) -- k_conv_wino_ps's 16 / PN, k_conv_wino_wp's 4, k_convt_w's 1.
+// Sets a.frames, a.zdiv, a.zgroup_shift, a.zrcp; returns grid.z, or OG_EINVAL when it would pass the hardware's 65535.
+int grid_z(const LaunchCtx& c, ConvArgs& a, int zdiv, int grid_tiles, int wgs = 0) {
+    const int frames = a.n_spatial / (a.tiles_x * a.tiles_y);
+    a.zdiv = zdiv;
+    a.frames = frames;
+    a.zgroup_shift = 0;
+    if (wgs == 0 && c.xcd_group && zdiv > 1) {
+        int txy = grid_tiles, g = 8;
+        while (g > 1 && txy % 2 == 0) { txy /= 2; g /= 2; }   // g = 8 / gcd(8, tiles per frame)
+        while (g > frames) g /= 2;
+        while ((1 << a.zgroup_shift) < g) ++a.zgroup_shift;
+    }
+    const int G = 1 << a.zgroup_shift, groups = (frames + G - 1) / G;
+    a.zrcp = 1.0f / (float)(zdiv * G);
+    const long long gz = (long long)groups * G * zdiv * (wgs ? wgs : 1);
+    if (gz > 65535) return fail(OG_EINVAL, "micro-batch too large for one launch (grid.z): lower the chunk size");
+    return (int)gz;
+}
+
+// LDS of k_conv_mfma: two halo buffers + two weight stages
+template <int NT, int MODE, int TH>
+constexpr int conv_t_lds() {
+    return 2 * (16 + 2 * ((MODE == 0) ? 1 : 0)) * (TH + 2 * ((MODE == 0) ? 1 : 0)) * 128 + 2 * 32 * NT * 128;
 }
 
 template <int NT, int MODE, int TH>
-int launch_conv_t(og_unet* h, const ConvArgs& a, int n_ntiles) {
-    constexpr int PAD = (MODE == 0) ? 1 : 0;
-    constexpr int lds = 2 * (16 + 2 * PAD) * (TH + 2 * PAD) * 128 + 2 * 32 * NT * 128;
-    const unsigned grid = (unsigned)(a.n_spatial * n_ntiles);
-    OG_LAUNCH((k_conv_mfma<NT, MODE, TH>), dim3(grid), dim3(256), lds, h->stream, a);
+int launch_conv_t(const LaunchCtx& c, const ConvArgs& a, int n_ntiles) {
+    constexpr int lds = conv_t_lds<NT, MODE, TH>();
+    ProfScope ps(c, "k_conv_mfma<%d,%d,%d>", NT, MODE, TH);
+    OG_LAUNCH_LDS((k_conv_mfma<NT, MODE, TH>), dim3((unsigned)(a.n_spatial * n_ntiles)), dim3(256), lds, c.stream, a);
     plan_inst("k_conv_mfma<%d, %d, %d>", NT, MODE, TH);
     return OG_OK;
 }
@@ -685,14 +816,6 @@ template <int NT, int MODE, int TH, int TPS>
 constexpr int conv_p_lds() {
     return 2 * (16 + 2 * ((MODE == 0) ? 1 : 0)) * (TH + 2 * ((MODE == 0) ? 1 : 0)) * 128 + 2 * TPS * 32 * NT * 128;
 }
-
-struct LaunchCtx {
-    hipStream_t stream;
-    int n_cu;
-    int wg_per_cu;
-    int xcd_group = 1;   // occupancy kernel: frame-interleaved grid.z so that a tile's column tiles share an XCD
-};
-
 
 // Split-K factor for a launch of `n_items` tiles over `n_chunks` 32-channel chunks: only when the
 // launch would leave >= 3/4 of the workgroup slots empty (small-batch / latency mode), so that
@@ -712,10 +835,12 @@ constexpr int conv_o_lds() {
     return ((MODE == 3) ? 18 * (TH + 1) : (16 + 2 * ((MODE == 0) ? 1 : 0)) * (TH + 2 * ((MODE == 0) ? 1 : 0))) * 128 +
            ((MODE == 0) ? 3 : 2) * 32 * NT * 128;
 }
+// ... and what the FIRST variants (the first layer computed inside downs.0's second conv) add to it: the 12 x 20 pixels of the u8
+// frame under a tile's halo, and the first layer's 9 x 32 weights, scale and shift
+constexpr int kFirstLds = (12 * 20 + 352) * 4;
 
 template <int NT, int MODE, int TH, int OCC, bool VS = false>
 int launch_conv_o(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {
-    constexpr int PAD = (MODE == 0) ? 1 : 0;
     constexpr int lds = conv_o_lds<NT, MODE, TH>();
     static_assert(lds >= 4 * 5120, "the epilogue's per-wave scratch needs 20 KB");
     ConvArgs a = a_in;
@@ -724,24 +849,14 @@ int launch_conv_o(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {
     else a.vsplit = 1;
     if (a.n_spatial * n_ntiles > kTileCounters) a.tile_counter = nullptr;
     if ((MODE == 2 || MODE == 3) && a.tile_counter == nullptr) a.ksplit = 1;   // these modes split K with the fused reduce only
-    const int frames = a.n_spatial / (a.tiles_x * a.tiles_y);
-    a.zdiv = n_ntiles * a.ksplit;
-    a.frames = frames;
-    a.zgroup_shift = 0;
-    if (c.xcd_group && a.zdiv > 1) {   // column tiles of one spatial tile onto one XCD (8 XCDs, blocks dealt round-robin)
-        int txy = a.tiles_x * a.tiles_y, g = 8;
-        while (g > 1 && txy % 2 == 0) { txy /= 2; g /= 2; }   // g = 8 / gcd(8, tiles per frame)
-        while (g > frames) g /= 2;
-        while ((1 << a.zgroup_shift) < g) ++a.zgroup_shift;
-    }
-    const int G = 1 << a.zgroup_shift, groups = (frames + G - 1) / G;
-    a.zrcp = 1.0f / (float)(a.zdiv * G);
-    if ((long long)groups * G * a.zdiv > 65535) return fail(OG_EINVAL, "micro-batch too large for one launch (grid.z): lower the chunk size");
+    ProfScope ps(c, "k_conv_mfma_o<%d,%d,%d>%s", NT, MODE, TH, a.ksplit > 1 ? "+splitK" : "");
+    const int gz = grid_z(c, a, n_ntiles * a.ksplit, a.tiles_x * a.tiles_y);
+    if (gz < 0) return gz;
     if (a.ksplit == 1) a.tile_counter = nullptr;
     if (a.ksplit > 1)   // raw accumulators of every K part (4 waves x MS sub-tiles x 16 registers x 64 lanes), arrivals per tile
         plan_need((long long)a.n_spatial * n_ntiles * a.ksplit * 4 * (((TH / 2) / (4 / NT)) * 16 * 64) * 4,
                   a.tile_counter ? (long long)a.n_spatial * n_ntiles : 0);
-    OG_LAUNCH((k_conv_mfma_o<NT, MODE, TH, OCC, false, VS>), dim3(a.tiles_x, a.tiles_y, groups * G * a.zdiv), dim3(256), lds, c.stream, a);
+    OG_LAUNCH_LDS((k_conv_mfma_o<NT, MODE, TH, OCC, false, VS>), dim3(a.tiles_x, a.tiles_y, gz), dim3(256), lds, c.stream, a);
     plan_inst(VS ? "k_conv_mfma_o<%d, %d, %d, %d, false, true> vsplit=%d" : "k_conv_mfma_o<%d, %d, %d, %d, false, false> ksplit=%d", NT, MODE,
               TH, OCC, VS ? a.vsplit : a.ksplit);
     if constexpr (MODE == 0 || MODE == 1) {
@@ -761,20 +876,10 @@ int launch_conv_wino(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {  
     ConvArgs a = a_in;   // (a.stamps: diagnostic timeline, 8 x u64 for the first 511 workgroups)
     a.ksplit = 1;
     a.tile_counter = nullptr;
-    const int frames = a.n_spatial / (a.tiles_x * a.tiles_y);
-    a.zdiv = n_ntiles;
-    a.frames = frames;
-    a.zgroup_shift = 0;
-    if (c.xcd_group && a.zdiv > 1) {
-        int txy = a.tiles_x * a.tiles_y, g = 8;
-        while (g > 1 && txy % 2 == 0) { txy /= 2; g /= 2; }
-        while (g > frames) g /= 2;
-        while ((1 << a.zgroup_shift) < g) ++a.zgroup_shift;
-    }
-    const int G = 1 << a.zgroup_shift, groups = (frames + G - 1) / G;
-    a.zrcp = 1.0f / (float)(a.zdiv * G);
-    if ((long long)groups * G * a.zdiv > 65535) return fail(OG_EINVAL, "micro-batch too large for one launch (grid.z): lower the chunk size");
-    OG_LAUNCH(k_conv_wino<NT>, dim3(a.tiles_x, a.tiles_y, groups * G * a.zdiv), dim3(256), wino_lds<NT>(), c.stream, a);
+    ProfScope ps(c, "k_conv_wino<%d>", NT);
+    const int gz = grid_z(c, a, n_ntiles, a.tiles_x * a.tiles_y);
+    if (gz < 0) return gz;
+    OG_LAUNCH_LDS(k_conv_wino<NT>, dim3(a.tiles_x, a.tiles_y, gz), dim3(256), wino_lds<NT>(), c.stream, a);
     plan_inst("k_conv_wino<%d>", NT);
     return OG_OK;
 }
@@ -789,17 +894,14 @@ constexpr int wino_ps_lds() {
 // (raw accumulators: 256 KB per (tile, column tile)) and the arrival counters
 template <int NT, int PN>
 int launch_conv_wino_ps(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {
+    constexpr int lds = wino_ps_lds<NT, PN>();
     ConvArgs a = a_in;   // (a.stamps: per-workgroup timeline of diagnostic runs, 4 x u64 for up to 1024 workgroups)
     a.ksplit = 1;
-    const int frames = a.n_spatial / (a.tiles_x * a.tiles_y);
-    a.zdiv = n_ntiles;
-    a.frames = frames;
-    a.zgroup_shift = 0;
-    a.zrcp = 1.0f / (float)a.zdiv;
-    if ((long long)frames * a.zdiv * (16 / PN) > 65535) return fail(OG_EINVAL, "k_conv_wino_ps: grid.z");
-    constexpr int lds = wino_ps_lds<NT, PN>();
+    ProfScope ps(c, "k_conv_wino_ps<%d,%d>", NT, PN);
+    const int gz = grid_z(c, a, n_ntiles, a.tiles_x * a.tiles_y, 16 / PN);
+    if (gz < 0) return gz;
     plan_need((long long)a.n_spatial * n_ntiles * (16 * 4 * 1024 * 4), (long long)a.n_spatial * n_ntiles);
-    OG_LAUNCH((k_conv_wino_ps<NT, PN>), dim3(a.tiles_x, a.tiles_y, frames * a.zdiv * (16 / PN)), dim3(256), lds, c.stream, a);
+    OG_LAUNCH_LDS((k_conv_wino_ps<NT, PN>), dim3(a.tiles_x, a.tiles_y, gz), dim3(256), lds, c.stream, a);
     plan_inst("k_conv_wino_ps<%d, %d>", NT, PN);
     return OG_OK;
 }
@@ -811,68 +913,58 @@ constexpr int wino_w_lds() {
 }
 
 // k_conv_wino_w: 8 WB x 16-pixel tiles x 32 output channels, the 16 positions over the four waves; a.tiles_y counts 8-row tiles
-// (the fused head's count slots), the grid has tiles_y / WB rows
+// (the fused head's count slots), the grid has tiles_y / WB rows.  nt: the layer's canonical form (which weight pack a.wpk is)
 template <int WB>
-int launch_conv_wino_w(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {
+int launch_conv_wino_w(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles, int nt) {
     ConvArgs a = a_in;   // (a.stamps: per-workgroup timeline of diagnostic runs, 4 x u64 for up to 1024 workgroups)
     a.ksplit = 1;
     a.tile_counter = nullptr;
     const int gy = a.tiles_y / WB;
-    const int frames = a.n_spatial / (a.tiles_x * a.tiles_y);
-    a.zdiv = n_ntiles;
-    a.frames = frames;
-    a.zgroup_shift = 0;
-    if (c.xcd_group && a.zdiv > 1) {
-        int txy = a.tiles_x * gy, g = 8;
-        while (g > 1 && txy % 2 == 0) { txy /= 2; g /= 2; }
-        while (g > frames) g /= 2;
-        while ((1 << a.zgroup_shift) < g) ++a.zgroup_shift;
-    }
-    const int G = 1 << a.zgroup_shift, groups = (frames + G - 1) / G;
-    a.zrcp = 1.0f / (float)(a.zdiv * G);
-    if ((long long)groups * G * a.zdiv > 65535) return fail(OG_EINVAL, "micro-batch too large for one launch (grid.z): lower the chunk size");
-    OG_LAUNCH(k_conv_wino_w<WB>, dim3(a.tiles_x, gy, groups * G * a.zdiv), dim3(256), wino_w_lds<WB>(), c.stream, a);
+    ProfScope ps(c, "k_conv_wino_w<%d,%d>", nt, WB);
+    const int gz = grid_z(c, a, n_ntiles, a.tiles_x * gy);
+    if (gz < 0) return gz;
+    OG_LAUNCH_LDS(k_conv_wino_w<WB>, dim3(a.tiles_x, gy, gz), dim3(256), wino_w_lds<WB>(), c.stream, a);
+    plan_inst("k_conv_wino_w<%d> nt=%d", WB, nt);
     return OG_OK;
 }
 
 constexpr int kWinoWpLds = 3 * 6 * 4096 + 9 * 4096;
 
 // k_conv_wino_wp: k_conv_wino_w<1>'s tiles, a tile's four position rows on four workgroups (grid.z x 4); needs the split-K workspace
-// (64 KB per tile) and the arrival counters
-int launch_conv_wino_wp(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {
+// (64 KB per tile) and the arrival counters.  nt: as for k_conv_wino_w
+int launch_conv_wino_wp(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles, int nt) {
     ConvArgs a = a_in;   // (a.stamps: per-workgroup timeline of diagnostic runs, 4 x u64 for up to 1024 workgroups)
     a.ksplit = 1;
-    const int frames = a.n_spatial / (a.tiles_x * a.tiles_y);
-    a.zdiv = n_ntiles;
-    a.frames = frames;
-    a.zgroup_shift = 0;
-    a.zrcp = 1.0f / (float)a.zdiv;
-    if ((long long)frames * a.zdiv * 4 > 65535) return fail(OG_EINVAL, "k_conv_wino_wp: grid.z");
+    ProfScope ps(c, "k_conv_wino_wp<%d>", nt);
+    const int gz = grid_z(c, a, n_ntiles, a.tiles_x * a.tiles_y, 4);
+    if (gz < 0) return gz;
     plan_need((long long)a.n_spatial * n_ntiles * 65536, (long long)a.n_spatial * n_ntiles);
-    OG_LAUNCH(k_conv_wino_wp, dim3(a.tiles_x, a.tiles_y, frames * a.zdiv * 4), dim3(256), kWinoWpLds, c.stream, a);
+    OG_LAUNCH_LDS(k_conv_wino_wp, dim3(a.tiles_x, a.tiles_y, gz), dim3(256), kWinoWpLds, c.stream, a);
+    plan_inst("k_conv_wino_wp nt=%d", nt);
+    return OG_OK;
+}
+
+// k_convt_w: the transposed conv on 32-pixel x 32-column wave tiles (operands straight to registers, no LDS); grid.z = frame x
+// column tile of 32 / 4 per workgroup
+int launch_convt_w(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {
+    ConvArgs a = a_in;
+    ProfScope ps(c, "k_convt_w<1,1,8>");
+    const int gz = grid_z(c, a, n_ntiles, a.tiles_x * a.tiles_y, 1);
+    if (gz < 0) return gz;
+    OG_LAUNCH(k_convt_w, dim3(a.tiles_x, (a.H + 1) / 2, gz), dim3(256), 0, c.stream, a);
     return OG_OK;
 }
 
 template <int NT, int MODE, int TH, int OCC, bool SQ = false>
-int launch_conv_h(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {   // split-precision twin of launch_conv_o (no split-K)
+int launch_conv_h(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {   // split-precision twin of launch_conv_o
     constexpr int lds = conv_o_lds<NT, MODE, TH>();
     ConvArgs a = a_in;
     a.stamps = nullptr;
     if (SQ || a.tile_counter == nullptr || a.partial == nullptr || a.n_spatial * n_ntiles > kTileCounters) a.ksplit = 1;   // fused reduce only
-    const int frames = a.n_spatial / (a.tiles_x * a.tiles_y);
-    a.zdiv = n_ntiles * a.ksplit;
-    a.frames = frames;
-    a.zgroup_shift = 0;
-    if (c.xcd_group && a.zdiv > 1) {
-        int txy = a.tiles_x * a.tiles_y, g = 8;
-        while (g > 1 && txy % 2 == 0) { txy /= 2; g /= 2; }
-        while (g > frames) g /= 2;
-        while ((1 << a.zgroup_shift) < g) ++a.zgroup_shift;
-    }
-    const int G = 1 << a.zgroup_shift, groups = (frames + G - 1) / G;
-    a.zrcp = 1.0f / (float)(a.zdiv * G);
-    if ((long long)groups * G * a.zdiv > 65535) return fail(OG_EINVAL, "micro-batch too large for one launch (grid.z): lower the chunk size");
-    OG_LAUNCH((k_conv_mfma_h<NT, MODE, TH, OCC, false, SQ>), dim3(a.tiles_x, a.tiles_y, groups * G * a.zdiv), dim3(256), lds, c.stream, a);
+    ProfScope ps(c, "k_conv_mfma_h<%d,%d,%d>", NT, MODE, TH);
+    const int gz = grid_z(c, a, n_ntiles * a.ksplit, a.tiles_x * a.tiles_y);
+    if (gz < 0) return gz;
+    OG_LAUNCH_LDS((k_conv_mfma_h<NT, MODE, TH, OCC, false, SQ>), dim3(a.tiles_x, a.tiles_y, gz), dim3(256), lds, c.stream, a);
     plan_inst("k_conv_mfma_h<%d, %d, %d, %d, false, %s> ksplit=%d", NT, MODE, TH, OCC, SQ ? "true" : "false", a.ksplit);
     return OG_OK;
 }
@@ -884,26 +976,19 @@ int launch_conv_f(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {   //
     a.stamps = nullptr;
     a.ksplit = 1;
     a.tile_counter = nullptr;
-    const int frames = a.n_spatial / (a.tiles_x * a.tiles_y);
-    a.zdiv = n_ntiles;
-    a.frames = frames;
-    a.zgroup_shift = 0;
-    if (c.xcd_group && a.zdiv > 1) {
-        int txy = a.tiles_x * a.tiles_y, g = 8;
-        while (g > 1 && txy % 2 == 0) { txy /= 2; g /= 2; }
-        while (g > frames) g /= 2;
-        while ((1 << a.zgroup_shift) < g) ++a.zgroup_shift;
-    }
-    const int G = 1 << a.zgroup_shift, groups = (frames + G - 1) / G;
-    a.zrcp = 1.0f / (float)(a.zdiv * G);
-    if ((long long)groups * G * a.zdiv > 65535) return fail(OG_EINVAL, "micro-batch too large for one launch (grid.z): lower the chunk size");
-    OG_LAUNCH((k_conv_mfma_f<NT, MODE, TH, OCC, false, SQ>), dim3(a.tiles_x, a.tiles_y, groups * G * a.zdiv), dim3(256), lds, c.stream, a);
-    if (g_plan) {
-        char inst[64];
-        snprintf(inst, sizeof inst, "(k_conv_mfma_f<%d, %d, %d, %d, false, %s>)", NT, MODE, TH, OCC, SQ ? "true" : "false");
-        plan_label_f(inst, a.n_chunks, a.k_half);
-    }
+    ProfScope ps(c, "k_conv_mfma_f<%d,%d,%d>", NT, MODE, TH);
+    const int gz = grid_z(c, a, n_ntiles, a.tiles_x * a.tiles_y);
+    if (gz < 0) return gz;
+    OG_LAUNCH_LDS((k_conv_mfma_f<NT, MODE, TH, OCC, false, SQ>), dim3(a.tiles_x, a.tiles_y, gz), dim3(256), lds, c.stream, a);
+    // (with the K walk it was given: 64-channel chunks, and whether the last one is a half)
+    plan_inst("(k_conv_mfma_f<%d, %d, %d, %d, false, %s>) chunks=%d k_half=%d", NT, MODE, TH, OCC, SQ ? "true" : "false", a.n_chunks, a.k_half);
     return OG_OK;
+}
+
+// the two reduced-precision families take the same instantiations: the handle's "precision" names the family
+template <int NT, int MODE, int TH, int OCC, bool SQ = false>
+int launch_conv_hf(const LaunchCtx& c, const ConvArgs& a, int n_ntiles, bool f16) {
+    return f16 ? launch_conv_f<NT, MODE, TH, OCC, SQ>(c, a, n_ntiles) : launch_conv_h<NT, MODE, TH, OCC, SQ>(c, a, n_ntiles);
 }
 
 template <int NT, int MODE, int TH, int TPS>
@@ -913,94 +998,14 @@ int launch_conv_p(const LaunchCtx& c, const ConvArgs& a, int n_ntiles) {
     const int slots = c.n_cu * ((lds > 80 * 1024) ? 1 : c.wg_per_cu);
     const int rounds = (n_items + slots - 1) / slots;
     const int grid = (n_items + rounds - 1) / rounds;  // <= slots, balanced: every workgroup gets rounds or rounds-1 items
+    ProfScope ps(c, "k_conv_mfma_p<%d,%d,%d,%d>", NT, MODE, TH, TPS);
     if (a.ksplit > 1) plan_need((long long)n_items * 4 * (((TH / 2) / (4 / NT)) * 16 * 64) * 4, 0);
-    OG_LAUNCH((k_conv_mfma_p<NT, MODE, TH, TPS>), dim3(grid), dim3(256), lds, c.stream, a, n_items);
+    OG_LAUNCH_LDS((k_conv_mfma_p<NT, MODE, TH, TPS>), dim3(grid), dim3(256), lds, c.stream, a, n_items);
     plan_inst("k_conv_mfma_p<%d, %d, %d, %d> ksplit=%d", NT, MODE, TH, TPS, a.ksplit);
     if (a.ksplit > 1) {
         OG_LAUNCH((k_splitk_epilogue<NT, MODE, TH>), dim3(a.n_spatial * n_ntiles), dim3(256), 4 * 5120, c.stream, a);
         plan_inst("k_splitk_epilogue<%d, %d, %d>", NT, MODE, TH);
     }
-    return OG_OK;
-}
-
-template <int NT, int MODE, int TH, int TPS>
-int set_conv_p_attr() {
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_p<NT, MODE, TH, TPS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               conv_p_lds<NT, MODE, TH, TPS>()));
-    return OG_OK;
-}
-
-template <int NT, int MODE, int TH>
-int set_conv_attr() {
-    constexpr int PAD = (MODE == 0) ? 1 : 0;
-    constexpr int lds = 2 * (16 + 2 * PAD) * (TH + 2 * PAD) * 128 + 2 * 32 * NT * 128;
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma<NT, MODE, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    return OG_OK;
-}
-
-int init_kernel_attrs() {  // must not run inside a stream capture
-    int rc;
-    if ((rc = set_conv_attr<2, 0, 8>())) return rc;
-    if ((rc = set_conv_attr<1, 0, 8>())) return rc;
-    if ((rc = set_conv_attr<2, 1, 8>())) return rc;
-    if ((rc = set_conv_p_attr<2, 0, 8, 1>())) return rc;
-    if ((rc = set_conv_p_attr<2, 0, 8, 3>())) return rc;
-    if ((rc = set_conv_p_attr<1, 0, 8, 1>())) return rc;
-    if ((rc = set_conv_p_attr<1, 0, 8, 3>())) return rc;
-    if ((rc = set_conv_p_attr<1, 0, 8, 9>())) return rc;
-    if ((rc = set_conv_p_attr<2, 1, 8, 1>())) return rc;
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<1, 0, 8, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               conv_o_lds<1, 0, 8>() + (12 * 20 + 352) * 4));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<2, 0, 8, 3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 0, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<1, 0, 8, 3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<1, 0, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<2, 2, 8, 3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 2, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<1, 2, 8, 3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<1, 2, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<2, 3, 8, 3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 3, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<1, 3, 8, 3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<1, 3, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<2, 2, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 2, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<1, 2, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<1, 2, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<2, 3, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 3, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<1, 3, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<1, 3, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<2, 0, 16, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 0, 16>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<1, 0, 16, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<1, 0, 16>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_wino<2>, hipFuncAttributeMaxDynamicSharedMemorySize, wino_lds<2>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_wino<1>, hipFuncAttributeMaxDynamicSharedMemorySize, wino_lds<1>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_wino_w<1>, hipFuncAttributeMaxDynamicSharedMemorySize, wino_w_lds<1>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_wino_w<2>, hipFuncAttributeMaxDynamicSharedMemorySize, wino_w_lds<2>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_wino_wp, hipFuncAttributeMaxDynamicSharedMemorySize, kWinoWpLds));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_wino_ps<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (wino_ps_lds<2, 1>())));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_wino_ps<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (wino_ps_lds<2, 2>())));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_wino_ps<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (wino_ps_lds<2, 4>())));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_wino_ps<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (wino_ps_lds<1, 1>())));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_wino_ps<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (wino_ps_lds<1, 2>())));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_wino_ps<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (wino_ps_lds<1, 4>())));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<2, 1, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 1, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<2, 0, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 0, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<1, 0, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<1, 0, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<2, 0, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 0, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_o<1, 0, 8, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<1, 0, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_h<1, 0, 8, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               conv_o_lds<1, 0, 8>() + (12 * 20 + 352) * 4));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_h<2, 0, 16, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 0, 16>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_h<2, 0, 16, 2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 0, 16>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_h<1, 0, 16, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<1, 0, 16>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_h<2, 0, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 0, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_h<1, 0, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<1, 0, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_h<2, 1, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 1, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_f<1, 0, 8, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               conv_o_lds<1, 0, 8>() + (12 * 20 + 352) * 4));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_f<2, 0, 16, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 0, 16>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_f<2, 0, 16, 2, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 0, 16>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_f<1, 0, 16, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<1, 0, 16>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_f<2, 0, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 0, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_f<1, 0, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<1, 0, 8>()));
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_f<2, 1, 8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<2, 1, 8>()));
-    if ((rc = set_conv_p_attr<2, 0, 16, 1>())) return rc;
-    if ((rc = set_conv_p_attr<2, 0, 16, 3>())) return rc;
-    if ((rc = set_conv_p_attr<1, 0, 16, 3>())) return rc;
-    if ((rc = set_conv_p_attr<1, 0, 16, 9>())) return rc;
-    if ((rc = set_conv_p_attr<2, 2, 8, 1>())) return rc;
-    if ((rc = set_conv_p_attr<1, 2, 8, 1>())) return rc;
     return OG_OK;
 }
 
@@ -1032,6 +1037,8 @@ int launch_conv(og_unet* h, const ConvLayer& L, int B, const Act& in, int in_off
         if (h->d_tile_counter) (void)hipMemsetAsync(h->d_tile_counter, 0x01, kTileCounters * sizeof(int), h->stream);
         return fail(OG_EHIP, "injected launch failure (option inject_fault)");
     }
+    if (L.mode == 0 && (out.H != in.H || out.W != in.W)) return fail(OG_EINVAL, "conv shape mismatch");
+    if (L.mode != 0 && (out.H != 2 * in.H || out.W != 2 * in.W)) return fail(OG_EINVAL, "convT shape mismatch");
     // 16x16 tiles only for the 3x3 convs of the persistent kernel, and only when every tile is full
     const bool full16 = (L.mode == 0 && in.H % 16 == 0 && in.W % 16 == 0);
     bool big = full16 && h->tile_h == 16 && (h->conv_impl == 1 || h->conv_impl == 2);
@@ -1039,50 +1046,21 @@ int launch_conv(og_unet* h, const ConvLayer& L, int B, const Act& in, int in_off
     // high-resolution layers and the 32-column kernel prefer three 8x16 workgroups per CU
     if (h->conv_impl == 2 && h->tile_h == 0) big = full16 && L.NT == 2 && in.H <= 64 && in.W <= 64;
     if (h->fuse.active) big = false;  // per-tile count slots are laid out for 8x16 tiles
-    const int th = big ? 16 : 8;
-    ConvArgs a;
-    a.in = in.p;
-    a.in_frame_stride = in.frame_stride();
-    a.in_pix_stride = in.C;
-    a.in_ch_off = in_off;
+    // F layout (f16 mode): the views' strides are already in 4-byte units (arena_layout); channel offsets become such units here
+    const int cdiv = (h->precision == 2) ? 2 : 1;
+    ConvArgs a = conv_args({in.p, in.frame_stride(), in.C, in_off / cdiv}, {out.p, out.frame_stride(), out.C, out_off / cdiv},
+                           pool ? ConvView{pool->p, pool->frame_stride(), pool->C, 0} : ConvView{}, ConvView{}, L.d_w, L.d_scale, L.d_shift,
+                           L.Cout_p, h->d_zero, (L.mode == 0) ? 1 : 0);
     a.n_chunks = L.Cin_p / 32;
     a.H = in.H;
     a.W = in.W;
     a.tiles_x = (in.W + 15) / 16;
-    a.tiles_y = (in.H + th - 1) / th;
-    a.n_spatial = B * a.tiles_x * a.tiles_y;
-    a.wpk = L.d_w;
-    a.scale = L.d_scale;
-    a.shift = L.d_shift;
-    a.aff_mod = L.Cout_p;
-    a.out = out.p;
-    a.out_frame_stride = out.frame_stride();
-    a.out_pix_stride = out.C;
-    a.out_ch_off = out_off;
-    a.pool = pool ? pool->p : nullptr;
-    a.pool_frame_stride = pool ? pool->frame_stride() : 0;
-    a.pool_pix_stride = pool ? pool->C : 0;
-    a.pool_ch_off = 0;
-    a.zero_page = h->d_zero;
-    a.act = (L.mode == 0) ? 1 : 0;
-    a.res = nullptr;
-    a.res_frame_stride = 0;
-    a.res_pix_stride = 0;
-    a.res_ch_off = 0;
-    const LaunchCtx ctx{h->stream, h->n_cu, h->wg_per_cu, h->xcd_group};
+    auto set_tile_h = [&](int th) {   // rows of a spatial tile: 16 (`big`) or 8
+        a.tiles_y = (in.H + th - 1) / th;
+        a.n_spatial = B * a.tiles_x * a.tiles_y;
+    };
+    set_tile_h(big ? 16 : 8);
     a.prio_mode = h->prio_mode;
-    a.first_u8 = nullptr;
-    a.first_w9 = nullptr;
-    a.first_scale = nullptr;
-    a.first_shift = nullptr;
-    a.head_w = nullptr;
-    a.head_bias = 0.f;
-    a.head_thr = 0.5f;
-    a.head_boxes = nullptr;
-    a.head_logits = nullptr;
-    a.head_mask = nullptr;
-    a.head_area = nullptr;
-    a.head_store_act = 0;
     a.range_flag = h->d_range;
     if (h->fuse.active) {  // set by enqueue_last_with_head for exactly one launch
         a.head_w = h->d_head_w;
@@ -1094,90 +1072,40 @@ int launch_conv(og_unet* h, const ConvLayer& L, int B, const Act& in, int in_off
         a.head_area = h->fuse.area;
         a.head_store_act = h->keep_taps;
     }
-    a.ksplit = 1;
-    a.vsplit = 1;
     a.partial = h->d_partial;
     a.tile_counter = (h->splitk_fused && h->d_tile_counter) ? h->d_tile_counter : nullptr;
-    a.k_half = 0;
-    if (h->precision == 2) {   // opt-in f16 mode: k_conv_mfma_f on the occupancy-shaped tiles, never split-K ("splitk" is refused)
-        // F layout: the views' strides are already in 4-byte units (arena_layout); channel offsets become such units here
-        a.in_ch_off = in_off / 2;
-        a.out_ch_off = out_off / 2;
-        a.n_chunks = (L.Cin_p + 63) / 64;
-        a.k_half = (L.Cin_p % 64) ? 1 : 0;
-        big = full16 && h->tile_h != 8;          // as split precision: 16-row tiles wherever they tile the image
-        if (a.head_w != nullptr) big = false;    // per-tile count slots of the fused head are laid out for 8x16 tiles
-        const int th_f = big ? 16 : 8;
-        a.tiles_y = (in.H + th_f - 1) / th_f;
-        a.n_spatial = B * a.tiles_x * a.tiles_y;
-        a.wpk = L.d_w_f;
-        a.stamps = nullptr;
-        const double px_f = (double)B * in.H * in.W;
-        int rc_f;
-        if (L.mode == 0) {
-            if (out.H != in.H || out.W != in.W) return fail(OG_EINVAL, "conv shape mismatch");
-            const int n_ntiles = L.Cout_p / (32 * L.NT);
-            const double fl = 2.0 * px_f * 9.0 * L.Cin * L.Cout;
-            if (big) {
-                prof_begin(h, L.name, L.NT == 2 ? "k_conv_mfma_f<2,0,16>" : "k_conv_mfma_f<1,0,16>", fl);
-                if (L.NT == 2) rc_f = h->h_square ? launch_conv_f<2, 0, 16, 2, true>(ctx, a, n_ntiles) : launch_conv_f<2, 0, 16, 2>(ctx, a, n_ntiles);
-                else rc_f = launch_conv_f<1, 0, 16, 2>(ctx, a, n_ntiles);
-            } else {
-                prof_begin(h, L.name, L.NT == 2 ? "k_conv_mfma_f<2,0,8>" : "k_conv_mfma_f<1,0,8>", fl);
-                rc_f = (L.NT == 2) ? launch_conv_f<2, 0, 8, 3>(ctx, a, n_ntiles) : launch_conv_f<1, 0, 8, 3>(ctx, a, n_ntiles);
-            }
-        } else {
-            if (out.H != 2 * in.H || out.W != 2 * in.W) return fail(OG_EINVAL, "convT shape mismatch");
-            a.tiles_y = (in.H + 7) / 8;
-            a.n_spatial = B * a.tiles_x * a.tiles_y;
-            prof_begin(h, L.name, "k_conv_mfma_f<2,1,8>", 2.0 * px_f * 4.0 * L.Cin * L.Cout);
-            rc_f = launch_conv_f<2, 1, 8, 3>(ctx, a, 4 * L.Cout_p / 64);
-        }
-        prof_end(h);
-        return rc_f;
-    }
-    if (h->precision == 1) {   // opt-in split precision: always the occupancy-shaped kernel, no split-K
+    const double px = (double)B * in.H * in.W;
+    const LaunchCtx ctx{h->stream, h->n_cu, h->wg_per_cu, h->xcd_group, h, &L.name, 2.0 * px * ((L.mode == 0) ? 9.0 : 4.0) * L.Cin * L.Cout};
+    // column tiles of the launch: 32 NT output channels each; the transposed conv is one GEMM with N = 4 Cout on 64-column tiles
+    const int n_ntiles = (L.mode == 0) ? L.Cout_p / (32 * L.NT) : 4 * L.Cout_p / 64;
+    if (h->precision != 0) {   // opt-in split precision (1: k_conv_mfma_h) / f16 mode (2: k_conv_mfma_f): always the occupancy-shaped kernel
+        const bool f16 = h->precision == 2;
         // tile height: an MFMA step is 5x shorter here than in the f32 kernels, so barriers and staged bytes per MFMA weigh
         // more: 16-row tiles wherever they tile the image ("tile_h" 8 forces 8 rows, 16 / 0 = this rule)
         big = full16 && h->tile_h != 8;
         if (a.head_w != nullptr) big = false;   // per-tile count slots of the fused head are laid out for 8x16 tiles
-        {   // small launches (one frame per chain): split K over workgroups exactly as the f32 occupancy kernel does
-            const int nt_s = (L.mode == 0) ? L.Cout_p / (32 * L.NT) : 4 * L.Cout_p / 64;
+        if (f16) {   // F layout: K walks 64-channel chunks; never split-K ("splitk" is refused)
+            a.n_chunks = (L.Cin_p + 63) / 64;
+            a.k_half = (L.Cin_p % 64) ? 1 : 0;
+            a.wpk = L.d_w_f;
+        } else {   // small launches (one frame per chain): split K over workgroups exactly as the f32 occupancy kernel does
             const int tiles8 = B * a.tiles_x * ((in.H + 7) / 8);
             const int k_units = a.n_chunks;   // whole channel chunks: finer parts measured 2 % slower on these (5x shorter) steps
-            const int ks = pick_ksplit(tiles8 * nt_s, k_units, h->n_cu * h->splitk_slots, (L.NT == 2) ? 2 : 1,
+            const int ks = pick_ksplit(tiles8 * n_ntiles, k_units, h->n_cu * h->splitk_slots, (L.NT == 2) ? 2 : 1,
                                        h->splitk != 0 && h->d_partial != nullptr && h->d_tile_counter != nullptr, h->splitk_div);
             a.ksplit = (ks > 1 && a.head_w == nullptr) ? ks : 1;
             if (a.ksplit > 1) big = false;
+            a.wpk = L.d_w_h;
         }
-        const int th_h = big ? 16 : 8;
-        a.tiles_y = (in.H + th_h - 1) / th_h;
-        a.n_spatial = B * a.tiles_x * a.tiles_y;
-        a.wpk = L.d_w_h;
-        a.stamps = nullptr;
-        const double px_h = (double)B * in.H * in.W;
-        int rc_h;
-        if (L.mode == 0) {
-            if (out.H != in.H || out.W != in.W) return fail(OG_EINVAL, "conv shape mismatch");
-            const int n_ntiles = L.Cout_p / (32 * L.NT);
-            const double fl = 2.0 * px_h * 9.0 * L.Cin * L.Cout;
-            if (big) {
-                prof_begin(h, L.name, L.NT == 2 ? "k_conv_mfma_h<2,0,16>" : "k_conv_mfma_h<1,0,16>", fl);
-                if (L.NT == 2) rc_h = h->h_square ? launch_conv_h<2, 0, 16, 2, true>(ctx, a, n_ntiles) : launch_conv_h<2, 0, 16, 2>(ctx, a, n_ntiles);
-                else rc_h = launch_conv_h<1, 0, 16, 2>(ctx, a, n_ntiles);
-            } else {
-                prof_begin(h, L.name, L.NT == 2 ? "k_conv_mfma_h<2,0,8>" : "k_conv_mfma_h<1,0,8>", fl);
-                rc_h = (L.NT == 2) ? launch_conv_h<2, 0, 8, 3>(ctx, a, n_ntiles) : launch_conv_h<1, 0, 8, 3>(ctx, a, n_ntiles);
+        set_tile_h(big ? 16 : 8);
+        if (L.mode != 0) return launch_conv_hf<2, 1, 8, 3>(ctx, a, n_ntiles, f16);
+        return og_pick<2, 1>(L.NT, [&](auto nt) {
+            constexpr int NT = decltype(nt)::value;
+            if constexpr (NT == 2) {   // 16x16 tiles of the 64-column kernel: 2x2 sub-tiles per wave ("h_square")
+                if (big && h->h_square) return launch_conv_hf<2, 0, 16, 2, true>(ctx, a, n_ntiles, f16);
             }
-        } else {
-            if (out.H != 2 * in.H || out.W != 2 * in.W) return fail(OG_EINVAL, "convT shape mismatch");
-            a.tiles_y = (in.H + 7) / 8;
-            a.n_spatial = B * a.tiles_x * a.tiles_y;
-            prof_begin(h, L.name, "k_conv_mfma_h<2,1,8>", 2.0 * px_h * 4.0 * L.Cin * L.Cout);
-            rc_h = launch_conv_h<2, 1, 8, 3>(ctx, a, 4 * L.Cout_p / 64);
-        }
-        prof_end(h);
-        return rc_h;
+            return big ? launch_conv_hf<NT, 0, 16, 2>(ctx, a, n_ntiles, f16) : launch_conv_hf<NT, 0, 8, 3>(ctx, a, n_ntiles, f16);
+        });
     }
     int impl = h->conv_impl;
     int NTu = L.NT;   // column sub-tiles per workgroup of THIS launch (32-column tiles on split 3x3 launches, see splitk_nt1)
@@ -1186,15 +1114,14 @@ int launch_conv(og_unet* h, const ConvLayer& L, int B, const Act& in, int in_off
                           (a.head_w == nullptr || L.NT == 1);
     if (!use_wino && (impl == 1 || impl == 2)) {
         const bool sk_occ = (impl == 2 && h->splitk_occ);
-        const int nt = (L.mode == 0) ? L.Cout_p / (32 * L.NT) : 4 * L.Cout_p / 64;
         const int tiles8 = B * a.tiles_x * ((in.H + 7) / 8);
         // occupancy split-K of a 3x3 conv: parts are ranges of (chunk, tap) steps, at least splitk_min_steps each
         const int k_units = (sk_occ && L.mode == 0) ? (a.n_chunks * 9) / h->splitk_min_steps : a.n_chunks;
-        int ks = pick_ksplit(tiles8 * nt, k_units, h->n_cu * (sk_occ ? h->splitk_slots : h->wg_per_cu), (L.NT == 2) ? 2 : 1,
+        int ks = pick_ksplit(tiles8 * n_ntiles, k_units, h->n_cu * (sk_occ ? h->splitk_slots : h->wg_per_cu), (L.NT == 2) ? 2 : 1,
                              h->splitk != 0 && h->d_partial != nullptr, sk_occ ? h->splitk_div : 4);
         bool nt1 = false;   // 32-column tiles where they still leave room to split K
         if (ks > 1 && sk_occ && h->splitk_nt1 && L.mode == 0 && L.NT == 2 && L.d_w1 != nullptr) {
-            const int ks1 = pick_ksplit(tiles8 * nt * 2, k_units, h->n_cu * h->splitk_slots, 1, true, h->splitk_div);
+            const int ks1 = pick_ksplit(tiles8 * n_ntiles * 2, k_units, h->n_cu * h->splitk_slots, 1, true, h->splitk_div);
             if (ks1 > 1) {
                 ks = ks1;
                 nt1 = true;
@@ -1203,15 +1130,14 @@ int launch_conv(og_unet* h, const ConvLayer& L, int B, const Act& in, int in_off
         // The occupancy variant needs at least one full round of workgroups (2/CU on 16x16 tiles, 3/CU on
         // 8x16); below that the persistent kernel (2/CU, balanced static schedule, split-K when the launch
         // cannot even fill a quarter of the chip) is faster.
-        const bool occ_fills = h->occ_min_pct ? (a.n_spatial * nt * 100 >= h->n_cu * h->occ_min_pct)
-                                              : (a.n_spatial * nt >= h->n_cu * (big ? 2 : 3));
+        const bool occ_fills = h->occ_min_pct ? (a.n_spatial * n_ntiles * 100 >= h->n_cu * h->occ_min_pct)
+                                              : (a.n_spatial * n_ntiles >= h->n_cu * (big ? 2 : 3));
         const bool split = (ks > 1 && a.head_w == nullptr);  // the fused head lives in the conv epilogue: no split-K on that launch
         if (split || (impl == 2 && !occ_fills)) {
             // h->splitk_occ: the K parts run on the (leaner) occupancy kernel, one workgroup per part; else the persistent kernel
             impl = (split && impl == 2 && h->splitk_occ) ? 4 : 1;
             big = false;
-            a.tiles_y = (in.H + 7) / 8;
-            a.n_spatial = tiles8;
+            set_tile_h(8);
             a.ksplit = split ? ks : 1;
             if (impl == 4 && nt1) {
                 NTu = 1;
@@ -1219,37 +1145,22 @@ int launch_conv(og_unet* h, const ConvLayer& L, int B, const Act& in, int in_off
             }
         }
     }
-    a.stamps = nullptr;
     if (h->probing && h->prof && h->d_stamps) {  // diagnostic clock stamps: og_unet_clock_probe only
         a.stamps = h->d_stamps + 4 * 1024 * h->prof->size();
     }
-    const double px = (double)B * in.H * in.W;
-    int rc;
     if (L.mode == 0) {
-        const int n_ntiles = L.Cout_p / (32 * L.NT);
-        if (out.H != in.H || out.W != in.W) return fail(OG_EINVAL, "conv shape mismatch");
-        const double fl = 2.0 * px * 9.0 * L.Cin * L.Cout;
         if (use_wino) {
             if (const int wb = pick_wino_w(h, L, B, in.H, in.W)) {
-                a.tiles_y = in.H / 8;
-                a.n_spatial = B * a.tiles_x * a.tiles_y;
+                set_tile_h(8);
                 a.wpk = (L.NT == 2) ? L.d_ww1 : L.d_ww;
-                static const char* nmw[2][3] = {{"k_conv_wino_w<1,1>", "k_conv_wino_w<1,2>", "k_conv_wino_wp<1>"},
-                                                {"k_conv_wino_w<2,1>", "k_conv_wino_w<2,2>", "k_conv_wino_wp<2>"}};
-                prof_begin(h, L.name, nmw[L.NT - 1][wb == 4 ? 2 : wb - 1], fl);   // <NT of the layer's canonical form[, WB]>
                 if (wb == 4) {
                     a.partial = h->d_partial;
                     a.tile_counter = h->d_tile_counter;
-                    rc = launch_conv_wino_wp(ctx, a, L.Cout_p / 32);
-                } else {
-                    rc = (wb == 1) ? launch_conv_wino_w<1>(ctx, a, L.Cout_p / 32) : launch_conv_wino_w<2>(ctx, a, L.Cout_p / 32);
+                    return launch_conv_wino_wp(ctx, a, L.Cout_p / 32, L.NT);
                 }
-                if (rc == OG_OK) plan_inst(wb == 4 ? "k_conv_wino_wp nt=%d" : wb == 1 ? "k_conv_wino_w<1> nt=%d" : "k_conv_wino_w<2> nt=%d", L.NT);   // nt: the layer's canonical form (its weight pack)
-                prof_end(h);
-                return rc;
+                return (wb == 1) ? launch_conv_wino_w<1>(ctx, a, L.Cout_p / 32, L.NT) : launch_conv_wino_w<2>(ctx, a, L.Cout_p / 32, L.NT);
             }
-            a.tiles_y = in.H / (32 / L.NT);
-            a.n_spatial = B * a.tiles_x * a.tiles_y;
+            set_tile_h(32 / L.NT);
             a.wpk = L.d_ww;
             // A launch that leaves most of the chip idle (one frame per chain, deep layers of small micro-batches) spreads the 16
             // Winograd positions of a tile over 16 / PN workgroups (k_conv_wino_ps): the same sums, bit for bit -- a scheduling
@@ -1266,106 +1177,42 @@ int launch_conv(og_unet* h, const ConvLayer& L, int B, const Act& in, int in_off
             if (pn) {
                 a.partial = h->d_partial;
                 a.tile_counter = h->d_tile_counter;
-                static const char* nm[2][3] = {{"k_conv_wino_ps<1,1>", "k_conv_wino_ps<1,2>", "k_conv_wino_ps<1,4>"},
-                                               {"k_conv_wino_ps<2,1>", "k_conv_wino_ps<2,2>", "k_conv_wino_ps<2,4>"}};
-                prof_begin(h, L.name, nm[L.NT - 1][pn == 1 ? 0 : pn == 2 ? 1 : 2], fl);
-                if (L.NT == 2) rc = (pn == 1) ? launch_conv_wino_ps<2, 1>(ctx, a, n_ntiles) : (pn == 2) ? launch_conv_wino_ps<2, 2>(ctx, a, n_ntiles)
-                                                                                                        : launch_conv_wino_ps<2, 4>(ctx, a, n_ntiles);
-                else rc = (pn == 1) ? launch_conv_wino_ps<1, 1>(ctx, a, n_ntiles) : (pn == 2) ? launch_conv_wino_ps<1, 2>(ctx, a, n_ntiles)
-                                                                                             : launch_conv_wino_ps<1, 4>(ctx, a, n_ntiles);
-                prof_end(h);
-                return rc;
             }
-            prof_begin(h, L.name, L.NT == 2 ? "k_conv_wino<2>" : "k_conv_wino<1>", fl);
-            rc = (L.NT == 2) ? launch_conv_wino<2>(ctx, a, n_ntiles) : launch_conv_wino<1>(ctx, a, n_ntiles);
-        } else if (impl == 0) {
-            prof_begin(h, L.name, L.NT == 2 ? "k_conv_mfma<2,0,8>" : "k_conv_mfma<1,0,8>", fl);
-            rc = (L.NT == 2) ? launch_conv_t<2, 0, TH>(h, a, n_ntiles) : launch_conv_t<1, 0, TH>(h, a, n_ntiles);
-        } else if (impl == 2 && big) {
-            a.ksplit = 1;
-            prof_begin(h, L.name, L.NT == 2 ? "k_conv_mfma_o<2,0,16>" : "k_conv_mfma_o<1,0,16>", fl);
-            rc = (L.NT == 2) ? launch_conv_o<2, 0, 16, 2>(ctx, a, n_ntiles) : launch_conv_o<1, 0, 16, 2>(ctx, a, n_ntiles);
-        } else if (impl == 4) {
-            prof_begin(h, L.name, NTu == 2 ? "k_conv_mfma_o<2,0,8>+splitK" : "k_conv_mfma_o<1,0,8>+splitK", fl);
-            rc = (NTu == 2) ? launch_conv_o<2, 0, TH, 3>(ctx, a, n_ntiles) : launch_conv_o<1, 0, TH, 3>(ctx, a, L.Cout_p / 32);
-        } else if (impl == 2 || impl == 3) {
-            a.ksplit = 1;
-            prof_begin(h, L.name, L.NT == 2 ? "k_conv_mfma_o<2,0,8>" : "k_conv_mfma_o<1,0,8>", fl);
-            if (impl == 2)
-                rc = (L.NT == 2) ? launch_conv_o<2, 0, TH, 3>(ctx, a, n_ntiles) : launch_conv_o<1, 0, TH, 3>(ctx, a, n_ntiles);
-            else
-                rc = (L.NT == 2) ? launch_conv_o<2, 0, TH, 4>(ctx, a, n_ntiles) : launch_conv_o<1, 0, TH, 4>(ctx, a, n_ntiles);
-        } else if (big && L.NT == 2) {
-            a.ksplit = 1;
-            if (h->tps_nt2 == 3) {
-                prof_begin(h, L.name, "k_conv_mfma_p<2,0,16,3>", fl);
-                rc = launch_conv_p<2, 0, 16, 3>(ctx, a, n_ntiles);
-            } else {
-                prof_begin(h, L.name, "k_conv_mfma_p<2,0,16,1>", fl);
-                rc = launch_conv_p<2, 0, 16, 1>(ctx, a, n_ntiles);
-            }
-        } else if (big) {
-            a.ksplit = 1;
-            if (h->tps_nt1 == 9) {
-                prof_begin(h, L.name, "k_conv_mfma_p<1,0,16,9>", fl);
-                rc = launch_conv_p<1, 0, 16, 9>(ctx, a, n_ntiles);
-            } else {
-                prof_begin(h, L.name, "k_conv_mfma_p<1,0,16,3>", fl);
-                rc = launch_conv_p<1, 0, 16, 3>(ctx, a, n_ntiles);
-            }
-        } else if (L.NT == 2) {
-            if (h->tps_nt2 == 3) {
-                prof_begin(h, L.name, "k_conv_mfma_p<2,0,8,3>", fl);
-                rc = launch_conv_p<2, 0, TH, 3>(ctx, a, n_ntiles);
-            } else {
-                prof_begin(h, L.name, "k_conv_mfma_p<2,0,8,1>", fl);
-                rc = launch_conv_p<2, 0, TH, 1>(ctx, a, n_ntiles);
-            }
-        } else {
-            if (h->tps_nt1 == 9) {
-                prof_begin(h, L.name, "k_conv_mfma_p<1,0,8,9>", fl);
-                rc = launch_conv_p<1, 0, TH, 9>(ctx, a, n_ntiles);
-            } else if (h->tps_nt1 == 3) {
-                prof_begin(h, L.name, "k_conv_mfma_p<1,0,8,3>", fl);
-                rc = launch_conv_p<1, 0, TH, 3>(ctx, a, n_ntiles);
-            } else {
-                prof_begin(h, L.name, "k_conv_mfma_p<1,0,8,1>", fl);
-                rc = launch_conv_p<1, 0, TH, 1>(ctx, a, n_ntiles);
-            }
+            return og_pick<2, 1>(L.NT, [&](auto nt) {
+                constexpr int NT = decltype(nt)::value;
+                if (!pn) return launch_conv_wino<NT>(ctx, a, n_ntiles);
+                return og_pick<1, 2, 4>(pn, [&](auto pn_) { return launch_conv_wino_ps<NT, decltype(pn_)::value>(ctx, a, n_ntiles); });
+            });
         }
-        prof_end(h);
-        return rc;
+        // the direct kernels, by the width of this launch's column tiles
+        return og_pick<2, 1>(NTu, [&](auto nt) {
+            constexpr int NT = decltype(nt)::value;
+            if (impl == 0) return launch_conv_t<NT, 0, TH>(ctx, a, n_ntiles);
+            if (impl == 2 && big) return launch_conv_o<NT, 0, 16, 2>(ctx, a, n_ntiles);
+            if (impl == 4) return launch_conv_o<NT, 0, TH, 3>(ctx, a, L.Cout_p / (32 * NT));
+            if (impl == 2) return launch_conv_o<NT, 0, TH, 3>(ctx, a, n_ntiles);
+            if (impl == 3) return launch_conv_o<NT, 0, TH, 4>(ctx, a, n_ntiles);
+            // the persistent kernel: taps per step by option ("tps_nt2", "tps_nt1")
+            if constexpr (NT == 2) {
+                return og_pick<3, 1>(h->tps_nt2, [&](auto tps) {
+                    constexpr int TPS = decltype(tps)::value;
+                    return big ? launch_conv_p<2, 0, 16, TPS>(ctx, a, n_ntiles) : launch_conv_p<2, 0, TH, TPS>(ctx, a, n_ntiles);
+                });
+            } else {
+                if (big) return og_pick<9, 3>(h->tps_nt1, [&](auto tps) { return launch_conv_p<1, 0, 16, decltype(tps)::value>(ctx, a, n_ntiles); });
+                return og_pick<9, 3, 1>(h->tps_nt1, [&](auto tps) { return launch_conv_p<1, 0, TH, decltype(tps)::value>(ctx, a, n_ntiles); });
+            }
+        });
     }
-    if (out.H != 2 * in.H || out.W != 2 * in.W) return fail(OG_EINVAL, "convT shape mismatch");
-    const double flt = 2.0 * px * 4.0 * L.Cin * L.Cout;
     // a launch that leaves most of the chip idle (one frame per chain): the same sums on 32-pixel x 32-column wave tiles -- a
     // scheduling choice among bit-identical kernels, so B may enter
-    if (h->conv_impl == 2 && a.ksplit == 1 && h->convt_w && L.d_w1 != nullptr && (long long)B * a.tiles_x * ((in.H + 7) / 8) * (4 * L.Cout_p / 64) * 2 <= h->n_cu) {
+    if (h->conv_impl == 2 && a.ksplit == 1 && h->convt_w && L.d_w1 != nullptr && (long long)B * a.tiles_x * ((in.H + 7) / 8) * n_ntiles * 2 <= h->n_cu) {
         a.wpk = L.d_w1;
-        a.zdiv = L.Cout_p / 32;   // column tiles of 32 / 4 per workgroup
-        a.frames = B;
-        if ((long long)B * a.zdiv > 65535) return fail(OG_EINVAL, "k_convt_w: grid.z");
-        prof_begin(h, L.name, "k_convt_w<1,1,8>", flt);
-        OG_LAUNCH(k_convt_w, dim3((in.W + 15) / 16, (in.H + 1) / 2, B * a.zdiv), dim3(256), 0, h->stream, a);
-        prof_end(h);
-        return OG_OK;
+        return launch_convt_w(ctx, a, L.Cout_p / 32);
     }
-    if (impl == 0) {
-        prof_begin(h, L.name, "k_conv_mfma<2,1,8>", flt);
-        rc = launch_conv_t<2, 1, TH>(h, a, 4 * L.Cout_p / 64);
-    } else if (impl == 4) {
-        prof_begin(h, L.name, "k_conv_mfma_o<2,1,8>+splitK", flt);
-        rc = launch_conv_o<2, 1, TH, 3>(ctx, a, 4 * L.Cout_p / 64);
-    } else if (impl >= 2 && h->convt_occ) {
-        a.ksplit = 1;
-        prof_begin(h, L.name, "k_conv_mfma_o<2,1,8>", flt);
-        rc = launch_conv_o<2, 1, TH, 3>(ctx, a, 4 * L.Cout_p / 64);
-    } else {
-        prof_begin(h, L.name, "k_conv_mfma_p<2,1,8,1>", flt);
-        rc = launch_conv_p<2, 1, TH, 1>(ctx, a, 4 * L.Cout_p / 64);
-    }
-    prof_end(h);
-    return rc;
+    if (impl == 0) return launch_conv_t<2, 1, TH>(ctx, a, n_ntiles);
+    if (impl == 4 || (impl >= 2 && h->convt_occ)) return launch_conv_o<2, 1, TH, 3>(ctx, a, n_ntiles);
+    return launch_conv_p<2, 1, TH, 1>(ctx, a, n_ntiles);
 }
 
 enum { KIND_U8 = 0, KIND_F32 = 1 };
@@ -1377,9 +1224,9 @@ int enqueue_first(og_unet* h, int kind, const void* in, int B, int H, int W) {
     const int Cp0 = cp32(h->features[0]);
     const int tiles = ((W + 15) / 16) * ((H + 15) / 16);
     const Act& o = h->A[0];
-    prof_begin(h, "downs.0.net.0.weight", h->precision == 2 ? (kind == KIND_U8 ? "k_conv_first_f<u8>" : "k_conv_first_f<f32>")
-                                          : kind == KIND_U8 ? "k_conv_first<u8>" : "k_conv_first<f32>",
-               2.0 * B * H * W * 9.0 * h->features[0]);
+    ProfScope ps(h, "downs.0.net.0.weight", h->precision == 2 ? (kind == KIND_U8 ? "k_conv_first_f<u8>" : "k_conv_first_f<f32>")
+                                            : kind == KIND_U8 ? "k_conv_first<u8>" : "k_conv_first<f32>",
+                 2.0 * B * H * W * 9.0 * h->features[0]);
     if (h->precision == 2 && kind == KIND_U8)
         OG_LAUNCH(k_conv_first_f<uint8_t>, dim3(B * tiles), dim3(256), 0, h->stream, (const uint8_t*)in, o.p,
                            h->d_first_w, h->d_first_scale, h->d_first_shift, H, W, Cp0, o.C, o.frame_stride(), h->d_range);
@@ -1398,7 +1245,6 @@ int enqueue_first(og_unet* h, int kind, const void* in, int B, int H, int W) {
     else
         OG_LAUNCH(k_conv_first<float>, dim3(B * tiles), dim3(256), 0, h->stream, (const float*)in, o.p,
                            h->d_first_w, h->d_first_scale, h->d_first_shift, H, W, Cp0, o.C, o.frame_stride(), (int*)nullptr);
-    prof_end(h);
     return OG_OK;
 }
 
@@ -1417,8 +1263,7 @@ int enqueue_first_fused(og_unet* h, const uint8_t* gray, int B, int H, int W) {
     const ConvLayer& L = h->enc_b[0];
     const Act& out = h->CAT[0];
     const Act& pool = h->P[0];
-    ConvArgs a;
-    memset(&a, 0, sizeof(a));
+    ConvArgs a{};   // no input view (the kernel reads the u8 frame), one column tile, no split: everything not set here is zero / null
     a.n_chunks = 1;
     a.H = H;
     a.W = W;
@@ -1433,7 +1278,6 @@ int enqueue_first_fused(og_unet* h, const uint8_t* gray, int B, int H, int W) {
     a.out = out.p;
     a.out_frame_stride = out.frame_stride();
     a.out_pix_stride = out.C;
-    a.out_ch_off = 0;
     a.pool = pool.p;
     a.pool_frame_stride = pool.frame_stride();
     a.pool_pix_stride = pool.C;
@@ -1445,22 +1289,19 @@ int enqueue_first_fused(og_unet* h, const uint8_t* gray, int B, int H, int W) {
     a.first_w9 = h->d_first_w;
     a.first_scale = h->d_first_scale;
     a.first_shift = h->d_first_shift;
-    constexpr int lds = conv_o_lds<1, 0, 8>() + (12 * 20 + 352) * 4;
-    prof_begin(h, "downs.0 (first + second conv fused)", h->precision == 2 ? "k_conv_mfma_f<1,0,8,FIRST>" : h->precision == 1 ? "k_conv_mfma_h<1,0,8,FIRST>" : "k_conv_mfma_o<1,0,8,FIRST>",
-               2.0 * B * H * W * 9.0 * (1.0 * h->features[0] + (double)h->features[0] * h->features[0]));
-    a.zdiv = 1;
-    a.zrcp = 1.0f;
-    a.zgroup_shift = 0;
-    a.frames = B;
     if (h->precision != 0) a.prio_mode = h->prio_mode;
+    constexpr int lds = conv_o_lds<1, 0, 8>() + kFirstLds;
+    ProfScope ps(h, "downs.0 (first + second conv fused)", h->precision == 2 ? "k_conv_mfma_f<1,0,8,FIRST>" : h->precision == 1 ? "k_conv_mfma_h<1,0,8,FIRST>" : "k_conv_mfma_o<1,0,8,FIRST>",
+                 2.0 * B * H * W * 9.0 * (1.0 * h->features[0] + (double)h->features[0] * h->features[0]));
+    const int gz = grid_z(LaunchCtx{h->stream, h->n_cu, h->wg_per_cu, h->xcd_group}, a, 1, a.tiles_x * a.tiles_y);   // one column tile: grid.z = B
+    if (gz < 0) return gz;
     if (h->precision == 2) {
-        OG_LAUNCH((k_conv_mfma_f<1, 0, 8, 3, true>), dim3(a.tiles_x, a.tiles_y, B), dim3(256), lds, h->stream, a);
-        plan_label_f("(k_conv_mfma_f<1, 0, 8, 3, true>)", a.n_chunks, a.k_half);
+        OG_LAUNCH_LDS((k_conv_mfma_f<1, 0, 8, 3, true>), dim3(a.tiles_x, a.tiles_y, gz), dim3(256), lds, h->stream, a);
+        plan_inst("(k_conv_mfma_f<1, 0, 8, 3, true>) chunks=%d k_half=%d", a.n_chunks, a.k_half);
     } else if (h->precision == 1)
-        OG_LAUNCH((k_conv_mfma_h<1, 0, 8, 3, true>), dim3(a.tiles_x, a.tiles_y, B), dim3(256), lds, h->stream, a);
+        OG_LAUNCH_LDS((k_conv_mfma_h<1, 0, 8, 3, true>), dim3(a.tiles_x, a.tiles_y, gz), dim3(256), lds, h->stream, a);
     else
-        OG_LAUNCH((k_conv_mfma_o<1, 0, 8, 3, true>), dim3(a.tiles_x, a.tiles_y, B), dim3(256), lds, h->stream, a);
-    prof_end(h);
+        OG_LAUNCH_LDS((k_conv_mfma_o<1, 0, 8, 3, true>), dim3(a.tiles_x, a.tiles_y, gz), dim3(256), lds, h->stream, a);
     return OG_OK;
 }
 
@@ -1530,7 +1371,7 @@ int enqueue_head(og_unet* h, int B, int H, int W, float thr, const int32_t* boxe
     const Act& u = h->UB[0];
     const int HW = H * W;
     const int bpf = (HW + 1023) / 1024;
-    prof_begin(h, "head", h->precision == 2 ? "k_head_f" : "k_head", 2.0 * B * HW * h->features[0]);
+    ProfScope ps(h, "head", h->precision == 2 ? "k_head_f" : "k_head", 2.0 * B * HW * h->features[0]);
     if (h->precision == 2)
         OG_LAUNCH(k_head_f, dim3(B * bpf), dim3(256), 0, h->stream, u.p, u.frame_stride(), u.C, h->d_head_w,
                            h->head_bias, cp32(h->features[0]), HW, W, thr, boxes, logits, mask, area, bpf);
@@ -1540,7 +1381,6 @@ int enqueue_head(og_unet* h, int B, int H, int W, float thr, const int32_t* boxe
     else
         OG_LAUNCH(k_head<false>, dim3(B * bpf), dim3(256), 0, h->stream, u.p, u.frame_stride(), u.C, h->d_head_w,
                            h->head_bias, cp32(h->features[0]), HW, W, thr, boxes, logits, mask, area, bpf);
-    prof_end(h);
     return OG_OK;
 }
 

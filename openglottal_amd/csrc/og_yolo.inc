@@ -348,28 +348,19 @@ int launch_conv_fy(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {
     constexpr int lds = conv_o_lds<NT, MODE, 8>();
     static_assert(lds >= 4 * 5120, "the epilogue's per-wave scratch needs 20 KB");
     ConvArgs a = a_in;
-    const int frames = a.n_spatial / (a.tiles_x * a.tiles_y);
-    a.zdiv = n_ntiles;
-    a.frames = frames;
-    a.zgroup_shift = 0;
-    if (c.xcd_group && a.zdiv > 1) {
-        int txy = a.tiles_x * a.tiles_y, g = 8;
-        while (g > 1 && txy % 2 == 0) { txy /= 2; g /= 2; }
-        while (g > frames) g /= 2;
-        while ((1 << a.zgroup_shift) < g) ++a.zgroup_shift;
-    }
-    const int G = 1 << a.zgroup_shift, groups = (frames + G - 1) / G;
-    a.zrcp = 1.0f / (float)(a.zdiv * G);
-    if ((long long)groups * G * a.zdiv > 65535) return fail(OG_EINVAL, "micro-batch too large for one launch (grid.z): lower the chunk size");
-    OG_LAUNCH((k_conv_mfma_fy<NT, MODE, 3, F32OUT>), dim3(a.tiles_x, a.tiles_y, groups * G * a.zdiv), dim3(256), lds, c.stream, a);
+    const int gz = grid_z(c, a, n_ntiles, a.tiles_x * a.tiles_y);
+    if (gz < 0) return gz;
+    OG_LAUNCH_LDS((k_conv_mfma_fy<NT, MODE, 3, F32OUT>), dim3(a.tiles_x, a.tiles_y, gz), dim3(256), lds, c.stream, a);
     plan_inst("k_conv_mfma_fy<%d, %d, 3, %s> chunks=%d k_half=%d", NT, MODE, F32OUT ? "true" : "false", a.n_chunks, a.k_half);
     return OG_OK;
 }
 
-template <int NT, int MODE, bool F32OUT>
-int set_conv_fy_attr() {
-    HIPCHK(hipFuncSetAttribute((const void*)k_conv_mfma_fy<NT, MODE, 3, F32OUT>, hipFuncAttributeMaxDynamicSharedMemorySize, conv_o_lds<NT, MODE, 8>()));
-    return OG_OK;
+// What both precisions pass for an MFMA conv of the detector: the views in the kernels' 4-byte units (f32 views: es 1, the plain
+// strides), the weight image of the precision, the layer's affine and activation, the optional residual.  The K walk is the caller's.
+ConvArgs y_conv_args(const og_yolo* h, const YConv& L, const float* wpk, const YView& in, const YView& out, const YView* res) {
+    return conv_args({in.base, in.fs4(), in.ps4(), in.off4()}, {out.base, out.fs4(), out.ps4(), out.off4()}, ConvView{},
+                     res ? ConvView{res->base, res->fs4(), res->ps4(), res->off4()} : ConvView{}, wpk, L.d_scale, L.d_shift, L.Cout_p,
+                     h->d_zero, L.act);
 }
 
 // f16 mode ("precision" 2): every MFMA conv on k_conv_mfma_fy, the whole K range in ONE workgroup in ONE order at every B -- no
@@ -391,11 +382,7 @@ int y_launch_f(og_yolo* h, const YConv& L, int B, const void* in_u8, const YView
     }
     if (!L.d_wf) return fail(OG_ESTATE, "no f16 weight image for " + L.name);
     if (L.f32out != (out.es == 1) || in.es != 2) return fail(OG_ESTATE, "f16 mode: buffer format mismatch at " + L.name);
-    ConvArgs a{};
-    a.in = in.base;
-    a.in_frame_stride = in.fs4();
-    a.in_pix_stride = in.ps4();
-    a.in_ch_off = in.off4();
+    ConvArgs a = y_conv_args(h, L, L.d_wf, in, out, res);
     const int cpc = (L.Cin_p + 63) / 64;
     a.n_chunks = (L.kind == 4) ? 4 * cpc : cpc;
     a.k_half = (L.Cin_p % 64) ? 1 : 0;
@@ -405,33 +392,19 @@ int y_launch_f(og_yolo* h, const YConv& L, int B, const void* in_u8, const YView
     a.tiles_x = (a.W + 15) / 16;
     a.tiles_y = (a.H + 7) / 8;
     a.n_spatial = B * a.tiles_x * a.tiles_y;
-    a.wpk = L.d_wf;
-    a.scale = L.d_scale;
-    a.shift = L.d_shift;
-    a.aff_mod = L.Cout_p;
-    a.out = out.base;
-    a.out_frame_stride = out.fs4();
-    a.out_pix_stride = out.ps4();
-    a.out_ch_off = out.off4();
-    a.zero_page = h->d_zero;
-    a.act = L.act;
-    a.res = res ? res->base : nullptr;
-    a.res_frame_stride = res ? res->fs4() : 0;
-    a.res_pix_stride = res ? res->ps4() : 0;
-    a.res_ch_off = res ? res->off4() : 0;
-    a.head_thr = 0.5f;
     a.range_flag = h->d_range;
-    a.ksplit = 1;
-    a.vsplit = 1;
     const LaunchCtx ctx{h->stream, h->n_cu, 2};
     const int n_ntiles = L.Cout_p / (32 * L.NT);
     if (L.f32out) {
         if (L.kind != 2 || L.act != 0 || res) return fail(OG_ESTATE, "f32 logits come from the plain 1x1 Conv2d layers only: " + L.name);
-        return (L.NT == 2) ? launch_conv_fy<2, 2, true>(ctx, a, n_ntiles) : launch_conv_fy<1, 2, true>(ctx, a, n_ntiles);
+        return og_pick<2, 1>(L.NT, [&](auto nt) { return launch_conv_fy<decltype(nt)::value, 2, true>(ctx, a, n_ntiles); });
     }
-    if (L.kind == 4) return (L.NT == 2) ? launch_conv_fy<2, 3>(ctx, a, n_ntiles) : launch_conv_fy<1, 3>(ctx, a, n_ntiles);
-    if (L.kind == 0) return (L.NT == 2) ? launch_conv_fy<2, 0>(ctx, a, n_ntiles) : launch_conv_fy<1, 0>(ctx, a, n_ntiles);
-    return (L.NT == 2) ? launch_conv_fy<2, 2>(ctx, a, n_ntiles) : launch_conv_fy<1, 2>(ctx, a, n_ntiles);
+    return og_pick<2, 1>(L.NT, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        if (L.kind == 4) return launch_conv_fy<NT, 3>(ctx, a, n_ntiles);
+        if (L.kind == 0) return launch_conv_fy<NT, 0>(ctx, a, n_ntiles);
+        return launch_conv_fy<NT, 2>(ctx, a, n_ntiles);
+    });
 }
 
 int y_launch(og_yolo* h, const std::string& mod, int B, const void* in_u8, const YView& in, const YView& out, const YView* res) {
@@ -460,53 +433,13 @@ int y_launch(og_yolo* h, const std::string& mod, int B, const void* in_u8, const
         plan_inst(px1 ? "k_conv_direct<true, 1> cq_shift=%d" : "k_conv_direct<true, 4> cq_shift=%d", cq_shift);
         return OG_OK;
     }
-    ConvArgs a;
-    a.in = in.base;
-    a.in_frame_stride = in.frame_stride();
-    a.in_pix_stride = in.Ctot;
-    a.in_ch_off = in.off;
+    ConvArgs a = y_conv_args(h, L, L.d_w, in, out, res);
     a.n_chunks = L.Cin_p / 32;
     a.H = in.H;
     a.W = in.W;
     a.tiles_x = (in.W + 15) / 16;
     a.tiles_y = (in.H + 7) / 8;
     a.n_spatial = B * a.tiles_x * a.tiles_y;
-    a.wpk = L.d_w;
-    a.scale = L.d_scale;
-    a.shift = L.d_shift;
-    a.aff_mod = L.Cout_p;
-    a.out = out.base;
-    a.out_frame_stride = out.frame_stride();
-    a.out_pix_stride = out.Ctot;
-    a.out_ch_off = out.off;
-    a.pool = nullptr;
-    a.pool_frame_stride = 0;
-    a.pool_pix_stride = 0;
-    a.pool_ch_off = 0;
-    a.zero_page = h->d_zero;
-    a.act = L.act;
-    a.res = res ? res->base : nullptr;
-    a.res_frame_stride = res ? res->frame_stride() : 0;
-    a.res_pix_stride = res ? res->Ctot : 0;
-    a.res_ch_off = res ? res->off : 0;
-    a.prio_mode = 0;
-    a.first_u8 = nullptr;
-    a.first_w9 = nullptr;
-    a.first_scale = nullptr;
-    a.first_shift = nullptr;
-    a.head_w = nullptr;
-    a.head_bias = 0.f;
-    a.head_thr = 0.5f;
-    a.head_boxes = nullptr;
-    a.head_logits = nullptr;
-    a.head_mask = nullptr;
-    a.head_area = nullptr;
-    a.head_store_act = 0;
-    a.range_flag = nullptr;
-    a.ksplit = 1;
-    a.vsplit = 1;
-    a.partial = nullptr;
-    a.stamps = nullptr;
     const LaunchCtx ctx{h->stream, h->n_cu, 2};
     // THE DETECTOR'S CANONICAL ARITHMETIC (a property of the handle, as the U-Net's is): a conv whose ONE-FRAME launch would leave
     // most of the chip idle sums its K range as `ks` parts, combined in split order -- decided from the layer's shape, the frame
@@ -546,23 +479,23 @@ int y_launch(og_yolo* h, const std::string& mod, int B, const void* in_u8, const
         a.n_spatial = B * a.tiles_x * a.tiles_y;
         a.n_chunks = chunks;
     }
-    if (ks > 1 && !real) {   // virtual split: any B, no workspace
-        a.vsplit = ks;
-        if (L.kind == 4) return (NTu == 2) ? launch_conv_o<2, 3, 8, 3, true>(ctx, a, n_ntiles) : launch_conv_o<1, 3, 8, 3, true>(ctx, a, n_ntiles);
-        if (L.kind == 0) return (NTu == 2) ? launch_conv_o<2, 0, 8, 3, true>(ctx, a, n_ntiles) : launch_conv_o<1, 0, 8, 3, true>(ctx, a, n_ntiles);
-        return (NTu == 2) ? launch_conv_o<2, 2, 8, 3, true>(ctx, a, n_ntiles) : launch_conv_o<1, 2, 8, 3, true>(ctx, a, n_ntiles);
-    }
-    a.ksplit = real ? ks : 1;
-    if (L.kind == 4) return (NTu == 2) ? launch_conv_o<2, 3, 8, 3>(ctx, a, n_ntiles) : launch_conv_o<1, 3, 8, 3>(ctx, a, n_ntiles);
-    if (L.kind == 0) {
-        // launches that fill the chip (3 workgroups per CU) take the occupancy kernel, as in the U-Net chain
-        if (a.ksplit > 1 || a.n_spatial * n_ntiles >= h->n_cu)
-            return (NTu == 2) ? launch_conv_o<2, 0, 8, 3>(ctx, a, n_ntiles) : launch_conv_o<1, 0, 8, 3>(ctx, a, n_ntiles);
-        return (NTu == 2) ? launch_conv_p<2, 0, 8, 1>(ctx, a, n_ntiles) : launch_conv_p<1, 0, 8, 3>(ctx, a, n_ntiles);
-    }
-    if (a.ksplit > 1 || a.n_spatial * n_ntiles >= h->n_cu)   // 1x1 convs: the occupancy kernel's MODE 2 (no halo border, one tap)
-        return (NTu == 2) ? launch_conv_o<2, 2, 8, 3>(ctx, a, n_ntiles) : launch_conv_o<1, 2, 8, 3>(ctx, a, n_ntiles);
-    return (NTu == 2) ? launch_conv_p<2, 2, 8, 1>(ctx, a, n_ntiles) : launch_conv_p<1, 2, 8, 1>(ctx, a, n_ntiles);
+    if (ks > 1 && !real) a.vsplit = ks;   // virtual split: any B, no workspace
+    else a.ksplit = real ? ks : 1;
+    // launches that fill the chip (3 workgroups per CU) take the occupancy kernel, as in the U-Net chain, and so does every split and
+    // every stride-2 conv (MODE 3 exists on that kernel only); the rest run on the persistent one
+    const bool occ = a.ksplit > 1 || a.n_spatial * n_ntiles >= h->n_cu;
+    return og_pick<2, 1>(NTu, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        if (a.vsplit > 1) {
+            if (L.kind == 4) return launch_conv_o<NT, 3, 8, 3, true>(ctx, a, n_ntiles);
+            if (L.kind == 0) return launch_conv_o<NT, 0, 8, 3, true>(ctx, a, n_ntiles);
+            return launch_conv_o<NT, 2, 8, 3, true>(ctx, a, n_ntiles);
+        }
+        if (L.kind == 4) return launch_conv_o<NT, 3, 8, 3>(ctx, a, n_ntiles);
+        if (L.kind == 0) return occ ? launch_conv_o<NT, 0, 8, 3>(ctx, a, n_ntiles) : launch_conv_p<NT, 0, 8, (NT == 2) ? 1 : 3>(ctx, a, n_ntiles);
+        // 1x1 convs: the occupancy kernel's MODE 2 (no halo border, one tap)
+        return occ ? launch_conv_o<NT, 2, 8, 3>(ctx, a, n_ntiles) : launch_conv_p<NT, 2, 8, 1>(ctx, a, n_ntiles);
+    });
 }
 
 // Channel width of a Conv module's output from its weight shape.
@@ -1000,10 +933,6 @@ int og_yolo_finalize(og_yolo* h) {
         return OG_OK;
     }
     if ((rc = init_kernel_attrs())) return rc;
-    if ((rc = set_conv_fy_attr<1, 0, false>()) || (rc = set_conv_fy_attr<2, 0, false>()) || (rc = set_conv_fy_attr<1, 2, false>()) ||
-        (rc = set_conv_fy_attr<2, 2, false>()) || (rc = set_conv_fy_attr<1, 2, true>()) || (rc = set_conv_fy_attr<2, 2, true>()) ||
-        (rc = set_conv_fy_attr<1, 3, false>()) || (rc = set_conv_fy_attr<2, 3, false>()))
-        return rc;
     {
         int dev = 0;
         hipDeviceProp_t prop;

@@ -773,48 +773,29 @@ ConvArgs conv_args(const ConvView& in, const ConvView& out, const ConvView& pool
     return a;
 }
 
-// grid.z of every kernel that decodes blockIdx.z with ConvArgs::zdiv / zrcp / zgroup_shift: (frame group, column tile x K part, frame
-// in group).  `zdiv` = column tiles (x K parts) per spatial tile, `grid_tiles` = the GRID's tiles per frame (k_conv_wino_w<2> has half
-// as many rows as a.tiles_y counts).  With "xcd_group" the frames are interleaved in groups of G = 8 / gcd(8, grid_tiles) so that
-// the column tiles of one spatial tile land on one XCD (8 XCDs, blocks dealt round-robin).  `wgs` > 0: the ungrouped forms, `wgs`
-// workgroups per (frame, column tile) -- k_conv_wino_ps's 16 / PN, k_conv_wino_wp's 4, k_convt_w's 1.
+// grid.z of every kernel that decodes blockIdx.z with og_zdecode: the layout is og_zlayout's (og_kernels.hpp, next to its inverse).
+// `zdiv` = column tiles (x K parts) per spatial tile, `grid_tiles` = the GRID's tiles per frame (k_conv_wino_w<2> has half as many
+// rows as a.tiles_y counts).  `wgs` > 0: the ungrouped forms, `wgs` workgroups per (frame, column tile) -- k_conv_wino_ps's 16 / PN,
+// k_conv_wino_wp's 4, k_convt_w's 1.
 // Sets a.frames, a.zdiv, a.zgroup_shift, a.zrcp; returns grid.z, or OG_EINVAL when it would pass the hardware's 65535.
 int grid_z(const LaunchCtx& c, ConvArgs& a, int zdiv, int grid_tiles, int wgs = 0) {
-    const int frames = a.n_spatial / (a.tiles_x * a.tiles_y);
     a.zdiv = zdiv;
-    a.frames = frames;
-    a.zgroup_shift = 0;
-    if (wgs == 0 && c.xcd_group && zdiv > 1) {
-        int txy = grid_tiles, g = 8;
-        while (g > 1 && txy % 2 == 0) { txy /= 2; g /= 2; }   // g = 8 / gcd(8, tiles per frame)
-        while (g > frames) g /= 2;
-        while ((1 << a.zgroup_shift) < g) ++a.zgroup_shift;
-    }
-    const int G = 1 << a.zgroup_shift, groups = (frames + G - 1) / G;
-    a.zrcp = 1.0f / (float)(zdiv * G);
-    const long long gz = (long long)groups * G * zdiv * (wgs ? wgs : 1);
-    if (gz > 65535) return fail(OG_EINVAL, "micro-batch too large for one launch (grid.z): lower the chunk size");
-    return (int)gz;
+    a.frames = a.n_spatial / (a.tiles_x * a.tiles_y);
+    const og_zlay l = og_zlayout(a.frames, zdiv, grid_tiles, c.xcd_group, wgs);
+    a.zgroup_shift = l.zgroup_shift;
+    a.zrcp = l.zrcp;
+    if (l.gz > 65535) return fail(OG_EINVAL, "micro-batch too large for one launch (grid.z): lower the chunk size");
+    return (int)l.gz;
 }
 
-// LDS of k_conv_mfma: two halo buffers + two weight stages
-template <int NT, int MODE, int TH>
-constexpr int conv_t_lds() {
-    return 2 * (16 + 2 * ((MODE == 0) ? 1 : 0)) * (TH + 2 * ((MODE == 0) ? 1 : 0)) * 128 + 2 * 32 * NT * 128;
-}
-
+// Every launcher below takes its dynamic LDS size from the ConvTile its kernel takes its geometry from.
 template <int NT, int MODE, int TH>
 int launch_conv_t(const LaunchCtx& c, const ConvArgs& a, int n_ntiles) {
-    constexpr int lds = conv_t_lds<NT, MODE, TH>();
+    constexpr int lds = ConvTile<NT, MODE, TH>::lds_bytes_2x(1);
     ProfScope ps(c, "k_conv_mfma<%d,%d,%d>", NT, MODE, TH);
     OG_LAUNCH_LDS((k_conv_mfma<NT, MODE, TH>), dim3((unsigned)(a.n_spatial * n_ntiles)), dim3(256), lds, c.stream, a);
     plan_inst("k_conv_mfma<%d, %d, %d>", NT, MODE, TH);
     return OG_OK;
-}
-
-template <int NT, int MODE, int TH, int TPS>
-constexpr int conv_p_lds() {
-    return 2 * (16 + 2 * ((MODE == 0) ? 1 : 0)) * (TH + 2 * ((MODE == 0) ? 1 : 0)) * 128 + 2 * TPS * 32 * NT * 128;
 }
 
 // Split-K factor for a launch of `n_items` tiles over `n_chunks` 32-channel chunks: only when the
@@ -829,20 +810,10 @@ inline int pick_ksplit(int n_items, int n_chunks, int slots, int ms, bool enable
     return k < 1 ? 1 : k;
 }
 
-// LDS of k_conv_mfma_o: one halo buffer + the weight ring (3 stages for the 3x3 conv, 2 otherwise)
-template <int NT, int MODE, int TH>
-constexpr int conv_o_lds() {
-    return ((MODE == 3) ? 18 * (TH + 1) : (16 + 2 * ((MODE == 0) ? 1 : 0)) * (TH + 2 * ((MODE == 0) ? 1 : 0))) * 128 +
-           ((MODE == 0) ? 3 : 2) * 32 * NT * 128;
-}
-// ... and what the FIRST variants (the first layer computed inside downs.0's second conv) add to it: the 12 x 20 pixels of the u8
-// frame under a tile's halo, and the first layer's 9 x 32 weights, scale and shift
-constexpr int kFirstLds = (12 * 20 + 352) * 4;
-
 template <int NT, int MODE, int TH, int OCC, bool VS = false>
 int launch_conv_o(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {
-    constexpr int lds = conv_o_lds<NT, MODE, TH>();
-    static_assert(lds >= 4 * 5120, "the epilogue's per-wave scratch needs 20 KB");
+    constexpr int lds = ConvTile<NT, MODE, TH>::lds_bytes;
+    static_assert(lds <= 160 * 1024, "one workgroup of this tile must fit a CU's LDS");
     ConvArgs a = a_in;
     a.stamps = nullptr;  // the probe buffer is sized for the persistent kernel's grid; this kernel's timeline is tools/ubench/occ_timeline
     if (VS) a.ksplit = 1;
@@ -957,7 +928,8 @@ int launch_convt_w(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {
 
 template <int NT, int MODE, int TH, int OCC, bool SQ = false>
 int launch_conv_h(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {   // split-precision twin of launch_conv_o
-    constexpr int lds = conv_o_lds<NT, MODE, TH>();
+    constexpr int lds = ConvTile<NT, MODE, TH, SQ>::lds_bytes;
+    static_assert(lds <= 160 * 1024, "one workgroup of this tile must fit a CU's LDS");
     ConvArgs a = a_in;
     a.stamps = nullptr;
     if (SQ || a.tile_counter == nullptr || a.partial == nullptr || a.n_spatial * n_ntiles > kTileCounters) a.ksplit = 1;   // fused reduce only
@@ -971,7 +943,8 @@ int launch_conv_h(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {   //
 
 template <int NT, int MODE, int TH, int OCC, bool SQ = false>
 int launch_conv_f(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {   // f16-mode twin of launch_conv_h (never splits K)
-    constexpr int lds = conv_o_lds<NT, MODE, TH>();
+    constexpr int lds = ConvTile<NT, MODE, TH, SQ>::lds_bytes;
+    static_assert(lds <= 160 * 1024, "one workgroup of this tile must fit a CU's LDS");
     ConvArgs a = a_in;
     a.stamps = nullptr;
     a.ksplit = 1;
@@ -993,7 +966,7 @@ int launch_conv_hf(const LaunchCtx& c, const ConvArgs& a, int n_ntiles, bool f16
 
 template <int NT, int MODE, int TH, int TPS>
 int launch_conv_p(const LaunchCtx& c, const ConvArgs& a, int n_ntiles) {
-    constexpr int lds = conv_p_lds<NT, MODE, TH, TPS>();
+    constexpr int lds = ConvTile<NT, MODE, TH>::lds_bytes_2x(TPS);
     const int n_items = a.n_spatial * n_ntiles * a.ksplit;
     const int slots = c.n_cu * ((lds > 80 * 1024) ? 1 : c.wg_per_cu);
     const int rounds = (n_items + slots - 1) / slots;
@@ -1290,7 +1263,9 @@ int enqueue_first_fused(og_unet* h, const uint8_t* gray, int B, int H, int W) {
     a.first_scale = h->d_first_scale;
     a.first_shift = h->d_first_shift;
     if (h->precision != 0) a.prio_mode = h->prio_mode;
-    constexpr int lds = conv_o_lds<1, 0, 8>() + kFirstLds;
+    using T = ConvTile<1, 0, 8>;   // of all three FIRST kernels below
+    constexpr int lds = T::lds_bytes + T::first_bytes;
+    static_assert(3 * lds <= 160 * 1024, "three workgroups of the fused first layer per CU");
     ProfScope ps(h, "downs.0 (first + second conv fused)", h->precision == 2 ? "k_conv_mfma_f<1,0,8,FIRST>" : h->precision == 1 ? "k_conv_mfma_h<1,0,8,FIRST>" : "k_conv_mfma_o<1,0,8,FIRST>",
                  2.0 * B * H * W * 9.0 * (1.0 * h->features[0] + (double)h->features[0] * h->features[0]));
     const int gz = grid_z(LaunchCtx{h->stream, h->n_cu, h->wg_per_cu, h->xcd_group}, a, 1, a.tiles_x * a.tiles_y);   // one column tile: grid.z = B

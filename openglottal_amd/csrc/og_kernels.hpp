@@ -243,6 +243,227 @@ struct ConvArgs {
     int k_half;             // k_conv_mfma_f only: n_chunks counts 64-channel chunks and the last one holds 32 channels
 };
 
+// ---- grid.z: the layout (host) and its inverse (device), side by side ----
+// grid.z = frame group q x (column tile x K part) zr x frame-in-group, G = 2^zgroup_shift frames per group: the column tiles of one
+// spatial tile then sit G * grid_tiles (a multiple of 8) blocks apart = on the same XCD, dispatched together, and share the input
+// tile in that XCD's L2.  G = 8 / gcd(8, grid_tiles), capped by `frames`; 1 without `xcd_group`, for a single column tile, and for
+// the forms with `wgs` > 0 workgroups per (frame, column tile), which peel their workgroup index off blockIdx.z themselves.
+// `gz` is the grid's z extent; the caller refuses a launch whose gz passes the hardware's 65535.
+struct og_zlay {
+    int zgroup_shift;
+    float zrcp;      // 1 / (zdiv << zgroup_shift)
+    long long gz;
+};
+inline og_zlay og_zlayout(int frames, int zdiv, int grid_tiles, bool xcd_group, int wgs) {
+    og_zlay l{0, 0.f, 0};
+    if (wgs == 0 && xcd_group && zdiv > 1) {
+        int txy = grid_tiles, g = 8;
+        while (g > 1 && txy % 2 == 0) { txy /= 2; g /= 2; }   // g = 8 / gcd(8, tiles per frame)
+        while (g > frames) g /= 2;
+        while ((1 << l.zgroup_shift) < g) ++l.zgroup_shift;
+    }
+    const int G = 1 << l.zgroup_shift, groups = (frames + G - 1) / G;
+    l.zrcp = 1.0f / (float)(zdiv * G);
+    l.gz = (long long)groups * G * zdiv * (wgs ? wgs : 1);
+    return l;
+}
+// The inverse: bz (blockIdx.z, less the workgroup index of the `wgs` forms) -> zr = column tile x K parts + K part, b = frame.
+// No integer division (each one is ~20 vector-ALU instructions, paid at the contended issue rate on the way to the first DMA):
+// the quotient by gz = zdiv << zgroup_shift is taken as (bz + 0.5) * zrcp, exact for every gz and bz < 65535 = every grid.z the
+// hardware takes (tests/test_zdecode.py sweeps all of them).  b >= a.frames in the tail of the last frame group: the caller
+// returns there, whole workgroup, before any barrier.
+// GROUPED = false: for a kernel that is only ever laid out with `wgs` > 0, i.e. with zgroup_shift 0 -- the same decode without the
+// shifts (k_conv_wino_wp: five scalar instructions in front of the first DMA of a kernel that runs several times per one-frame
+// chain; with them latency_mode.one_lane measured 0.11-0.17 % lower, profiles/r10_headline_ab.txt).
+template <bool GROUPED = true>
+__host__ __device__ __forceinline__ void og_zdecode(const ConvArgs& a, int bz, int& zr, int& b) {
+    const int sh = GROUPED ? a.zgroup_shift : 0;
+    const int gz = a.zdiv << sh;
+    const int q = (gz == 1) ? bz : (int)(((float)bz + 0.5f) * a.zrcp);
+    const int rz = bz - q * gz;
+    zr = rz >> sh;
+    b = (q << sh) + (rz & ((1 << sh) - 1));
+}
+// linear workgroup index of a 3-D grid (diagnostic stamps)
+__device__ __forceinline__ unsigned og_wg_index() { return ((unsigned)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x; }
+
+// ---- tile geometry of the implicit-GEMM conv family, for host and device: the kernels take their constants from it and the
+//      launchers their LDS size, so a halo shape cannot change on one side only ----
+// MODE / NT / TH as described at k_conv_mfma below.  SQ (k_conv_mfma_h / _f): square wave tiles, 2 row sub-tiles x both column sub-tiles.
+template <int NT_, int MODE_, int TH_, bool SQ_ = false>
+struct ConvTile {
+    static constexpr int NT = NT_, MODE = MODE_, TH = TH_;
+    static constexpr int TW = 16;
+    static constexpr int PAD = (MODE == 0 || MODE == 3) ? 1 : 0;   // rows / columns of halo above / left of the tile
+    static constexpr int HW_ = (MODE == 3) ? TW + 2 : TW + 2 * PAD;   // MODE 3 needs 17 columns; an even pitch keeps
+    static constexpr int HH_ = (MODE == 3) ? TH + 1 : TH + 2 * PAD;   // the slot swizzle conflict-free
+    static constexpr int HALO_PIX = HW_ * HH_;
+    static constexpr int HALO_BYTES = HALO_PIX * 128;
+    static constexpr int HALO_PIECES = HALO_PIX * 8;
+    static constexpr int HALO_IT = (HALO_PIECES + 255) / 256;
+    static constexpr int TAPS = (MODE == 0) ? 9 : (MODE == 3) ? 4 : 1;
+    static constexpr int NDX = (MODE == 0) ? 3 : (MODE == 3) ? 2 : 1;   // distinct tap columns
+    static constexpr int WROWS = 32 * NT;
+    static constexpr int WBYTES = WROWS * 128;   // one tap slice
+    // weight ring: 3 stages for the 3x3 conv, so that a tap's stage (t % 3, nine taps per chunk) is a compile-time
+    // constant and the B-fragment reads need no address arithmetic; 2 stages (runtime parity) elsewhere
+    static constexpr int NSTG = (MODE == 0) ? 3 : 2;
+    // the f16-operand kernels stage weight slices TWO steps ahead in the 3-stage ring: a step is ~5x shorter than in the f32 kernel
+    // (24 MFMAs of 32 cycles per wave at most), less than the latency of the LDS-DMA that has to land before the next step
+    static constexpr int WAHEAD = (NSTG == 3) ? 2 : 1;
+    static constexpr int WM = SQ_ ? 4 : 4 / NT;   // waves along M
+    static constexpr int NC = SQ_ ? 2 : 1;        // 32-column sub-tiles per wave
+    static constexpr int MS = (TH / 2) / WM;      // 32-row M sub-tiles (2 pixel rows x 16) per wave
+    static_assert(MS >= 1, "tile too small");
+    // k_conv_mfma_o / _h / _f / _fy: ONE halo buffer + the weight ring
+    static constexpr int lds_bytes = HALO_BYTES + NSTG * WBYTES;
+    // ... and what their FIRST variants (the first layer computed inside downs.0's second conv) add behind it: the pixels of the u8
+    // frame under a tile's halo, and the first layer's 9 x 32 weights, 32 scales and 32 shifts
+    static constexpr int FIRST_PATCH = (HH_ + 2) * (HW_ + 2), FIRST_W = 9 * 32 + 32 + 32;
+    static constexpr int first_bytes = (FIRST_PATCH + FIRST_W) * 4;
+    // k_conv_mfma (TPS 1) / k_conv_mfma_p: two halo buffers + two weight stages of TPS tap slices
+    static constexpr int lds_bytes_2x(int tps) { return 2 * HALO_BYTES + 2 * tps * WBYTES; }
+    static constexpr int SCRATCH = 4 * 5120;   // the epilogues' per-wave scratch (4 KB tile + 1 KB pooled tile), over the dead staging buffers
+};
+
+// 16-B slot swizzle of the halo image in k_conv_mfma_o: with the 2x2-window-major lane -> pixel order, each
+// 16-lane group of a ds_read_b128 ({0-3,12-15,20-27}, ...) touches 8 pixels of an even and 8 of an odd row; the
+// column pair index XOR 4x the row parity gives the 16 lanes 16 distinct (128-B half, slot) places -> conflict-free
+// (the linear-pixel swizzle (p >> 1) & 7 used by the other variants is 2-way conflicted on these reads).
+__device__ __forceinline__ int og_halo_swz(int py, int px) { return ((px >> 1) ^ ((py & 1) << 2)) & 7; }
+
+// ---- set-up shared by k_conv_mfma_o / _h / _f / _fy (T = the kernel's ConvTile) ----
+// LDS-DMA staging of one workgroup: the halo image of a tile (one 32-channel / 64-channel-f16 chunk at a time) and the weight ring.
+// HALF (the f16-operand kernels): a lone half chunk fetches only the 64 live bytes per pixel, the other lanes carry OG_OOB.
+template <class T, bool HALF = false>
+struct ConvStage {
+    og_i32x4 in_rsrc, w_rsrc;
+    unsigned hoff[T::HALO_IT];   // per-thread halo source offsets (bytes, fixed across channel chunks)
+    unsigned woff, lds0;
+    int wave;                    // a wave stages 1 KB of every 4 KB round
+    bool last_valid;
+
+    // this frame's input as a raw buffer: offsets past num_records read as zeros (= the conv's zero padding)
+    __device__ __forceinline__ void init_halo(const ConvArgs& a, unsigned lds0_, int tid, int wave_, int b, int ty0, int tx0, int cpp = 0) {
+        in_rsrc = og_make_rsrc(a.in + (long long)b * a.in_frame_stride + a.in_ch_off, (unsigned)(a.in_frame_stride - a.in_ch_off) * 4u);
+        constexpr int HW_ = T::HW_;
+        const bool only_half = (a.k_half != 0 && cpp == 1);   // HALF: cpp = 64-channel chunks per pixel; the last one holds 32 channels when a.k_half
+        constexpr bool S2 = (T::MODE == 3);   // (gy, gx) is a 2x2 input block = the output pixel grid; the block's (0,0) pixel is the base
+        int hy = ((tid >> 3) >= HW_) ? 1 : 0;   // the pixel index walks incrementally
+        int hx = (tid >> 3) - hy * HW_;
+        const int in_w = S2 ? 2 * a.W : a.W;
+        const int row_b = in_w * a.in_pix_stride * (S2 ? 8 : 4);   // bytes per halo row step
+        const int col_b = a.in_pix_stride * (S2 ? 8 : 4);          // bytes per halo column step
+#pragma unroll
+        for (int it = 0; it < T::HALO_IT; ++it) {
+            const int logical = (tid & 7) ^ og_halo_swz(hy, hx);
+            const int gy = ty0 + hy - T::PAD, gx = tx0 + hx - T::PAD;
+            const bool inb = (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W && !(HALF && only_half && logical >= 4);
+            hoff[it] = inb ? (unsigned)(gy * row_b + gx * col_b + logical * 16) : OG_OOB;
+            hx += 32 % HW_;
+            hy += 32 / HW_;
+            if (hx >= HW_) { hx -= HW_; hy += 1; }
+        }
+        last_valid = ((T::HALO_IT - 1) * 256 + tid) < T::HALO_PIECES;
+        lds0 = lds0_;
+        wave = wave_;
+    }
+    // this column tile's `n_steps` weight slices as a raw buffer
+    __device__ __forceinline__ void init_w(const ConvArgs& a, int tid, int n_tile, int n_steps) {
+        w_rsrc = og_make_rsrc(a.wpk + (long long)n_tile * n_steps * (T::WROWS * 32), (unsigned)n_steps * T::WBYTES);
+        woff = (unsigned)tid * 16u;
+    }
+    // soff = wave-uniform byte offset of the chunk within a pixel (and of the input-pixel parity, MODE 3)
+    __device__ __forceinline__ void halo(unsigned soff) const {
+        const unsigned base = lds0 + wave * 1024;
+#pragma unroll
+        for (int it = 0; it < T::HALO_IT; ++it) {
+            if (it < T::HALO_IT - 1 || last_valid) glds16b(hoff[it], in_rsrc, soff, base + it * 4096);
+        }
+    }
+    __device__ __forceinline__ void w(int stage, int step) const {
+        const unsigned base = lds0 + T::HALO_BYTES + stage * T::WBYTES + wave * 1024;
+#pragma unroll
+        for (int i = 0; i < T::NT; ++i) glds16b(woff, w_rsrc, (unsigned)step * T::WBYTES + i * 4096, base + i * 4096);
+    }
+};
+
+// Fragment addressing.  A rows: i -> 2x2-window-major pixel order, so that the 4 accumulator registers (reg&3) of one lane are
+// exactly one pooling window (see the epilogues).  Everything lane-dependent of an A-fragment address sits in NDX x 4 registers:
+//   abase[dx][pat] = ((pyl*HW_ + px0+dx) * 128 + ((lh ^ swz(pyl, px0+dx)) << 4) + wave row offset) ^ (pat << 5)
+// and a tap's dy, the k-group j and the M sub-tile m only select pat = j ^ ((dy & 1) << 1) (row parity flips slot
+// bit 2) and add the compile-time constant (dy + 2m) * HW_ * 128, which the ds_read carries as its immediate.
+// bbase[j]: B fragments, stage 0 of the weight ring, k-group j (slot = (2j + lh) ^ swz == ((lh ^ swz) << 4) ^ (j << 5) in bytes).
+template <class T>
+__device__ __forceinline__ void og_frag_bases(unsigned lds0, int li, int lh, int wm, int wn, unsigned (&abase)[T::NDX][4], unsigned (&bbase)[4]) {
+    const int px0 = 2 * (li >> 2) + (li & 1);
+    const int pyl = (li >> 1) & 1;
+    const int brow = wn * 32 + li;
+    const int boff = brow * 128 + ((lh ^ ((brow >> 1) & 7)) << 4);
+#pragma unroll
+    for (int dx = 0; dx < T::NDX; ++dx) {
+        const int px = px0 + dx;
+        const unsigned o = (unsigned)((pyl * T::HW_ + px) * 128 + ((lh ^ og_halo_swz(pyl, px)) << 4) + wm * (T::MS * 2 * T::HW_ * 128));
+#pragma unroll
+        for (int pat = 0; pat < 4; ++pat) {
+            abase[dx][pat] = lds0 + (o ^ (unsigned)(pat << 5));   // absolute LDS address
+            asm volatile("" : "+v"(abase[dx][pat]));              // opaque: or hipcc re-adds the (link-time 0) smem base per read
+        }
+    }
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+        bbase[jj] = lds0 + T::HALO_BYTES + (unsigned)(boff ^ (jj << 5));
+        asm volatile("" : "+v"(bbase[jj]));
+    }
+}
+
+// this lane's output channel in column sub-tile wn: folded BN scale / shift, loaded during set-up so that the epilogue does not wait for them
+template <class T>
+__device__ __forceinline__ void og_load_affine(const ConvArgs& a, int n_tile, int wn, int li, float& esc, float& esh) {
+    const int ecol = n_tile * T::WROWS + wn * 32 + li;
+    const int eco = (T::MODE == 1) ? ecol % a.aff_mod : ecol;
+    esc = a.scale[eco];
+    esh = a.shift[eco];
+}
+
+// FIRST variants: the u8 patch under the tile's halo (/255, zero outside the frame) and the first layer's w9[9][32] | scale[32] |
+// shift[32] into LDS behind the weight ring.  Returns the patch [HH_+2][HW_+2]; the weights follow it.  The caller's barrier publishes both.
+template <class T>
+__device__ __forceinline__ float* og_first_load(const ConvArgs& a, unsigned char* smem, int tid, int b, int ty0, int tx0) {
+    float* patch = (float*)(smem + T::lds_bytes);
+    float* fw = patch + T::FIRST_PATCH;
+    const uint8_t* fin = a.first_u8 + (long long)b * a.H * a.W;
+    for (int i = tid; i < T::FIRST_PATCH; i += 256) {
+        const int hy = i / (T::HW_ + 2), hx = i - hy * (T::HW_ + 2);
+        const int gy = ty0 + hy - 2, gx = tx0 + hx - 2;
+        patch[i] = (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) ? (float)fin[(long long)gy * a.W + gx] / 255.0f : 0.f;
+    }
+    for (int i = tid; i < T::FIRST_W; i += 256) fw[i] = (i < 288) ? a.first_w9[i] : (i < 320 ? a.first_scale[i - 288] : a.first_shift[i - 320]);
+    return patch;
+}
+
+// ---- fused split-K reduce (k_conv_mfma_h; k_conv_mfma_o keeps its own text of the same steps: with these helpers the wait
+// sequence of its MODE 2 instantiations changes, profiles/r10_isa_diff.txt): the LAST part of a tile to arrive sums all parts in split order (its own from
+// memory too, so the result does not depend on who is last) and runs the epilogue -- one launch less per split layer.  A part = the
+// raw accumulators in register order, lane-contiguous (256-B stores).  Device-scope release/acquire around the arrival counter:
+// the parts come from other XCDs' L2s.  (The sum stays in the kernel: _o fetches PG parts at a time, _h one.) ----
+template <int MS>
+__device__ __forceinline__ void og_splitk_put(float* pw, const f32x16* acc) {
+    // device-scope (write-through) stores: visible to the other XCDs once acknowledged, without flushing an L2
+#pragma unroll
+    for (int m = 0; m < MS; ++m)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) __hip_atomic_store(pw + (m * 16 + r) * 64, acc[m][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// true in the workgroup that arrived last at `counter` (all of its threads); `flag` = one LDS word, dead staging space
+__device__ __forceinline__ bool og_splitk_arrive(int* counter, int ks_n, int* flag, int tid) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's part is written through
+    __syncthreads();
+    if (tid == 0) *flag = (atomicAdd(counter, 1) == ks_n - 1) ? 1 : 0;
+    __syncthreads();
+    return *(volatile int*)flag != 0;
+}
+
 // MODE 0: 3x3 conv, pad 1, stride 1  (+ per-channel affine, ReLU, optional 2x2 max-pool)
 // MODE 1: 2x2 stride-2 transposed conv as one GEMM with N = 4*Cout (dy,dx,co), scattered store
 // MODE 2: 1x1 conv (detector): no halo border, one tap, plain epilogue
@@ -252,20 +473,9 @@ struct ConvArgs {
 // TH    : tile height in pixels (tile is TH x 16)
 template <int NT, int MODE, int TH>
 __global__ __launch_bounds__(256, 2) void k_conv_mfma(ConvArgs a) {
-    constexpr int TW = 16;
-    constexpr int PAD = (MODE == 0) ? 1 : 0;
-    constexpr int HW_ = TW + 2 * PAD;
-    constexpr int HH_ = TH + 2 * PAD;
-    constexpr int HALO_PIX = HW_ * HH_;
-    constexpr int HALO_BYTES = HALO_PIX * 128;
-    constexpr int HALO_PIECES = HALO_PIX * 8;
-    constexpr int HALO_IT = (HALO_PIECES + 255) / 256;
-    constexpr int TAPS = (MODE == 0) ? 9 : 1;
-    constexpr int WROWS = 32 * NT;
-    constexpr int WBYTES = WROWS * 128;
-    constexpr int WM = 4 / NT;
-    constexpr int MS = (TH / 2) / WM;  // 32-row M sub-tiles (2 pixel rows x 16) per wave
-    static_assert(MS >= 1, "tile too small");
+    using T = ConvTile<NT, MODE, TH>;
+    constexpr int TW = T::TW, PAD = T::PAD, HW_ = T::HW_, HALO_BYTES = T::HALO_BYTES, HALO_PIECES = T::HALO_PIECES, HALO_IT = T::HALO_IT;
+    constexpr int TAPS = T::TAPS, WROWS = T::WROWS, WBYTES = T::WBYTES, MS = T::MS;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const halo0 = smem;
@@ -760,12 +970,6 @@ __global__ __launch_bounds__(256) void k_sum_counts(const int32_t* __restrict__ 
     if (threadIdx.x == 0) area[b] = s[0];
 }
 
-// 16-B slot swizzle of the halo image in k_conv_mfma_o: with the 2x2-window-major lane -> pixel order, each
-// 16-lane group of a ds_read_b128 ({0-3,12-15,20-27}, ...) touches 8 pixels of an even and 8 of an odd row; the
-// column pair index XOR 4x the row parity gives the 16 lanes 16 distinct (128-B half, slot) places -> conflict-free
-// (the linear-pixel swizzle (p >> 1) & 7 used by the other variants is 2-way conflicted on these reads).
-__device__ __forceinline__ int og_halo_swz(int py, int px) { return ((px >> 1) ^ ((py & 1) << 2)) & 7; }
-
 // Occupancy variant: ONE halo buffer (reloaded at each chunk boundary, the stall is covered by the
 // other workgroups) -> 39 KB of LDS, so 3-4 workgroups fit a CU instead of 2.  Same arithmetic and
 // accumulation order as k_conv_mfma.
@@ -776,27 +980,14 @@ __device__ __forceinline__ int og_halo_swz(int py, int px) { return ((px >> 1) ^
 // latency path) or not (batched path).
 template <int NT, int MODE, int TH, int OCC, bool FIRST = false, bool VS = false>
 __global__ __launch_bounds__(256, OCC) void k_conv_mfma_o(ConvArgs a) {
-    constexpr int TW = 16;
-    constexpr int PAD = (MODE == 0 || MODE == 3) ? 1 : 0;                 // rows/columns of halo above / left of the tile
-    constexpr int HW_ = (MODE == 3) ? TW + 2 : TW + 2 * PAD;             // MODE 3 needs 17 columns; an even pitch keeps
-    constexpr int HH_ = (MODE == 3) ? TH + 1 : TH + 2 * PAD;             // the slot swizzle conflict-free
-    constexpr int HALO_PIX = HW_ * HH_;
-    constexpr int HALO_BYTES = HALO_PIX * 128;
-    constexpr int HALO_PIECES = HALO_PIX * 8;
-    constexpr int HALO_IT = (HALO_PIECES + 255) / 256;
-    constexpr int TAPS = (MODE == 0) ? 9 : (MODE == 3) ? 4 : 1;
-    constexpr int WROWS = 32 * NT;
-    constexpr int WBYTES = WROWS * 128;
-    // weight ring: 3 stages for the 3x3 conv, so that a tap's stage (t % 3, nine taps per chunk) is a compile-time
-    // constant and the B-fragment reads need no address arithmetic; 2 stages (runtime parity) elsewhere
-    constexpr int NSTG = (MODE == 0) ? 3 : 2;
-    constexpr int WM = 4 / NT;
-    constexpr int MS = (TH / 2) / WM;  // 32-row M sub-tiles (2 pixel rows x 16) per wave
-    static_assert(MS >= 1, "tile too small");
+    using T = ConvTile<NT, MODE, TH>;
+    constexpr int TW = T::TW, HW_ = T::HW_, HALO_BYTES = T::HALO_BYTES, HALO_PIECES = T::HALO_PIECES, HALO_IT = T::HALO_IT, TAPS = T::TAPS;
+    constexpr int WROWS = T::WROWS, WBYTES = T::WBYTES, NSTG = T::NSTG, MS = T::MS;
+    static_assert(T::SCRATCH <= T::lds_bytes, "the epilogue's per-wave scratch lies over the staging buffers");
+    static_assert(!FIRST || T::lds_bytes + T::first_bytes <= 160 * 1024, "the FIRST patch and weights follow the weight ring");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const halo0 = smem;
-    unsigned char* const wbuf0 = smem + HALO_BYTES;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -812,7 +1003,7 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_o(ConvArgs a) {
     // set-up, the DMA issue and the epilogue are served first; the main loops only need a slot every 64 cycles.
     if (a.prio_mode == 3) __builtin_amdgcn_s_setprio(3);
     // diagnostic timeline (tools/ubench/occ_timeline.hip only; nullptr on every product path)
-    unsigned long long* const st = a.stamps ? a.stamps + 8ull * (((unsigned long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) : nullptr;
+    unsigned long long* const st = a.stamps ? a.stamps + 8ull * og_wg_index() : nullptr;
     if (st != nullptr && tid == 0) {
         st[0] = __builtin_amdgcn_s_memtime();
         st[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);  // HW_REG_HW_ID: wave slot, SIMD, CU, SE
@@ -823,15 +1014,8 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_o(ConvArgs a) {
     //      on the way to the first DMA (each one is ~20 vector-ALU instructions, paid at the contended issue rate).
     //      split-K (latency mode, MODE 0/1): K part = a range of (chunk, tap) steps ----
     const int ks_n = a.ksplit;
-    // grid.z = frame group q x (column tile, K part) x frame-in-group: the column tiles of one spatial tile then sit
-    // G * tiles_x * tiles_y (a multiple of 8) blocks apart = on the same XCD, dispatched together, and share the input
-    // tile in that XCD's L2 (G = 2^zgroup_shift frames per group; 1 when tiles_x * tiles_y is already a multiple of 8)
-    const int bz = (int)blockIdx.z;
-    const int gz = a.zdiv << a.zgroup_shift;
-    const int q = (gz == 1) ? bz : (int)(((float)bz + 0.5f) * a.zrcp);   // zrcp = 1 / gz; exact for bz < 2^16
-    const int rz = bz - q * gz;
-    const int zr = rz >> a.zgroup_shift;                                   // column tile x K parts + K part
-    const int b = (q << a.zgroup_shift) + (rz & ((1 << a.zgroup_shift) - 1));
+    int zr, b;   // column tile x K parts + K part, frame
+    og_zdecode(a, (int)blockIdx.z, zr, b);
     if (b >= a.frames) return;   // tail of the last frame group (whole workgroup, before any barrier)
     const int n_tile = (ks_n == 1) ? zr : zr / ks_n;
     const int kpart = (ks_n == 1) ? 0 : zr - n_tile * ks_n;
@@ -862,76 +1046,37 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_o(ConvArgs a) {
     const int tile_id = n_tile * a.n_spatial + (b * a.tiles_y + (int)blockIdx.y) * a.tiles_x + (int)blockIdx.x;
     const int item_id = tile_id * ks_n + kpart;
 
-    // this frame's input as a raw buffer: offsets past num_records read as zeros (= the conv's zero padding)
-    const og_i32x4 in_rsrc = og_make_rsrc(a.in + (long long)b * a.in_frame_stride + a.in_ch_off,
-                                          (unsigned)(a.in_frame_stride - a.in_ch_off) * 4u);
-
-    // ---- per-thread halo source offsets (bytes, fixed across channel chunks); pixel index walks incrementally ----
-    unsigned hoff[HALO_IT];
-    {
-        int hy = ((tid >> 3) >= HW_) ? 1 : 0;
-        int hx = (tid >> 3) - hy * HW_;
-        const int in_w = (MODE == 3) ? 2 * a.W : a.W;
-        const int row_b = in_w * a.in_pix_stride * ((MODE == 3) ? 8 : 4);   // bytes per halo row step
-        const int col_b = a.in_pix_stride * ((MODE == 3) ? 8 : 4);          // bytes per halo column step
-#pragma unroll
-        for (int it = 0; it < HALO_IT; ++it) {
-            const int logical = (tid & 7) ^ og_halo_swz(hy, hx);
-            const int gy = ty0 + hy - PAD, gx = tx0 + hx - PAD;
-            // MODE 3: (gy, gx) is a 2x2 input block = the output pixel grid; the block's (0,0) pixel is the base
-            const bool inb = (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
-            hoff[it] = inb ? (unsigned)(gy * row_b + gx * col_b + logical * 16) : OG_OOB;
-            hx += 32 % HW_;
-            hy += 32 / HW_;
-            if (hx >= HW_) { hx -= HW_; hy += 1; }
-        }
-    }
-    const bool last_valid = ((HALO_IT - 1) * 256 + tid) < HALO_PIECES;
-
     const unsigned lds0 = og_lds_addr(smem);
+    ConvStage<T> stg_;
+    stg_.init_halo(a, lds0, tid, wave, b, ty0, tx0);
     // MODE 3 (3x3 stride-2 conv as a 2x2 stride-1 conv over the space-to-depth view, never materialised):
     // virtual chunk c = (input-pixel parity par = c / cpc, 32-channel chunk c % cpc)
-    auto stage_halo = [&](int buf, int c) {
-        const unsigned base = lds0 + wave * 1024;
-        (void)buf;
+    auto stage_halo = [&](int c) {
         unsigned soff = (unsigned)c * 128u;  // wave-uniform byte offset of the chunk
         if (MODE == 3) {
             const int par = c / cpc;
             soff = (unsigned)((((par >> 1) * 2 * a.W + (par & 1)) * a.in_pix_stride + (c - par * cpc) * 32) * 4);
         }
-#pragma unroll
-        for (int it = 0; it < HALO_IT; ++it) {
-            if (it < HALO_IT - 1 || last_valid) glds16b(hoff[it], in_rsrc, soff, base + it * 4096);
-        }
+        stg_.halo(soff);
     };
     const int total_steps = (MODE == 3) ? cpc * 9 : a.n_chunks * TAPS;  // MODE 3: only the 9 non-zero (tap, parity) pairs
-    const og_i32x4 w_rsrc = og_make_rsrc(a.wpk + (long long)n_tile * total_steps * (WROWS * 32), (unsigned)total_steps * WBYTES);
-    const unsigned woff = (unsigned)tid * 16u;
-    auto stage_w = [&](int stage, int step) {
-        const unsigned base = lds0 + HALO_BYTES + stage * WBYTES + wave * 1024;
-#pragma unroll
-        for (int i = 0; i < NT; ++i) glds16b(woff, w_rsrc, (unsigned)step * WBYTES + i * 4096, base + i * 4096);
-    };
+    stg_.init_w(a, tid, n_tile, total_steps);
+    auto stage_w = [&](int stage, int step) { stg_.w(stage, step); };
 
     // first halo and weights are on their way before the rest of the set-up (which then hides their latency)
     if (!FIRST) {
         if (st != nullptr && tid == 0) st[6] = __builtin_amdgcn_s_memtime();
-        stage_halo(0, c_lo);
+        stage_halo(c_lo);
         stage_w((NSTG == 3) ? s_lo % 3 : (s_lo & 1), s_lo);
     }
 
-    // ---- fragment addressing ----
-    // A rows: i -> 2x2-window-major pixel order, so that the 4 accumulator registers
-    // (reg&3) of one lane are exactly one pooling window (see epilogue).
+    // ---- fragment addressing: og_frag_bases' and og_load_affine's arithmetic, written out -- through the helpers the NT = 2
+    //      instantiations of THIS kernel come out with two SGPRs less and another schedule (profiles/r10_isa_diff.txt) ----
     const int px0 = 2 * (li >> 2) + (li & 1);
     const int pyl = (li >> 1) & 1;
     const int brow = wn * 32 + li;
     const int boff = brow * 128 + ((lh ^ ((brow >> 1) & 7)) << 4);
-    // Everything lane-dependent of an A-fragment address sits in NDX x 4 registers:
-    //   abase[dx][pat] = ((pyl*HW_ + px0+dx) * 128 + ((lh ^ swz(pyl, px0+dx)) << 4) + wave row offset) ^ (pat << 5)
-    // and a tap's dy, the k-group j and the M sub-tile m only select pat = j ^ ((dy & 1) << 1) (row parity flips slot
-    // bit 2) and add the compile-time constant (dy + 2m) * HW_ * 128, which the ds_read carries as its immediate.
-    constexpr int NDX = (MODE == 0) ? 3 : (MODE == 3) ? 2 : 1;
+    constexpr int NDX = T::NDX;
     unsigned abase[NDX][4];
 #pragma unroll
     for (int dx = 0; dx < NDX; ++dx) {
@@ -964,15 +1109,8 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_o(ConvArgs a) {
     if (FIRST) {
         // halo tile of the first layer's OUTPUT, computed here: 12x20 u8 patch -> /255 -> 3x3 conv -> BN -> ReLU,
         // written in the same swizzled [pixel][8 x 16 B] image the LDS-DMA would have produced
-        float* patch = (float*)(smem + HALO_BYTES + NSTG * WBYTES);  // [HH_+2][HW_+2]
-        float* fw = patch + (HH_ + 2) * (HW_ + 2);                // w9[9][32] | scale[32] | shift[32]
-        const uint8_t* fin = a.first_u8 + (long long)b * a.H * a.W;
-        for (int i = tid; i < (HH_ + 2) * (HW_ + 2); i += 256) {
-            const int hy = i / (HW_ + 2), hx = i - hy * (HW_ + 2);
-            const int gy = ty0 + hy - 2, gx = tx0 + hx - 2;
-            patch[i] = (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) ? (float)fin[(long long)gy * a.W + gx] / 255.0f : 0.f;
-        }
-        for (int i = tid; i < 352; i += 256) fw[i] = (i < 288) ? a.first_w9[i] : (i < 320 ? a.first_scale[i - 288] : a.first_shift[i - 320]);
+        const float* patch = og_first_load<T>(a, smem, tid, b, ty0, tx0);
+        const float* fw = patch + T::FIRST_PATCH;
         stage_w(0, 0);
         __syncthreads();
 #pragma unroll
@@ -1071,7 +1209,7 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_o(ConvArgs a) {
             ++step;
         }
         if (c + 1 < c_hi) {  // every read of the halo buffer completed before the barrier above
-            stage_halo(0, c + 1);
+            stage_halo(c + 1);
             og_wait_dma();
             __syncthreads();
         }
@@ -1361,18 +1499,14 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino(ConvArgs a) {
     const int li = lane & 31, lh = lane >> 5;
 
     // tile decode: as k_conv_mfma_o (grid.z = frame group x column tile x frame-in-group)
-    const int bz = (int)blockIdx.z;
-    const int gz = a.zdiv << a.zgroup_shift;
-    const int q_ = (gz == 1) ? bz : (int)(((float)bz + 0.5f) * a.zrcp);
-    const int rz = bz - q_ * gz;
-    const int n_tile = rz >> a.zgroup_shift;
-    const int b = (q_ << a.zgroup_shift) + (rz & ((1 << a.zgroup_shift) - 1));
+    int n_tile, b;
+    og_zdecode(a, (int)blockIdx.z, n_tile, b);
     if (b >= a.frames) return;
     const int ty0 = (int)blockIdx.y * TH, tx0 = (int)blockIdx.x * 16;
     // diagnostic timeline (og_unet_clock_probe only; nullptr on every product path): 8 stamps for the first 511 workgroups
     unsigned long long* st = nullptr;
     if (a.stamps != nullptr) {
-        const unsigned wg = ((unsigned)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        const unsigned wg = og_wg_index();
         st = a.stamps + 8ull * (wg < 511u ? wg : 511u);
         if (tid == 0) st[0] = __builtin_amdgcn_s_memtime();
     }
@@ -1721,15 +1855,11 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_ps(ConvArgs a) {
     // grid.z = k_conv_wino's z (frame group x column tile x frame-in-group) x position group
     const int bzf = (int)blockIdx.z;
     const int pg = bzf % NPG, bz = bzf / NPG;
-    const int gz = a.zdiv << a.zgroup_shift;
-    const int q_ = (gz == 1) ? bz : (int)(((float)bz + 0.5f) * a.zrcp);
-    const int rz = bz - q_ * gz;
-    const int n_tile = rz >> a.zgroup_shift;
-    const int b = (q_ << a.zgroup_shift) + (rz & ((1 << a.zgroup_shift) - 1));
+    int n_tile, b;
+    og_zdecode(a, bz, n_tile, b);
     if (b >= a.frames) return;   // every position group of such a tile returns: nobody waits for it
     // diagnostic timeline (og_unet_clock_probe only; nullptr on every product path): entry, loop start, loop end, exit
-    unsigned long long* const st = a.stamps ? a.stamps + 4ull * (((unsigned)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x < 1023u
-                                                                    ? ((unsigned)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x : 1023u) : nullptr;
+    unsigned long long* const st = a.stamps ? a.stamps + 4ull * (og_wg_index() < 1023u ? og_wg_index() : 1023u) : nullptr;
     if (st != nullptr && tid == 0) st[0] = __builtin_amdgcn_s_memtime();
     const int ty0 = (int)blockIdx.y * TH, tx0 = (int)blockIdx.x * 16;
     const int tile_id = ((b * a.tiles_y + (int)blockIdx.y) * a.tiles_x + (int)blockIdx.x) * a.zdiv + n_tile;
@@ -2007,18 +2137,14 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_w(ConvArgs a) {
     const int li = lane & 31, lh = lane >> 5;
 
     // tile decode: as k_conv_wino (grid.z = frame group x column tile x frame-in-group)
-    const int bz = (int)blockIdx.z;
-    const int gz = a.zdiv << a.zgroup_shift;
-    const int q_ = (gz == 1) ? bz : (int)(((float)bz + 0.5f) * a.zrcp);
-    const int rz = bz - q_ * gz;
-    const int n_tile = rz >> a.zgroup_shift;
-    const int b = (q_ << a.zgroup_shift) + (rz & ((1 << a.zgroup_shift) - 1));
+    int n_tile, b;
+    og_zdecode(a, (int)blockIdx.z, n_tile, b);
     if (b >= a.frames) return;
     const int ty0 = (int)blockIdx.y * TH, tx0 = (int)blockIdx.x * 16;
     // diagnostic timeline (og_unet_clock_probe only; nullptr on every product path): entry, loop start, loop end, exit
     unsigned long long* st = nullptr;
     if (a.stamps != nullptr) {
-        const unsigned wg = ((unsigned)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        const unsigned wg = og_wg_index();
         st = a.stamps + 4ull * (wg < 1023u ? wg : 1023u);
         if (tid == 0) st[0] = __builtin_amdgcn_s_memtime();
     }
@@ -2317,15 +2443,14 @@ __global__ __launch_bounds__(256, 1) void k_conv_wino_wp(ConvArgs a) {
 
     // grid.z = k_conv_wino_w's z (frame x column tile) x position row: a tile's four workgroups are neighbours in the dispatch order
     const int prow = (int)blockIdx.z & 3, bz = (int)blockIdx.z >> 2;
-    const int q_ = (a.zdiv == 1) ? bz : (int)(((float)bz + 0.5f) * a.zrcp);
-    const int n_tile = bz - q_ * a.zdiv;
-    const int b = q_;
+    int n_tile, b;
+    og_zdecode<false>(a, bz, n_tile, b);   // launched with wgs = 4 only: no frame groups
     if (b >= a.frames) return;   // every position row of such a tile returns: nobody waits for it
     const int ty0 = (int)blockIdx.y * 8, tx0 = (int)blockIdx.x * 16;
     const int tile_id = ((b * a.tiles_y + (int)blockIdx.y) * a.tiles_x + (int)blockIdx.x) * a.zdiv + n_tile;
     unsigned long long* st = nullptr;   // diagnostic timeline (og_unet_clock_probe only): entry, loop start, loop end, exit (top bit: reducer)
     if (a.stamps != nullptr) {
-        const unsigned wg = ((unsigned)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        const unsigned wg = og_wg_index();
         st = a.stamps + 4ull * (wg < 1023u ? wg : 1023u);
         if (tid == 0) st[0] = __builtin_amdgcn_s_memtime();
     }
@@ -2528,6 +2653,8 @@ __global__ __launch_bounds__(256) void k_convt_w(ConvArgs a) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, lh = lane >> 5;
+    // (not og_zdecode: this form is laid out with wgs = 1, i.e. never in frame groups and without a tail, so z = b * zdiv + zr plainly;
+    //  the one integer division stays as it is so that this kernel's instructions do)
     const int b = (int)blockIdx.z / a.zdiv;                       // zdiv = column tiles / 4
     const int n_tile = ((int)blockIdx.z - b * a.zdiv) * 4 + wave;
     const int ty0 = (int)blockIdx.y * 2, tx0 = (int)blockIdx.x * 16;
@@ -2587,25 +2714,11 @@ template <int NT, int MODE, int TH, int OCC, bool FIRST = false, bool SQ = false
 __global__ __launch_bounds__(256, OCC) void k_conv_mfma_h(ConvArgs a) {
     static_assert(MODE == 0 || MODE == 1, "split precision: 3x3 conv and transposed conv only");
     static_assert(!SQ || (NT == 2 && TH == 16 && !FIRST), "square wave tiles: 64-column kernel on 16x16 tiles");
-    constexpr int TW = 16;
-    constexpr int PAD = (MODE == 0) ? 1 : 0;
-    constexpr int HW_ = TW + 2 * PAD;
-    constexpr int HH_ = TH + 2 * PAD;
-    constexpr int HALO_PIX = HW_ * HH_;
-    constexpr int HALO_BYTES = HALO_PIX * 128;
-    constexpr int HALO_PIECES = HALO_PIX * 8;
-    constexpr int HALO_IT = (HALO_PIECES + 255) / 256;
-    constexpr int TAPS = (MODE == 0) ? 9 : 1;
-    constexpr int WROWS = 32 * NT;
-    constexpr int WBYTES = WROWS * 128;
-    constexpr int NSTG = (MODE == 0) ? 3 : 2;   // weight ring: a tap's stage is t % 3 (compile time) for the 3x3 conv
-    // Weight slices are staged TWO steps ahead in the 3-stage ring: a step is ~5x shorter than in the f32 kernel (24 MFMAs
-    // of 32 cycles per wave at most), less than the latency of the LDS-DMA that has to land before the next step.
-    constexpr int WAHEAD = (NSTG == 3) ? 2 : 1;
-    constexpr int WM = SQ ? 4 : 4 / NT;          // waves along M
-    constexpr int NC = SQ ? 2 : 1;               // 32-column sub-tiles per wave
-    constexpr int MS = (TH / 2) / WM;            // 32-row M sub-tiles (2 pixel rows x 16) per wave
-    static_assert(MS >= 1, "tile too small");
+    using T = ConvTile<NT, MODE, TH, SQ>;
+    constexpr int TW = T::TW, HW_ = T::HW_, HALO_PIX = T::HALO_PIX, TAPS = T::TAPS, WBYTES = T::WBYTES;
+    constexpr int NSTG = T::NSTG, WAHEAD = T::WAHEAD, NC = T::NC, MS = T::MS;
+    static_assert(T::SCRATCH <= T::lds_bytes, "the epilogue's per-wave scratch lies over the staging buffers");
+    static_assert(!FIRST || T::lds_bytes + T::first_bytes <= 160 * 1024, "the FIRST patch and weights follow the weight ring");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const halo0 = smem;
@@ -2620,12 +2733,8 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_h(ConvArgs a) {
     if (a.prio_mode == 3) __builtin_amdgcn_s_setprio(3);   // set-up, DMA issue and epilogue at raised priority (see k_conv_mfma_o)
 
     // ---- tile decode (scalar): grid = (tile column, tile row, frame group x column tile x frame in group), as k_conv_mfma_o ----
-    const int bz = (int)blockIdx.z;
-    const int gz = a.zdiv << a.zgroup_shift;
-    const int q = (gz == 1) ? bz : (int)(((float)bz + 0.5f) * a.zrcp);   // zrcp = 1 / gz; exact for bz < 2^16
-    const int rz = bz - q * gz;
-    const int zr = rz >> a.zgroup_shift;                                   // column tile x K parts + K part
-    const int b = (q << a.zgroup_shift) + (rz & ((1 << a.zgroup_shift) - 1));
+    int zr, b;   // column tile x K parts + K part, frame
+    og_zdecode(a, (int)blockIdx.z, zr, b);
     if (b >= a.frames) return;   // tail of the last frame group (whole workgroup, before any barrier)
     // split-K (small launches, one frame per chain): K part = a range [s_lo, s_hi) of (chunk, tap) steps; the last part of a
     // tile to arrive sums all parts in split order and runs the epilogue (as k_conv_mfma_o; not with the square wave tiles)
@@ -2640,45 +2749,12 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_h(ConvArgs a) {
     const int c_lo = s_lo / TAPS, c_hi = (s_hi + TAPS - 1) / TAPS;
     const int tile_id = n_tile * a.n_spatial + (b * a.tiles_y + (int)blockIdx.y) * a.tiles_x + (int)blockIdx.x;
 
-    // this frame's input as a raw buffer: offsets past num_records read as zeros (= the conv's zero padding)
-    const og_i32x4 in_rsrc = og_make_rsrc(a.in + (long long)b * a.in_frame_stride + a.in_ch_off,
-                                          (unsigned)(a.in_frame_stride - a.in_ch_off) * 4u);
-
-    // ---- per-thread halo source offsets (bytes, fixed across channel chunks); pixel index walks incrementally ----
-    unsigned hoff[HALO_IT];
-    {
-        int hy = ((tid >> 3) >= HW_) ? 1 : 0;
-        int hx = (tid >> 3) - hy * HW_;
-        const int row_b = a.W * a.in_pix_stride * 4;   // bytes per halo row step
-        const int col_b = a.in_pix_stride * 4;         // bytes per halo column step
-#pragma unroll
-        for (int it = 0; it < HALO_IT; ++it) {
-            const int logical = (tid & 7) ^ og_halo_swz(hy, hx);
-            const int gy = ty0 + hy - PAD, gx = tx0 + hx - PAD;
-            const bool inb = (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
-            hoff[it] = inb ? (unsigned)(gy * row_b + gx * col_b + logical * 16) : OG_OOB;
-            hx += 32 % HW_;
-            hy += 32 / HW_;
-            if (hx >= HW_) { hx -= HW_; hy += 1; }
-        }
-    }
-    const bool last_valid = ((HALO_IT - 1) * 256 + tid) < HALO_PIECES;
-
     const unsigned lds0 = og_lds_addr(smem);
-    auto stage_halo = [&](int c) {
-        const unsigned base = lds0 + wave * 1024;
-#pragma unroll
-        for (int it = 0; it < HALO_IT; ++it) {
-            if (it < HALO_IT - 1 || last_valid) glds16b(hoff[it], in_rsrc, (unsigned)c * 128u, base + it * 4096);
-        }
-    };
-    const og_i32x4 w_rsrc = og_make_rsrc(a.wpk + (long long)n_tile * n_steps * (WROWS * 32), (unsigned)n_steps * WBYTES);
-    const unsigned woff = (unsigned)tid * 16u;
-    auto stage_w = [&](int stage, int step) {
-        const unsigned base = lds0 + HALO_BYTES + stage * WBYTES + wave * 1024;
-#pragma unroll
-        for (int i = 0; i < NT; ++i) glds16b(woff, w_rsrc, (unsigned)step * WBYTES + i * 4096, base + i * 4096);
-    };
+    ConvStage<T> stg_;
+    stg_.init_halo(a, lds0, tid, wave, b, ty0, tx0);
+    stg_.init_w(a, tid, n_tile, n_steps);
+    auto stage_halo = [&](int c) { stg_.halo((unsigned)c * 128u); };
+    auto stage_w = [&](int stage, int step) { stg_.w(stage, step); };
 
     // first halo and weights are on their way before the rest of the set-up (which then hides their latency)
     if (!FIRST) {
@@ -2687,39 +2763,11 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_h(ConvArgs a) {
         if (WAHEAD == 2 && s_lo + 1 < s_hi) stage_w((s_lo + 1) % 3, s_lo + 1);
     }
 
-    // ---- fragment addressing: exactly k_conv_mfma_o's (2x2-window-major pixel order, 12 A registers, 4 B registers) ----
-    const int px0 = 2 * (li >> 2) + (li & 1);
-    const int pyl = (li >> 1) & 1;
-    const int brow = wn * 32 + li;
-    const int boff = brow * 128 + ((lh ^ ((brow >> 1) & 7)) << 4);
-    constexpr int NDX = (MODE == 0) ? 3 : 1;
-    unsigned abase[NDX][4];
-#pragma unroll
-    for (int dx = 0; dx < NDX; ++dx) {
-        const int px = px0 + dx;
-        const unsigned o = (unsigned)((pyl * HW_ + px) * 128 + ((lh ^ og_halo_swz(pyl, px)) << 4) + wm * (MS * 2 * HW_ * 128));
-#pragma unroll
-        for (int pat = 0; pat < 4; ++pat) {
-            abase[dx][pat] = lds0 + (o ^ (unsigned)(pat << 5));   // absolute LDS address
-            asm volatile("" : "+v"(abase[dx][pat]));              // opaque: or hipcc re-adds the (link-time 0) smem base per read
-        }
-    }
-    unsigned bbase[4];
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-        bbase[jj] = lds0 + HALO_BYTES + (unsigned)(boff ^ (jj << 5));
-        asm volatile("" : "+v"(bbase[jj]));
-    }
-
-    // this lane's output channel: folded BN scale / shift, loaded now so that the epilogue does not wait for them
+    unsigned abase[T::NDX][4], bbase[4];
+    og_frag_bases<T>(lds0, li, lh, wm, wn, abase, bbase);
     float esc[NC], esh[NC];
 #pragma unroll
-    for (int n = 0; n < NC; ++n) {
-        const int ecol = n_tile * WROWS + (wn + n) * 32 + li;
-        const int eco = (MODE == 1) ? ecol % a.aff_mod : ecol;
-        esc[n] = a.scale[eco];
-        esh[n] = a.shift[eco];
-    }
+    for (int n = 0; n < NC; ++n) og_load_affine<T>(a, n_tile, wn + n, li, esc[n], esh[n]);
 
     f32x16 acc[NC][MS], cor[NC][MS];   // hi*hi | hi*lo + lo*hi (scaled by 2^11)
 #pragma unroll
@@ -2735,15 +2783,8 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_h(ConvArgs a) {
     if (FIRST) {
         // halo tile of the first layer's OUTPUT, computed here: 12x20 u8 patch -> /255 -> 3x3 conv -> BN -> ReLU, split and
         // written in the swizzled H-layout image the LDS-DMA would have produced
-        float* patch = (float*)(smem + HALO_BYTES + NSTG * WBYTES);  // [HH_+2][HW_+2]
-        float* fw = patch + (HH_ + 2) * (HW_ + 2);                // w9[9][32] | scale[32] | shift[32]
-        const uint8_t* fin = a.first_u8 + (long long)b * a.H * a.W;
-        for (int i = tid; i < (HH_ + 2) * (HW_ + 2); i += 256) {
-            const int hy = i / (HW_ + 2), hx = i - hy * (HW_ + 2);
-            const int gy = ty0 + hy - 2, gx = tx0 + hx - 2;
-            patch[i] = (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) ? (float)fin[(long long)gy * a.W + gx] / 255.0f : 0.f;
-        }
-        for (int i = tid; i < 352; i += 256) fw[i] = (i < 288) ? a.first_w9[i] : (i < 320 ? a.first_scale[i - 288] : a.first_shift[i - 320]);
+        const float* patch = og_first_load<T>(a, smem, tid, b, ty0, tx0);
+        const float* fw = patch + T::FIRST_PATCH;
         stage_w(0, 0);
         if (WAHEAD == 2 && 1 < n_steps) stage_w(1, 1);
         __syncthreads();
@@ -2844,17 +2885,8 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_h(ConvArgs a) {
             for (int r = 0; r < 16; ++r) acc[n][m][r] = fmaf(cor[n][m][r], OG_LO_INV, acc[n][m][r]);
     if (!SQ && ks_n > 1) {
         // this part's (combined, f32) accumulators: device-scope write-through stores, then the arrival counter
-        float* pw = a.partial + (((long long)tile_id * ks_n + kpart) * 4 + wave) * (MS * 16 * 64) + lane;
-#pragma unroll
-        for (int m = 0; m < MS; ++m)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) __hip_atomic_store(pw + (m * 16 + r) * 64, acc[0][m][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's part is written through
-        __syncthreads();
-        int* const flag = (int*)smem;
-        if (tid == 0) *flag = (atomicAdd(a.tile_counter + tile_id, 1) == ks_n - 1) ? 1 : 0;
-        __syncthreads();
-        if (!*(volatile int*)flag) return;   // not the last part of this tile
+        og_splitk_put<MS>(a.partial + (((long long)tile_id * ks_n + kpart) * 4 + wave) * (MS * 16 * 64) + lane, acc[0]);
+        if (!og_splitk_arrive(a.tile_counter + tile_id, ks_n, (int*)smem, tid)) return;   // not the last part of this tile
 #pragma unroll
         for (int m = 0; m < MS; ++m)
 #pragma unroll
@@ -3035,23 +3067,11 @@ template <int NT, int MODE, int TH, int OCC, bool FIRST = false, bool SQ = false
 __global__ __launch_bounds__(256, OCC) void k_conv_mfma_f(ConvArgs a) {
     static_assert(MODE == 0 || MODE == 1, "f16 mode: 3x3 conv and transposed conv only");
     static_assert(!SQ || (NT == 2 && TH == 16 && !FIRST), "square wave tiles: 64-column kernel on 16x16 tiles");
-    constexpr int TW = 16;
-    constexpr int PAD = (MODE == 0) ? 1 : 0;
-    constexpr int HW_ = TW + 2 * PAD;
-    constexpr int HH_ = TH + 2 * PAD;
-    constexpr int HALO_PIX = HW_ * HH_;
-    constexpr int HALO_BYTES = HALO_PIX * 128;
-    constexpr int HALO_PIECES = HALO_PIX * 8;
-    constexpr int HALO_IT = (HALO_PIECES + 255) / 256;
-    constexpr int TAPS = (MODE == 0) ? 9 : 1;
-    constexpr int WROWS = 32 * NT;
-    constexpr int WBYTES = WROWS * 128;
-    constexpr int NSTG = (MODE == 0) ? 3 : 2;
-    constexpr int WAHEAD = (NSTG == 3) ? 2 : 1;   // weight slices two steps ahead (a step is at most 16 MFMAs of 32 cycles per wave)
-    constexpr int WM = SQ ? 4 : 4 / NT;
-    constexpr int NC = SQ ? 2 : 1;
-    constexpr int MS = (TH / 2) / WM;
-    static_assert(MS >= 1, "tile too small");
+    using T = ConvTile<NT, MODE, TH, SQ>;
+    constexpr int TW = T::TW, HW_ = T::HW_, HALO_PIX = T::HALO_PIX, TAPS = T::TAPS, WBYTES = T::WBYTES;
+    constexpr int NSTG = T::NSTG, WAHEAD = T::WAHEAD, NC = T::NC, MS = T::MS;
+    static_assert(T::SCRATCH <= T::lds_bytes, "the epilogue's per-wave scratch lies over the staging buffers");
+    static_assert(!FIRST || T::lds_bytes + T::first_bytes <= 160 * 1024, "the FIRST patch and weights follow the weight ring");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const halo0 = smem;
@@ -3066,56 +3086,20 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_f(ConvArgs a) {
     if (a.prio_mode == 3) __builtin_amdgcn_s_setprio(3);
 
     // ---- tile decode (scalar): grid = (tile column, tile row, frame group x column tile x frame in group), as k_conv_mfma_o ----
-    const int bz = (int)blockIdx.z;
-    const int gz = a.zdiv << a.zgroup_shift;
-    const int q = (gz == 1) ? bz : (int)(((float)bz + 0.5f) * a.zrcp);
-    const int rz = bz - q * gz;
-    const int n_tile = rz >> a.zgroup_shift;
-    const int b = (q << a.zgroup_shift) + (rz & ((1 << a.zgroup_shift) - 1));
+    int n_tile, b;
+    og_zdecode(a, (int)blockIdx.z, n_tile, b);
     if (b >= a.frames) return;   // tail of the last frame group (whole workgroup, before any barrier)
     const int ty0 = (int)blockIdx.y * TH;
     const int tx0 = (int)blockIdx.x * TW;
     const int n_chunks = a.n_chunks;          // 64-channel chunks; the last one holds 32 channels when a.k_half
     const int n_steps = n_chunks * TAPS;
-    const bool only_half = (a.k_half != 0 && n_chunks == 1);
-
-    const og_i32x4 in_rsrc = og_make_rsrc(a.in + (long long)b * a.in_frame_stride + a.in_ch_off,
-                                          (unsigned)(a.in_frame_stride - a.in_ch_off) * 4u);
-
-    unsigned hoff[HALO_IT];
-    {
-        int hy = ((tid >> 3) >= HW_) ? 1 : 0;
-        int hx = (tid >> 3) - hy * HW_;
-        const int row_b = a.W * a.in_pix_stride * 4;
-        const int col_b = a.in_pix_stride * 4;
-#pragma unroll
-        for (int it = 0; it < HALO_IT; ++it) {
-            const int logical = (tid & 7) ^ og_halo_swz(hy, hx);
-            const int gy = ty0 + hy - PAD, gx = tx0 + hx - PAD;
-            const bool inb = (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W && !(only_half && logical >= 4);
-            hoff[it] = inb ? (unsigned)(gy * row_b + gx * col_b + logical * 16) : OG_OOB;
-            hx += 32 % HW_;
-            hy += 32 / HW_;
-            if (hx >= HW_) { hx -= HW_; hy += 1; }
-        }
-    }
-    const bool last_valid = ((HALO_IT - 1) * 256 + tid) < HALO_PIECES;
 
     const unsigned lds0 = og_lds_addr(smem);
-    auto stage_halo = [&](int c) {
-        const unsigned base = lds0 + wave * 1024;
-#pragma unroll
-        for (int it = 0; it < HALO_IT; ++it) {
-            if (it < HALO_IT - 1 || last_valid) glds16b(hoff[it], in_rsrc, (unsigned)c * 128u, base + it * 4096);
-        }
-    };
-    const og_i32x4 w_rsrc = og_make_rsrc(a.wpk + (long long)n_tile * n_steps * (WROWS * 32), (unsigned)n_steps * WBYTES);
-    const unsigned woff = (unsigned)tid * 16u;
-    auto stage_w = [&](int stage, int step) {
-        const unsigned base = lds0 + HALO_BYTES + stage * WBYTES + wave * 1024;
-#pragma unroll
-        for (int i = 0; i < NT; ++i) glds16b(woff, w_rsrc, (unsigned)step * WBYTES + i * 4096, base + i * 4096);
-    };
+    ConvStage<T, true> stg_;
+    stg_.init_halo(a, lds0, tid, wave, b, ty0, tx0, n_chunks);
+    stg_.init_w(a, tid, n_tile, n_steps);
+    auto stage_halo = [&](int c) { stg_.halo((unsigned)c * 128u); };
+    auto stage_w = [&](int stage, int step) { stg_.w(stage, step); };
 
     if (!FIRST) {
         stage_halo(0);
@@ -3123,38 +3107,11 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_f(ConvArgs a) {
         if (WAHEAD == 2 && 1 < n_steps) stage_w(1, 1);
     }
 
-    // ---- fragment addressing: k_conv_mfma_h's ----
-    const int px0 = 2 * (li >> 2) + (li & 1);
-    const int pyl = (li >> 1) & 1;
-    const int brow = wn * 32 + li;
-    const int boff = brow * 128 + ((lh ^ ((brow >> 1) & 7)) << 4);
-    constexpr int NDX = (MODE == 0) ? 3 : 1;
-    unsigned abase[NDX][4];
-#pragma unroll
-    for (int dx = 0; dx < NDX; ++dx) {
-        const int px = px0 + dx;
-        const unsigned o = (unsigned)((pyl * HW_ + px) * 128 + ((lh ^ og_halo_swz(pyl, px)) << 4) + wm * (MS * 2 * HW_ * 128));
-#pragma unroll
-        for (int pat = 0; pat < 4; ++pat) {
-            abase[dx][pat] = lds0 + (o ^ (unsigned)(pat << 5));
-            asm volatile("" : "+v"(abase[dx][pat]));
-        }
-    }
-    unsigned bbase[4];
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-        bbase[jj] = lds0 + HALO_BYTES + (unsigned)(boff ^ (jj << 5));
-        asm volatile("" : "+v"(bbase[jj]));
-    }
-
+    unsigned abase[T::NDX][4], bbase[4];
+    og_frag_bases<T>(lds0, li, lh, wm, wn, abase, bbase);
     float esc[NC], esh[NC];
 #pragma unroll
-    for (int n = 0; n < NC; ++n) {
-        const int ecol = n_tile * WROWS + (wn + n) * 32 + li;
-        const int eco = (MODE == 1) ? ecol % a.aff_mod : ecol;
-        esc[n] = a.scale[eco];
-        esh[n] = a.shift[eco];
-    }
+    for (int n = 0; n < NC; ++n) og_load_affine<T>(a, n_tile, wn + n, li, esc[n], esh[n]);
 
     f32x16 acc[NC][MS];
 #pragma unroll
@@ -3167,15 +3124,8 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_f(ConvArgs a) {
     if (FIRST) {
         // halo tile of the first layer's OUTPUT, computed here (k_conv_first's fma chain), rounded to f16 once and written in the
         // swizzled image the LDS-DMA would have produced: 32 channels = slots 0..3 of the (half) chunk
-        float* patch = (float*)(smem + HALO_BYTES + NSTG * WBYTES);  // [HH_+2][HW_+2]
-        float* fw = patch + (HH_ + 2) * (HW_ + 2);                // w9[9][32] | scale[32] | shift[32]
-        const uint8_t* fin = a.first_u8 + (long long)b * a.H * a.W;
-        for (int i = tid; i < (HH_ + 2) * (HW_ + 2); i += 256) {
-            const int hy = i / (HW_ + 2), hx = i - hy * (HW_ + 2);
-            const int gy = ty0 + hy - 2, gx = tx0 + hx - 2;
-            patch[i] = (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) ? (float)fin[(long long)gy * a.W + gx] / 255.0f : 0.f;
-        }
-        for (int i = tid; i < 352; i += 256) fw[i] = (i < 288) ? a.first_w9[i] : (i < 320 ? a.first_scale[i - 288] : a.first_shift[i - 320]);
+        const float* patch = og_first_load<T>(a, smem, tid, b, ty0, tx0);
+        const float* fw = patch + T::FIRST_PATCH;
         stage_w(0, 0);
         if (WAHEAD == 2 && 1 < n_steps) stage_w(1, 1);
         __syncthreads();
@@ -3358,21 +3308,14 @@ __device__ __forceinline__ void conv_epilogue_fy(const ConvArgs& a, const f32x16
 template <int NT, int MODE, int OCC, bool F32OUT = false>
 __global__ __launch_bounds__(256, OCC) void k_conv_mfma_fy(ConvArgs a) {
     static_assert(MODE == 0 || MODE == 2 || MODE == 3, "detector f16 mode: 3x3, 1x1 and 3x3 stride-2 convs");
-    constexpr int TW = 16, TH = 8;
-    constexpr int PAD = (MODE == 0 || MODE == 3) ? 1 : 0;
-    constexpr int HW_ = (MODE == 3) ? TW + 2 : TW + 2 * PAD;   // MODE 3 needs 17 columns; an even pitch keeps the slot swizzle conflict-free
-    constexpr int HH_ = (MODE == 3) ? TH + 1 : TH + 2 * PAD;
-    constexpr int HALO_PIX = HW_ * HH_;
-    constexpr int HALO_BYTES = HALO_PIX * 128;
-    constexpr int HALO_PIECES = HALO_PIX * 8;
-    constexpr int HALO_IT = (HALO_PIECES + 255) / 256;
-    constexpr int TAPS = (MODE == 0) ? 9 : (MODE == 3) ? 4 : 1;
-    constexpr int WROWS = 32 * NT;
-    constexpr int WBYTES = WROWS * 128;
-    constexpr int NSTG = (MODE == 0) ? 3 : 2;
-    constexpr int WAHEAD = (NSTG == 3) ? 2 : 1;
-    constexpr int WM = 4 / NT;
-    constexpr int MS = (TH / 2) / WM;
+    // (geometry and z decode are the shared ones; the staging, fragment bases and affine load below are ConvStage<T, true>'s,
+    //  og_frag_bases' and og_load_affine's arithmetic written out: through the helpers this kernel's instantiations come out with one
+    //  or two VGPRs fewer and <2, 3> with another K-loop schedule, profiles/r10_isa_diff.txt)
+    constexpr int TH = 8;
+    using T = ConvTile<NT, MODE, TH>;
+    constexpr int TW = T::TW, PAD = T::PAD, HW_ = T::HW_, HALO_BYTES = T::HALO_BYTES, HALO_PIECES = T::HALO_PIECES, HALO_IT = T::HALO_IT;
+    constexpr int TAPS = T::TAPS, WROWS = T::WROWS, WBYTES = T::WBYTES, NSTG = T::NSTG, WAHEAD = T::WAHEAD, MS = T::MS;
+    static_assert(T::SCRATCH <= T::lds_bytes, "the epilogue's per-wave scratch lies over the staging buffers");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -3385,12 +3328,8 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_fy(ConvArgs a) {
     const int lh = lane >> 5;
 
     // ---- tile decode (scalar): grid = (tile column, tile row, frame group x column tile x frame in group), as k_conv_mfma_f ----
-    const int bz = (int)blockIdx.z;
-    const int gz = a.zdiv << a.zgroup_shift;
-    const int q = (gz == 1) ? bz : (int)(((float)bz + 0.5f) * a.zrcp);
-    const int rz = bz - q * gz;
-    const int n_tile = rz >> a.zgroup_shift;
-    const int b = (q << a.zgroup_shift) + (rz & ((1 << a.zgroup_shift) - 1));
+    int n_tile, b;
+    og_zdecode(a, (int)blockIdx.z, n_tile, b);
     if (b >= a.frames) return;   // tail of the last frame group (whole workgroup, before any barrier)
     const int ty0 = (int)blockIdx.y * TH;
     const int tx0 = (int)blockIdx.x * TW;
@@ -3560,24 +3499,15 @@ __global__ __launch_bounds__(256, OCC) void k_conv_mfma_fy(ConvArgs a) {
 // bit-identical between the two).  MODE 2 (this kernel only): 1x1 conv, no halo, plain epilogue.
 template <int NT, int MODE, int TH, int TPS>
 __global__ __launch_bounds__(256, (TH >= 16) ? 1 : 2) void k_conv_mfma_p(ConvArgs a, int n_items) {
-    constexpr int TW = 16;
-    constexpr int PAD = (MODE == 0) ? 1 : 0;
-    constexpr int HW_ = TW + 2 * PAD;
-    constexpr int HH_ = TH + 2 * PAD;
-    constexpr int HALO_PIX = HW_ * HH_;
-    constexpr int HALO_BYTES = HALO_PIX * 128;
-    constexpr int HALO_PIECES = HALO_PIX * 8;
-    constexpr int HALO_IT = (HALO_PIECES + 255) / 256;
-    constexpr int TAPS = (MODE == 0) ? 9 : 1;  // MODE 1 (convT) and MODE 2 (1x1): one tap
+    using T = ConvTile<NT, MODE, TH>;
+    constexpr int TW = T::TW, PAD = T::PAD, HW_ = T::HW_, HALO_BYTES = T::HALO_BYTES, HALO_PIECES = T::HALO_PIECES, HALO_IT = T::HALO_IT;
+    constexpr int TAPS = T::TAPS;  // MODE 1 (convT) and MODE 2 (1x1): one tap
     static_assert(TAPS % TPS == 0, "TPS must divide the tap count");
     constexpr int NSTEP_U = TAPS / TPS;  // steps per (item, chunk) unit
     constexpr int NSUB = TPS * 4;        // k8 sub-steps per step
-    constexpr int WROWS = 32 * NT;
-    constexpr int WBYTES = WROWS * 128;  // one tap slice
+    constexpr int WROWS = T::WROWS, WBYTES = T::WBYTES;
     constexpr int SBYTES = TPS * WBYTES; // one stage
-    constexpr int WM = 4 / NT;
-    constexpr int MS = (TH / 2) / WM;
-    static_assert(MS >= 1, "tile too small");
+    constexpr int MS = T::MS;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const halo0 = smem;

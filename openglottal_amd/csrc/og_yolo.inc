@@ -345,8 +345,8 @@ int y_build_conv(og_yolo* h, const std::string& mod, bool plain_conv2d, int kind
 // k_conv_mfma_fy: the occupancy-shaped grid of launch_conv_f (tile column, tile row, frame group x column tile x frame in group)
 template <int NT, int MODE, bool F32OUT = false>
 int launch_conv_fy(const LaunchCtx& c, const ConvArgs& a_in, int n_ntiles) {
-    constexpr int lds = conv_o_lds<NT, MODE, 8>();
-    static_assert(lds >= 4 * 5120, "the epilogue's per-wave scratch needs 20 KB");
+    constexpr int lds = ConvTile<NT, MODE, 8>::lds_bytes;
+    static_assert(lds <= 160 * 1024, "one workgroup of this tile must fit a CU's LDS");
     ConvArgs a = a_in;
     const int gz = grid_z(c, a, n_ntiles, a.tiles_x * a.tiles_y);
     if (gz < 0) return gz;

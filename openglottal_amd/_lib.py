@@ -1,4 +1,5 @@
-"""ctypes binding of ``libopenglottal_hip.so`` (include/openglottal_hip.h, include/openglottal_hip_crops.h).
+"""ctypes binding of ``libopenglottal_hip.so`` (include/openglottal_hip.h, include/openglottal_hip_crops.h,
+include/openglottal_hip_classic.h).
 
 cffi is not installed in the build image, so the thin C-ABI layer
 the north-star asks for is bound with ctypes; the declarations below are the
@@ -125,6 +126,31 @@ CROP_PROTOTYPES = {
                                      C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
 }
 
+# name -> (restype, argtypes); the complete export list of openglottal_hip_classic.h (guided-VFT and YOLO+Otsu)
+_VFT_STREAM = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+CLASSIC_PROTOTYPES = {
+    "og_classic_limit": (C.c_longlong, [C.c_int]),
+    "og_percentile_host": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
+    "og_otsu_threshold_host": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "og_box_hist_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "og_vft_step_host": (C.c_int, [C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "og_blobs_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "og_classic_create": (C.c_void_p, []),
+    "og_classic_destroy": (None, [C.c_void_p]),
+    "og_classic_sync": (C.c_int, [C.c_void_p]),
+    "og_classic_set_chunk": (C.c_int, [C.c_void_p, C.c_int]),
+    "og_vft_guided_reset": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int]),
+    "og_vft_guided_init_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "og_vft_guided_get_state": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "og_vft_guided_set_state": (C.c_int, [C.c_void_p, C.c_double]),
+    "og_vft_guided_stream_u8": (C.c_int, _VFT_STREAM),
+    "og_vft_guided_stream_frames_u8": (C.c_int, _VFT_STREAM),
+    "og_vft_guided_u8_dev": (C.c_int, _VFT_STREAM),
+    "og_otsu_in_box_u8": (C.c_int, _VFT_STREAM),
+    "og_otsu_in_box_u8_dev": (C.c_int, _VFT_STREAM),
+    "og_classic_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
+}
+
 
 def lib() -> C.CDLL:
     """Load the HIP library once; fail loudly if it is not built."""
@@ -146,7 +172,7 @@ def lib() -> C.CDLL:
             l = C.CDLL(LIB_PATH)
         except OSError as e:  # missing libamdhip64 etc.
             raise OpenGlottalHipError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in list(PROTOTYPES.items()) + list(CROP_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(CROP_PROTOTYPES.items()) + list(CLASSIC_PROTOTYPES.items()):
             fn = getattr(l, name)  # AttributeError if a symbol is missing: also loud
             fn.restype = res
             fn.argtypes = args

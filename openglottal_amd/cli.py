@@ -1,7 +1,9 @@
-"""``python -m openglottal_amd.cli run <video> --pipeline {unet,unet-only,yolo-crop+unet}``.
+"""``python -m openglottal_amd.cli run <video> --pipeline {guided-vft,unet,unet-only,yolo-crop+unet}``.
 
-Counterpart of the two U-Net branches of `openglottal/cli.py:46-103` (`_cmd_run`), plus the ``yolo-crop+unet`` pipeline of
-`scripts/infer.py:222-248` (``--crop-weights``: the crop-trained U-Net checkpoint, `infer.py --crop-weights`): same flags, same
+Counterpart of the ``guided-vft`` branch and the two U-Net branches of `openglottal/cli.py:46-103` (`_cmd_run`), plus the
+``yolo-crop+unet`` pipeline of `scripts/infer.py:222-248` (``--crop-weights``: the crop-trained U-Net checkpoint, `infer.py
+--crop-weights`).  ``guided-vft`` (YOLO-guided VFT, training-free) needs ``--yolo-weights`` only; ``vft`` is refused with the reason
+(its ROI depends on a Gaussian blur that cannot be pinned without OpenCV).  Same flags, same
 `features.json` payload (every key of the feature dict incl. the ``_area`` waveform as a list, `cli.py:97`), same
 messages; ``--annotate`` additionally records ``pipeline``/``video`` in the file.  ``<video>`` may be a ``.npy``/``.npz`` frame stack (or an AVI when OpenCV
 is importable); weights are a torch ``state_dict`` file (U-Net, `weights_only=True`) and a flat
@@ -20,7 +22,7 @@ def main(argv=None) -> int:
     sub = ap.add_subparsers(dest="cmd", required=True)
     r = sub.add_parser("run")
     r.add_argument("video")
-    r.add_argument("--pipeline", choices=["unet", "unet-only", "yolo-crop+unet"], default="unet-only")
+    r.add_argument("--pipeline", choices=["vft", "guided-vft", "unet", "unet-only", "yolo-crop+unet"], default="unet-only")
     r.add_argument("--unet-weights", default=None, help="U-Net checkpoint (required for --pipeline unet / unet-only)")
     r.add_argument("--yolo-weights", default=None)
     r.add_argument("--crop-weights", default=None, help="crop-trained U-Net checkpoint (required for --pipeline yolo-crop+unet)")
@@ -38,6 +40,16 @@ def main(argv=None) -> int:
                         "throughput mode of batched calls)")
     a = ap.parse_args(argv)
     crop = a.pipeline == "yolo-crop+unet"
+    if a.pipeline == "vft":
+        ap.error("--pipeline vft is not provided: its ROI comes from thresholding a Gaussian-blurred f32 motion map, which cannot be "
+                 "pinned without OpenCV (DESIGN.md section 15); use --pipeline guided-vft")
+    if a.pipeline == "guided-vft":
+        if not a.yolo_weights:
+            ap.error("--yolo-weights is required for --pipeline guided-vft")
+        from . import TemporalDetector, extract_features_yolo_guided_vft
+
+        detector = TemporalDetector(a.yolo_weights, precision=a.detector_precision)
+        return _save(a, extract_features_yolo_guided_vft(a.video, detector))
     if crop and not a.crop_weights:
         ap.error("--crop-weights is required for --pipeline yolo-crop+unet")
     if not crop and not a.unet_weights:
@@ -55,7 +67,11 @@ def main(argv=None) -> int:
     if a.precision != "f32":
         model.set_option("precision", {"split": 1, "f16": 2}[a.precision])
     detector = TemporalDetector(a.yolo_weights, precision=a.detector_precision) if (a.pipeline == "unet" or crop) else None
-    feats = extract_features_unet_crop(a.video, detector, model, a.device) if crop else extract_features_unet(a.video, detector, model, a.device)
+    return _save(a, extract_features_unet_crop(a.video, detector, model, a.device) if crop
+                 else extract_features_unet(a.video, detector, model, a.device))
+
+
+def _save(a, feats) -> int:
     if feats is None:
         print("No glottis detected — check your weights or input video.")
         return 1

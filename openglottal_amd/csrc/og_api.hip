@@ -1654,6 +1654,7 @@ static void bgr2gray_host_loop(const uint8_t* __restrict__ bgr, long long n, uin
 
 #include "og_yolo.inc"
 #include "og_crops.inc"
+#include "og_classic.inc"
 
 extern "C" {
 

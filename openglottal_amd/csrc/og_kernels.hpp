@@ -5071,3 +5071,393 @@ __global__ __launch_bounds__(256) void k_scale_boxes(float* __restrict__ best, i
 #pragma unroll
     for (int k = 0; k < 4; ++k) best[(long long)b * 5 + k] = row[k];
 }
+
+// =======================================================================================
+// The training-free family: guided-VFT (openglottal/models/tracker.py:117-232) and YOLO+Otsu (scripts/eval_girafe.py:162-171)
+// over frames that already sit on the device (include/openglottal_hip_classic.h).  Every rule is ONE inline
+// function below, called by the kernels, by the host twins (og_percentile_host, og_otsu_threshold_host, og_blobs_host, ...) and
+// through them by the CPU tests.
+//   * og_roi: a box as utils.normalize_box leaves it (Python slice semantics already applied; x1 < 0: None) cut to the frame.
+//     Empty or inverted: no ROI.  A kernel indexes the frame only inside r[].
+//   * og_percentile_hist: numpy's default (linear) percentile of the sorted ROI bytes, f64, order statistics from the cumulative
+//     histogram: v = (n - 1) * (q / 100), lo = floor(v), g = v - lo, a + (b - a) * g below g = 0.5 and b - (b - a) * (1 - g) from there.
+//   * og_vft_step: thresh = beta * thresh + (1 - beta) * cur, two rounded products and one rounded sum (an FMA gives other bits).
+//   * og_vft_cut: frame < thresh for integer pixels is frame < ceil(thresh), clamped to 0..256.
+//   * og_otsu_hist: OpenCV's getThreshVal_Otsu_8u restated (parity unpinned: OpenCV is absent from the build image).
+//   * og_window_key / og_blob_rank: the blob filter's sort key -- twice the contour area, from the 2x2 windows of the frame padded
+//     by one background ring -- and THE tie rule: among equal areas the blob whose raster-first pixel comes LATER is taken first
+//     (findContours lists external contours last-found-first and Python's sort is stable; unpinned, flip it here).
+// =======================================================================================
+__host__ __device__ inline bool og_roi(int x1, int y1, int x2, int y2, int H, int W, int r[4]) {
+    r[0] = r[1] = r[2] = r[3] = 0;
+    if (x1 < 0 || y1 < 0) return false;
+    const int xe = x2 < W ? x2 : W, ye = y2 < H ? y2 : H;
+    if (xe <= x1 || ye <= y1) return false;
+    r[0] = x1;
+    r[1] = y1;
+    r[2] = xe;
+    r[3] = ye;
+    return true;
+}
+
+__host__ __device__ inline long long og_hist_count(const uint32_t* __restrict__ h) {
+    long long n = 0;
+    for (int i = 0; i < 256; ++i) n += h[i];
+    return n;
+}
+
+// the k-th smallest byte (k from 0) of the multiset a histogram stands for
+__host__ __device__ inline int og_hist_order(const uint32_t* __restrict__ h, long long k) {
+    long long c = 0;
+    for (int i = 0; i < 256; ++i) {
+        c += h[i];
+        if (c > k) return i;
+    }
+    return 255;
+}
+
+// n = og_hist_count(h) >= 1
+__host__ __device__ inline double og_percentile_hist(const uint32_t* __restrict__ h, long long n, double q) {
+#pragma clang fp contract(off)
+    const double v = (double)(n - 1) * (q / 100.0);
+    const double lo = floor(v), g = v - lo;
+    long long ilo = (long long)lo;
+    ilo = ilo < 0 ? 0 : (ilo > n - 1 ? n - 1 : ilo);
+    const long long ihi = ilo + 1 < n - 1 ? ilo + 1 : n - 1;
+    const double a = (double)og_hist_order(h, ilo), b = (double)og_hist_order(h, ihi), d = b - a;
+    if (g < 0.5) {
+        const double t = d * g;
+        return a + t;
+    }
+    const double t = d * (1.0 - g);
+    return b - t;
+}
+
+__host__ __device__ inline double og_vft_step(double thresh, double beta, double cur) {
+#pragma clang fp contract(off)
+    const double a = beta * thresh;
+    const double b = (1.0 - beta) * cur;
+    return a + b;
+}
+
+// tracker.py:225: the frame's percentile when its ROI has more than 10 pixels, else the running threshold
+__host__ __device__ inline double og_vft_next(double thresh, double beta, const uint32_t* __restrict__ h, double q) {
+    const long long n = og_hist_count(h);
+    return og_vft_step(thresh, beta, n > 10 ? og_percentile_hist(h, n, q) : thresh);
+}
+
+__host__ __device__ inline int og_vft_cut(double thresh) {
+    const double c = ceil(thresh);
+    if (!(c > 0.0)) return 0;   // (a NaN threshold selects nothing, as `frame < nan` does)
+    return c > 256.0 ? 256 : (int)c;
+}
+
+__host__ __device__ inline int og_otsu_hist(const uint32_t* __restrict__ h, long long n) {
+#pragma clang fp contract(off)
+    if (n <= 0) return 0;
+    const double eps = 1.1920928955078125e-07;   // FLT_EPSILON
+    const double scale = 1.0 / (double)n;
+    double mu = 0.0;
+    for (int i = 0; i < 256; ++i) mu += (double)i * (double)h[i];
+    mu *= scale;
+    double mu1 = 0.0, q1 = 0.0, max_sigma = 0.0;
+    int best = 0;
+    for (int i = 0; i < 256; ++i) {
+        const double p = (double)h[i] * scale;
+        mu1 *= q1;
+        q1 += p;
+        const double q2 = 1.0 - q1;
+        const double lo = q1 < q2 ? q1 : q2, hi = q1 < q2 ? q2 : q1;
+        if (lo < eps || hi > 1.0 - eps) continue;
+        const double ip = (double)i * p;
+        mu1 = (mu1 + ip) / q1;
+        const double qm = q1 * mu1;
+        const double mu2 = (mu - qm) / q2;
+        const double d = mu1 - mu2;
+        const double sigma = ((q1 * q2) * d) * d;
+        if (sigma > max_sigma) {
+            max_sigma = sigma;
+            best = i;
+        }
+    }
+    return best;
+}
+
+// what one 2x2 window with `filled` blob pixels adds to twice the contour area (its four pixels are mutually 8-adjacent: one blob)
+__host__ __device__ inline int og_window_key(int filled) { return filled == 4 ? 2 : (filled == 3 ? 1 : 0); }
+
+// THE order of the blob filter: a blob with the greater rank is taken first.  Ranks are unique (one raster-first pixel per blob).
+__host__ __device__ inline unsigned long long og_blob_rank(unsigned area2, unsigned first) { return ((unsigned long long)area2 << 32) | first; }
+__host__ __device__ inline unsigned og_blob_rank_first(unsigned long long rank) { return (unsigned)(rank & 0xffffffffull); }
+
+// grid (kHistBlocks, nb): 256-bin histogram of gray(frame) inside the ROI; LDS bins, integer atomics (deterministic);
+// hist [nb,256] must be zero on entry
+constexpr int kHistBlocks = 4;
+template <int C>
+__global__ __launch_bounds__(256) void k_box_hist(const uint8_t* __restrict__ src, int H, int W, const int32_t* __restrict__ boxes,
+                                                  uint32_t* __restrict__ hist) {
+    __shared__ uint32_t bins[256];
+    const int b = blockIdx.y;
+    bins[threadIdx.x] = 0;
+    __syncthreads();
+    int r[4];
+    if (og_roi(boxes[b * 4], boxes[b * 4 + 1], boxes[b * 4 + 2], boxes[b * 4 + 3], H, W, r)) {
+        const uint8_t* frame = src + (long long)b * H * W * C;
+        const int ww = r[2] - r[0], n = (r[3] - r[1]) * ww;
+        for (int p = blockIdx.x * 256 + threadIdx.x; p < n; p += gridDim.x * 256) {
+            const int yy = p / ww;
+            atomicAdd(&bins[og_gray_at<C>(frame, (long long)(r[1] + yy) * W + r[0] + (p - yy * ww))], 1u);
+        }
+    }
+    __syncthreads();
+    if (bins[threadIdx.x]) atomicAdd(&hist[b * 256 + threadIdx.x], bins[threadIdx.x]);
+}
+
+// one thread: tracker.py:200-202, the seed of the running threshold from the histogram of the last init frame
+__global__ void k_vft_seed(const uint32_t* __restrict__ hist, double q, double* __restrict__ state) {
+    const long long n = og_hist_count(hist);
+    *state = n > 0 ? og_percentile_hist(hist, n, q) : 127.0;
+}
+
+// ONE workgroup: a lane per frame takes the percentile (cur, or -1 for "keep the running threshold": n <= 10), then lane 0 walks the
+// frames in order through og_vft_step, from *state (the previous micro-batch's last threshold) and back into it
+__global__ __launch_bounds__(256) void k_vft_thresholds(const uint32_t* __restrict__ hist, int nb, double q, double beta,
+                                                        double* __restrict__ state, double* __restrict__ thresh, int32_t* __restrict__ cut) {
+    for (int b = threadIdx.x; b < nb; b += 256) {
+        const uint32_t* h = hist + b * 256;
+        const long long n = og_hist_count(h);
+        thresh[b] = n > 10 ? og_percentile_hist(h, n, q) : -1.0;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = *state;
+        for (int b = 0; b < nb; ++b) {
+            const double cur = thresh[b];
+            t = og_vft_step(t, beta, cur < 0.0 ? t : cur);
+            thresh[b] = t;
+            cut[b] = og_vft_cut(t);
+        }
+        *state = t;
+    }
+}
+
+// a lane per frame: T and the cut of `gray <= T` (0 for an empty ROI: nothing is selected)
+__global__ __launch_bounds__(64) void k_otsu_thresholds(const uint32_t* __restrict__ hist, int nb, int32_t* __restrict__ T, int32_t* __restrict__ cut) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= nb) return;
+    const long long n = og_hist_count(hist + b * 256);
+    const int t = og_otsu_hist(hist + b * 256, n);
+    T[b] = t;
+    cut[b] = n > 0 ? t + 1 : 0;
+}
+
+// grid (ceil(H*W / 256), nb): mask = 255 where the pixel is inside the ROI and gray < cut[b], else 0 (mask may be null);
+// area (zero on entry) counts them, one 64-lane reduction and one atomicAdd per wave as in k_mask_area
+template <int C>
+__global__ __launch_bounds__(256) void k_threshold_in_box(const uint8_t* __restrict__ src, int H, int W, const int32_t* __restrict__ boxes,
+                                                          const int32_t* __restrict__ cut, uint8_t* __restrict__ mask, int32_t* __restrict__ area) {
+    const int b = blockIdx.y;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    int r[4];
+    const bool ok = og_roi(boxes[b * 4], boxes[b * 4 + 1], boxes[b * 4 + 2], boxes[b * 4 + 3], H, W, r);
+    int cnt = 0;
+    if (p < H * W) {
+        const int y = p / W, x = p - y * W;
+        const bool on = ok && x >= r[0] && x < r[2] && y >= r[1] && y < r[3] && og_gray_at<C>(src + (long long)b * H * W * C, p) < cut[b];
+        if (mask != nullptr) mask[(long long)b * H * W + p] = on ? 255 : 0;
+        cnt = on ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&area[b], cnt);
+}
+
+// --- the blob filter (tracker.py:167-179) -------------------------------------------------------------------------------------
+// ONE workgroup per frame: nothing of a frame leaves its workgroup, so no protocol between workgroups is needed (plain stores are
+// not seen across XCDs), and the chip fills over the frames of a micro-batch.  The two label arrays of a frame (4 bytes per pixel
+// each) live in the handle's workspace; EVERY access to them goes through agent-scope relaxed atomics (they bypass the CU's L1, which
+// may hold a stale line), and the waves of the workgroup meet at og_blob_sync between phases: a release fence, so that a wave's
+// stores and atomics have completed before it arrives, and the barrier.
+// Union by minimum linear index (atomicMin on the greater root; retried from the value found there when another wave got in between):
+// the root of a component is its raster-first pixel, so the labelling is unique -- deterministic -- and carries what the tie rule needs.
+#define OG_LD(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define OG_ST(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+__device__ __forceinline__ void og_blob_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __syncthreads();
+}
+__device__ inline int og_uf_find(int* L, int x) {
+    for (int p; (p = OG_LD(&L[x])) != x;) x = p;   // parents only decrease: the walk ends at a root
+    return x;
+}
+__device__ inline void og_uf_union(int* L, int a0, int b0) {
+    int a = a0, b = b0;
+    for (;;) {
+        a = og_uf_find(L, a);
+        b = og_uf_find(L, b);
+        if (a == b) break;
+        if (a < b) {
+            const int t = a;
+            a = b;
+            b = t;
+        }
+        const int old = atomicMin(&L[a], b);
+        if (old == a) break;
+        a = old;   // a had been hung under `old` meanwhile: that link still has to be joined with b
+    }
+    if (b < a0) atomicMin(&L[a0], b);   // shorten the walks of later finds (b is in a0's set and below it)
+}
+
+constexpr int kBlobThreads = 1024;
+constexpr int kBlobMax = 8;
+// Everything set lies inside the ROI, so the labelling runs on the WINDOW = the ROI grown by one pixel and cut to the frame, with the
+// window's border in the place of the frame's: a window-border pixel is either on the frame border or outside the ROI, where everything
+// is background out to the frame border.  Holes, keys and the raster order of first pixels are those of the whole frame.  A frame
+// without a ROI writes its zero mask and area 0 and labels nothing.  Label indices are window-local.
+template <int C>
+__global__ __launch_bounds__(kBlobThreads) void k_blobs(const uint8_t* __restrict__ src, int H, int W, const int32_t* __restrict__ boxes,
+                                                        const int32_t* __restrict__ cut, int n_comp, int* __restrict__ la_all,
+                                                        int* __restrict__ lb_all, uint8_t* __restrict__ mask, int32_t* __restrict__ area) {
+    __shared__ unsigned long long s_part[kBlobThreads / 64];
+    __shared__ unsigned long long s_pick;
+    __shared__ int s_sel[kBlobMax];
+    __shared__ int s_cnt;
+    const int f = blockIdx.x, tid = threadIdx.x, FN = H * W;
+    const uint8_t* frame = src + (long long)f * FN * C;
+    int* LA = la_all + (long long)f * FN;   // background labels, then the keys
+    int* LB = lb_all + (long long)f * FN;   // raw membership, then the labels of the hole-filled mask
+    int r[4];
+    const bool ok = og_roi(boxes[f * 4], boxes[f * 4 + 1], boxes[f * 4 + 2], boxes[f * 4 + 3], H, W, r);
+    if (!ok) {   // (uniform over the workgroup)
+        if (mask != nullptr)
+            for (int q = tid; q < FN; q += kBlobThreads) mask[(long long)f * FN + q] = 0;
+        if (tid == 0) area[f] = 0;
+        return;
+    }
+    const int x0 = r[0] > 0 ? r[0] - 1 : 0, y0 = r[1] > 0 ? r[1] - 1 : 0;
+    const int ww = (r[2] < W ? r[2] + 1 : W) - x0, wh = (r[3] < H ? r[3] + 1 : H) - y0, N = ww * wh;   // N <= FN
+    const int c = cut[f];
+    if (tid == 0) s_cnt = 0;
+    // raw mask: (gray < thresh) & roi
+    for (int p = tid; p < N; p += kBlobThreads) {
+        const int ly = p / ww, y = y0 + ly, x = x0 + p - ly * ww;
+        const bool on = x >= r[0] && x < r[2] && y >= r[1] && y < r[3] && og_gray_at<C>(frame, (long long)y * W + x) < c;
+        OG_ST(&LA[p], on ? -1 : p);
+        OG_ST(&LB[p], on ? p : -1);
+    }
+    og_blob_sync();
+    // background components, 4-connected
+    for (int p = tid; p < N; p += kBlobThreads) {
+        if (OG_LD(&LA[p]) < 0) continue;
+        const int y = p / ww, x = p - y * ww;
+        if (x > 0 && OG_LD(&LA[p - 1]) >= 0) og_uf_union(LA, p, p - 1);
+        if (y > 0 && OG_LD(&LA[p - ww]) >= 0) og_uf_union(LA, p, p - ww);
+    }
+    og_blob_sync();
+    for (int p = tid; p < N; p += kBlobThreads)
+        if (OG_LD(&LA[p]) >= 0) OG_ST(&LA[p], og_uf_find(LA, p));
+    og_blob_sync();
+    // border contact: the top bit of the root's own entry
+    for (int p = tid; p < N; p += kBlobThreads) {
+        const int y = p / ww, x = p - y * ww;
+        if (x != 0 && y != 0 && x != ww - 1 && y != wh - 1) continue;
+        const int l = OG_LD(&LA[p]);
+        if (l == -1) continue;
+        atomicOr((unsigned*)&LA[l & 0x7fffffff], 0x80000000u);
+    }
+    og_blob_sync();
+    // holes (background whose root never met the border) join the mask
+    for (int p = tid; p < N; p += kBlobThreads) {
+        const int l = OG_LD(&LA[p]);
+        if (l == -1) continue;
+        if (OG_LD(&LA[l & 0x7fffffff]) >= 0) OG_ST(&LB[p], p);
+    }
+    og_blob_sync();
+    // components of the filled mask, 8-connected; LA becomes the key array
+    for (int p = tid; p < N; p += kBlobThreads) {
+        OG_ST(&LA[p], 0);
+        if (OG_LD(&LB[p]) < 0) continue;
+        const int y = p / ww, x = p - y * ww;
+        if (x > 0 && OG_LD(&LB[p - 1]) >= 0) og_uf_union(LB, p, p - 1);
+        if (y > 0) {
+            if (OG_LD(&LB[p - ww]) >= 0) og_uf_union(LB, p, p - ww);
+            if (x > 0 && OG_LD(&LB[p - ww - 1]) >= 0) og_uf_union(LB, p, p - ww - 1);
+            if (x < ww - 1 && OG_LD(&LB[p - ww + 1]) >= 0) og_uf_union(LB, p, p - ww + 1);
+        }
+    }
+    og_blob_sync();
+    for (int p = tid; p < N; p += kBlobThreads)
+        if (OG_LD(&LB[p]) >= 0) OG_ST(&LB[p], og_uf_find(LB, p));
+    og_blob_sync();
+    // keys: the 2x2 windows of the window padded by one background ring
+    for (int w = tid; w < (wh + 1) * (ww + 1); w += kBlobThreads) {
+        const int wy = w / (ww + 1), wx = w - wy * (ww + 1);
+        int filled = 0, root = -1;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int y = wy - 1 + (k >> 1), x = wx - 1 + (k & 1);
+            if (y < 0 || y >= wh || x < 0 || x >= ww) continue;
+            const int l = OG_LD(&LB[y * ww + x]);
+            if (l >= 0) {
+                ++filled;
+                root = l;
+            }
+        }
+        const int key = og_window_key(filled);
+        if (key) atomicAdd(&LA[root], key);
+    }
+    og_blob_sync();
+    // the n_comp greatest ranks, one after the other (rank + 1, so that 0 is "none left")
+    unsigned long long lim = ~0ull;
+    int n_sel = 0;
+    for (int k = 0; k < n_comp; ++k) {
+        unsigned long long best = 0;
+        for (int p = tid; p < N; p += kBlobThreads) {
+            if (OG_LD(&LB[p]) != p) continue;
+            const unsigned long long v = og_blob_rank((unsigned)OG_LD(&LA[p]), (unsigned)p) + 1;
+            if (v < lim && v > best) best = v;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long t = __shfl_down(best, o);
+            best = t > best ? t : best;
+        }
+        if ((tid & 63) == 0) s_part[tid >> 6] = best;
+        __syncthreads();
+        if (tid == 0) {
+            unsigned long long m = 0;
+            for (int i = 0; i < kBlobThreads / 64; ++i) m = s_part[i] > m ? s_part[i] : m;
+            s_pick = m;
+            if (m) s_sel[k] = (int)og_blob_rank_first(m - 1);
+        }
+        __syncthreads();
+        lim = s_pick;
+        if (lim == 0) break;
+        ++n_sel;
+    }
+    // paint the whole frame and count
+    int cnt = 0;
+    if (mask == nullptr)   // areas only: nothing outside the window counts
+        for (int p = tid; p < N; p += kBlobThreads) {
+            const int l = OG_LD(&LB[p]);
+            bool on = false;
+            for (int k = 0; k < n_sel; ++k) on |= (l == s_sel[k]);
+            cnt += (on && l >= 0) ? 1 : 0;
+        }
+    for (int q = tid; mask != nullptr && q < FN; q += kBlobThreads) {
+        const int y = q / W - y0, x = q - (q / W) * W - x0;
+        bool on = false;
+        if (y >= 0 && y < wh && x >= 0 && x < ww) {
+            const int l = OG_LD(&LB[y * ww + x]);
+            for (int k = 0; k < n_sel; ++k) on |= (l == s_sel[k]);
+            on &= l >= 0;
+        }
+        if (mask != nullptr) mask[(long long)f * FN + q] = on ? 255 : 0;
+        cnt += on ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+    if ((tid & 63) == 0 && cnt) atomicAdd(&s_cnt, cnt);
+    __syncthreads();
+    if (tid == 0) area[f] = s_cnt;
+}

@@ -3,8 +3,10 @@
 Same pipelines, metrics and table as the reference for the rows on the U-Net/YOLO path —
 ``unet-only``, ``yolo+unet`` (mask zeroed outside the box), ``yolo-crop+unet``
 (crop → letterbox 256 → U-Net → unletterbox → paste) — but batched: every frame's U-Net
-mask comes from ONE device pass, every crop from a second one.  The classical-CV rows
-(``yolo+otsu``, ``yolo+motion``) are out of scope.
+mask comes from ONE device pass, every crop from a second one.  ``evaluate(..., classical=True)``
+adds the two training-free rows, ``yolo+otsu`` and ``yolo+motion`` (YOLO-guided VFT per patient), in
+the reference's row order; their masks are made and counted on the device (``classic.Classic``,
+``og_mask_stats_dev``).
 
 Inputs are arrays (``[N,H,W,3]`` BGR or ``[N,H,W]`` gray, GT masks ``[N,H,W]``): image-file
 decoding is host I/O behind cv2 and stays with the caller.
@@ -22,6 +24,7 @@ from .geometry import INTER_NEAREST, letterbox, letterbox_with_info, unletterbox
 from .utils import NET_SIZE, bgr_to_gray, frame_metrics, unet_segment_frame
 
 PIPELINES = ["unet-only", "yolo+unet", "yolo-crop+unet"]
+CLASSICAL_PIPELINES = ["unet-only", "yolo+otsu", "yolo+unet", "yolo-crop+unet", "yolo+motion"]   # OUR_PIPELINES, eval_girafe.py:61
 
 
 def unet_on_crop(gray: np.ndarray, box, model, device=None, crop_size: int = NET_SIZE) -> np.ndarray:
@@ -61,14 +64,20 @@ def unet_on_crops(grays: np.ndarray, boxes, model, device=None, crop_size: int =
 
 
 def evaluate(frames, gts, unet_model, detector=None, crop_model=None, device=None, patients=None,
-             reset_every_frame: bool = False, canvas: int | None = None, crop_pad: int = 0):
+             reset_every_frame: bool = False, canvas: int | None = None, crop_pad: int = 0, classical: bool = False):
     """Returns ``(agg, patient_dice, det_stats)``.
+
+    ``classical=True`` adds ``yolo+otsu`` (eval_girafe.py:162-171,270-280) and ``yolo+motion`` (:176-220,310-322) to ``agg``:
+    the latter per run of one patient with a fresh tracker, the first ``YGVFT_INIT`` frames of each run excluded from the metrics
+    but counted in ``n_det`` / ``n_total``.  It needs a detector (``ValueError`` without one).  The default changes nothing.
 
     ``patients``: per-frame patient id → ``detector.reset()`` at every change (GIRAFE,
     eval_girafe.py:246-247).  ``reset_every_frame=True`` is the BAGLS convention
     (eval_bagls.py:164-166).  ``canvas``: letterbox frames and GT to this size first
     (eval_bagls.py:153-155).  ``crop_model`` defaults to ``unet_model`` (eval_girafe.py:302).
     """
+    if classical and detector is None:
+        raise ValueError("classical=True needs a detector: yolo+otsu and yolo+motion are defined by its boxes")
     frames = [np.asarray(f) for f in frames]
     gts = [np.asarray(g) for g in gts]
     if canvas is not None:
@@ -118,7 +127,7 @@ def evaluate(frames, gts, unet_model, detector=None, crop_model=None, device=Non
     else:
         masks_u = np.stack([unet_segment_frame(g, unet_model, device) for g in grays])
 
-    agg = {p: {"dice": [], "iou": [], "n_det": 0, "n_total": 0} for p in PIPELINES}
+    agg = {p: {"dice": [], "iou": [], "n_det": 0, "n_total": 0} for p in (CLASSICAL_PIPELINES if classical else PIPELINES)}
     patient_dice: dict = defaultdict(lambda: defaultdict(list))
 
     def add(pipe, i, mask, detected):
@@ -146,7 +155,67 @@ def evaluate(frames, gts, unet_model, detector=None, crop_model=None, device=Non
         masks_c = unet_on_crops(grays, cboxes, crop_model if crop_model is not None else unet_model, device)
         for i in range(n):
             add("yolo-crop+unet", i, masks_c[i], boxes[i] is not None)
+        if classical:
+            _classical_rows(agg, patient_dice, grays, gts, boxes, patients, unet_model)
     return agg, {k: dict(v) for k, v in patient_dice.items()}, det_stats
+
+
+def _classical_rows(agg, patient_dice, grays, gts, boxes, patients, unet_model) -> None:
+    """``yolo+otsu`` and ``yolo+motion`` on the device: frames, ground truth and masks stay there, 12 bytes of confusion counts
+    per frame come back (``og_mask_stats_dev``).  The boxes are those of the pass above: the reference runs the detector a second
+    time per patient for ``yolo+motion`` (eval_girafe.py:189-199), from ``reset()`` and over the same frames, so it sees the same."""
+    import torch
+
+    from ._lib import check, lib, ptr
+    from .classic import Classic
+    from .features import YGVFT_INIT, YGVFT_PARAMS
+    from .utils import normalize_box
+
+    n, H, W = grays.shape
+    unet_model._require()
+    dev = torch.device("cuda", unet_model._device or 0)
+    d_gray = torch.from_numpy(np.ascontiguousarray(grays)).to(dev)
+    d_gt = torch.from_numpy(np.ascontiguousarray(gts)).to(dev)
+    d_box = torch.from_numpy(np.array([normalize_box(b, W, H) for b in boxes], np.int32).reshape(n, 4)).to(dev)
+    mask = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
+    area = torch.empty(n, dtype=torch.int32, device=dev)
+    stats = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    eng = Classic(YGVFT_PARAMS["beta"], YGVFT_PARAMS["glottal_percentile"], YGVFT_PARAMS["max_glottal_components"])
+
+    def count(lo, hi):   # confusion counts of mask[lo:hi] against the ground truth -> (dice, iou) per frame
+        eng.sync()
+        check(lib().og_mask_stats_dev(unet_model._h, ptr(mask[lo:hi]), ptr(d_gt[lo:hi]), hi - lo, H, W, None, ptr(stats[lo:hi])),
+              "og_mask_stats_dev")
+        unet_model.sync()
+        return [metrics_from_counts(int(tp), int(npred), int(ngt)) for tp, npred, ngt in stats[lo:hi].cpu().numpy()]
+
+    T = torch.empty(n, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)
+    eng.otsu_in_box_dev(d_gray, n, H, W, 1, d_box, area, T, mask)
+    for i, (d, j) in enumerate(count(0, n)):
+        agg["yolo+otsu"]["dice"].append(d)
+        agg["yolo+otsu"]["iou"].append(j)
+        agg["yolo+otsu"]["n_total"] += 1
+        agg["yolo+otsu"]["n_det"] += int(boxes[i] is not None)
+        patient_dice[patients[i]]["yolo+otsu"].append(d)
+    lo = 0
+    while lo < n:   # runs of one patient
+        hi = lo + 1
+        while hi < n and patients[hi] == patients[lo]:
+            hi += 1
+        agg["yolo+motion"]["n_det"] += sum(b is not None for b in boxes[lo:hi])
+        agg["yolo+motion"]["n_total"] += hi - lo
+        first = lo + YGVFT_INIT
+        if first <= hi:
+            eng.reset(YGVFT_PARAMS["beta"], YGVFT_PARAMS["glottal_percentile"], YGVFT_PARAMS["max_glottal_components"])
+            eng.init(grays[lo:first], next((b for b in boxes[lo:first] if b is not None), None))
+            if first < hi:
+                eng.guided_vft_dev(d_gray[first:hi], hi - first, H, W, 1, d_box[first:hi], area[first:hi], mask[first:hi])
+                for d, j in count(first, hi):
+                    agg["yolo+motion"]["dice"].append(d)
+                    agg["yolo+motion"]["iou"].append(j)
+                    patient_dice[patients[lo]]["yolo+motion"].append(d)
+        lo = hi
 
 
 def summarize(agg) -> dict:
@@ -166,7 +235,8 @@ def summarize(agg) -> dict:
 
 
 def print_table(agg) -> None:
-    label = {"unet-only": "U-Net only", "yolo+unet": "YOLO+UNet", "yolo-crop+unet": "YOLO-Crop+UNet"}
+    label = {"unet-only": "U-Net only", "yolo+otsu": "YOLO+OTSU", "yolo+unet": "YOLO+UNet", "yolo-crop+unet": "YOLO-Crop+UNet",
+             "yolo+motion": "YOLO+Motion"}
     sep = "─" * 76
     print(f"\n{sep}\n  {'Method':<25}  {'Det.Recall':>10}  {'Dice':>8}  {'IoU':>8}  {'Dice≥0.5':>10}\n{sep}")
     for p, r in summarize(agg).items():

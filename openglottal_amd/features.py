@@ -1,4 +1,4 @@
-"""`extract_features_unet` and `_kinematic_features` (`openglottal/features.py`)."""
+"""`extract_features_unet`, `extract_features_yolo_guided_vft` and `_kinematic_features` (`openglottal/features.py`)."""
 
 from __future__ import annotations
 
@@ -8,6 +8,10 @@ import numpy as np
 
 from ._lib import OpenGlottalHipError
 from .utils import NET_SIZE, bgr_to_gray, normalize_box, unet_segment_frame
+
+# Defaults of pipeline 2 (features.py:23-32).  alpha and gaussian_ksize drive the tracker's motion map, which reaches no output.
+YGVFT_PARAMS = dict(alpha=0.98, beta=0.7, glottal_percentile=30, gaussian_ksize=13, max_glottal_components=2)
+YGVFT_INIT = 2  # seed frames
 
 
 def _kinematic_features(area_wave) -> dict | None:
@@ -261,4 +265,62 @@ def extract_features_unet_crop(avi_path, detector, crop_model, device=None) -> d
     wave = crop_area_waveform(avi_path, detector, crop_model, device)
     if len(wave) == 0:
         return None
+    return _kinematic_features([float(v) for v in wave])
+
+
+def guided_vft_area_waveform(frames, detector, ygvft_init: int = YGVFT_INIT, params: dict | None = None) -> np.ndarray:
+    """The frame loop of features.py:178-194 (YOLO-guided VFT) as batched device passes: the first ``ygvft_init`` frames seed the
+    tracker (threshold from the last of them inside the first box seen among them) and contribute ``0.0``; every later frame is
+    ``sum(process_frame(gray, box) > 0)``.
+
+    The blocks and their boxes come from ``_blocks_with_boxes``, unchanged: with the native detector backend the detector network
+    and the temporal state machine of block k + 1 run on the worker thread under the classical pass of block k.  Each run of
+    equal-shape u8 frames (gray or BGR, any size) goes to ``Classic.guided_vft``; the threshold is carried on the device from
+    call to call.  A video shorter than ``ygvft_init`` frames gives all zeros.
+    """
+    from .classic import Classic
+
+    if ygvft_init < 1:
+        raise ValueError("ygvft_init must be at least 1")
+    p = dict(YGVFT_PARAMS, **(params or {}))
+    eng = Classic(p["beta"], p["glottal_percentile"], p["max_glottal_components"])
+    detector.reset()
+    out, seen, first_box, seeded = [], 0, None, False
+    for blk, boxes in _blocks_with_boxes(frames, detector):
+        n = len(blk)
+        a = np.zeros(n, np.float64)
+        lo0 = 0
+        if not seeded:
+            lo0 = min(n, ygvft_init - seen)
+            for i in range(lo0):
+                if first_box is None and boxes[i][0] >= 0:
+                    first_box = tuple(int(v) for v in boxes[i])
+            seen += lo0
+            if seen >= ygvft_init:
+                last = blk[lo0 - 1]
+                eng.init([last if getattr(last, "dtype", None) == np.uint8 else bgr_to_gray(last)], first_box)
+                seeded = True
+        if seeded and lo0 < n:
+            rest = blk[lo0:]
+            for lo, hi in _shape_runs(rest):
+                run = rest[lo:hi]
+                f0 = run[0]
+                if not (getattr(f0, "dtype", None) == np.uint8 and (f0.ndim == 2 or (f0.ndim == 3 and f0.shape[2] == 3))):
+                    run = [bgr_to_gray(f) for f in run]   # any other dtype / layout: the host conversion of features.py:179
+                _, ar = eng.guided_vft(run if isinstance(run, np.ndarray) else list(run), boxes[lo0 + lo:lo0 + hi], want_mask=False)
+                a[lo0 + lo:lo0 + hi] = ar
+        out.append(a)
+    return np.concatenate(out) if out else np.zeros(0, np.float64)
+
+
+def extract_features_yolo_guided_vft(avi_path, detector, ygvft_init: int = YGVFT_INIT) -> dict | None:
+    """Drop-in for `openglottal/features.py:147-196`: ``None`` below ``ygvft_init + 2`` frames or for a silent waveform."""
+    src = avi_path
+    if isinstance(src, str) and src.endswith(".npy") and os.path.exists(src):
+        src = np.load(src, mmap_mode="r")
+    elif not isinstance(src, (np.ndarray, list, tuple)):
+        src = load_frames_bgr(src)
+    if len(src) < ygvft_init + 2:
+        return None
+    wave = guided_vft_area_waveform(src, detector, ygvft_init)
     return _kinematic_features([float(v) for v in wave])

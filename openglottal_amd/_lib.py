@@ -1,5 +1,5 @@
 """ctypes binding of ``libopenglottal_hip.so`` (include/openglottal_hip.h, include/openglottal_hip_crops.h,
-include/openglottal_hip_classic.h).
+include/openglottal_hip_classic.h, include/openglottal_hip_gated.h).
 
 cffi is not installed in the build image, so the thin C-ABI layer
 the north-star asks for is bound with ctypes; the declarations below are the
@@ -151,6 +151,25 @@ CLASSIC_PROTOTYPES = {
     "og_classic_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
 }
 
+# name -> (restype, argtypes); the complete export list of openglottal_hip_gated.h (device tracker, gated engine)
+_GATED_STREAM = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+GATED_PROTOTYPES = {
+    "og_track_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "og_gated_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
+    "og_gated_create": (C.c_void_p, [C.c_void_p, C.c_void_p]),
+    "og_gated_destroy": (None, [C.c_void_p]),
+    "og_gated_sync": (C.c_int, [C.c_void_p]),
+    "og_gated_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
+    "og_gated_reset": (C.c_int, [C.c_void_p]),
+    "og_gated_set_params": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "og_gated_get_state": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "og_gated_set_state": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "og_track_boxes_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "og_gated_stream_u8": (C.c_int, _GATED_STREAM),
+    "og_gated_stream_frames_u8": (C.c_int, _GATED_STREAM),
+}
+
 
 def lib() -> C.CDLL:
     """Load the HIP library once; fail loudly if it is not built."""
@@ -172,7 +191,8 @@ def lib() -> C.CDLL:
             l = C.CDLL(LIB_PATH)
         except OSError as e:  # missing libamdhip64 etc.
             raise OpenGlottalHipError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in list(PROTOTYPES.items()) + list(CROP_PROTOTYPES.items()) + list(CLASSIC_PROTOTYPES.items()):
+        for name, (res, args) in (list(PROTOTYPES.items()) + list(CROP_PROTOTYPES.items()) + list(CLASSIC_PROTOTYPES.items())
+                                  + list(GATED_PROTOTYPES.items())):
             fn = getattr(l, name)  # AttributeError if a symbol is missing: also loud
             fn.restype = res
             fn.argtypes = args

@@ -1655,6 +1655,7 @@ static void bgr2gray_host_loop(const uint8_t* __restrict__ bgr, long long n, uin
 #include "og_yolo.inc"
 #include "og_crops.inc"
 #include "og_classic.inc"
+#include "og_gated.inc"
 
 extern "C" {
 

@@ -5461,3 +5461,149 @@ __global__ __launch_bounds__(kBlobThreads) void k_blobs(const uint8_t* __restric
     __syncthreads();
     if (tid == 0) area[f] = s_cnt;
 }
+
+// =======================================================================================
+// The temporal tracker of the gated pipeline (openglottal/models/detector.py:61-96; include/openglottal_hip_gated.h, DESIGN.md
+// section 16): one box per frame from the detector's `best` row and the state carried from the frame before.  The rule is ONE
+// inline function, og_track_step, in two halves -- og_track_measure (independent per frame: centre, padded size, has-detection) and
+// og_track_advance (sequential: jump test, hold, miss counter, clamp, Python-slice normalisation) -- called by k_track_boxes, by
+// og_track_host and through it by the CPU tests.  The arithmetic is that of numpy 2 on f32 scalars (detector.py keeps the centre
+// as np.float32 and compares it with Python numbers, which numpy takes to f32).
+// =======================================================================================
+struct OgTrackState {   // the words of og_track_state, in its order
+    float cx, cy;       // centre of the last accepted detection
+    int w, h;           // its size, padding included
+    int misses;
+    int has;            // 0: no centre (detector.py's `_centre is None`; the other words are then 0)
+};
+struct OgTrackParams {
+    float max_shift;
+    int padding, max_hold;
+};
+
+// detector.py:65-68: `row` = x1, y1, x2, y2, conf; conf < 0 is "no detection"
+__host__ __device__ inline bool og_track_measure(const float* row, int padding, float& cx, float& cy, int& w, int& h) {
+#pragma clang fp contract(off)
+    const float x1 = row[0], y1 = row[1], x2 = row[2], y2 = row[3];
+    cx = (x1 + x2) / 2.0f;
+    cy = (y1 + y2) / 2.0f;
+    w = (int)(x2 - x1) + 2 * padding;   // int(): toward zero
+    h = (int)(y2 - y1) + 2 * padding;
+    return row[4] >= 0.0f;
+}
+
+// np.hypot on two f32 scalars: the sum of the exact squares rounded once in f64, its root, one rounding to f32
+__host__ __device__ inline float og_track_hypot(float dx, float dy) {
+#pragma clang fp contract(off)
+    const double a = (double)dx * (double)dx, b = (double)dy * (double)dy;
+    return (float)sqrt(a + b);
+}
+
+__host__ __device__ inline int og_floor_half(int v) { return v >> 1; }   // Python's v // 2
+
+// slice(a, b).indices(n) for step 1: each end counted from the far edge when negative, then clamped to 0..n
+__host__ __device__ inline int og_slice_end(int v, int n) {
+    if (v < 0) {
+        v += n;
+        return v < 0 ? 0 : v;
+    }
+    return v > n ? n : v;
+}
+
+// np.clip(c, lo, hi) on f32 (minimum(maximum(c, lo), hi): hi where lo > hi), then int()
+__host__ __device__ inline int og_track_clamp(float c, int lo, int hi) {
+    const float l = (float)lo, u = (float)hi;
+    float v = c < l ? l : c;
+    v = v > u ? u : v;
+    return (int)v;
+}
+
+// detector.py:70-87 and utils.normalize_box: (-1,-1,-1,-1) for None, (0,0,0,0) for an empty slice
+__host__ __device__ inline void og_track_advance(OgTrackState& s, bool det, float cx, float cy, int w, int h, int W, int H,
+                                                 const OgTrackParams& p, int box[4]) {
+#pragma clang fp contract(off)
+    bool fresh = det;
+    if (det && s.has) {
+        const float jump = og_track_hypot(cx - s.cx, cy - s.cy);
+        if (jump > p.max_shift) fresh = false;   // spurious jump: treated as a miss
+    }
+    if (fresh) {
+        s.cx = cx;
+        s.cy = cy;
+        s.w = w;
+        s.h = h;
+        s.misses = 0;
+        s.has = 1;
+    } else if (s.has) {
+        ++s.misses;
+        if (s.misses > p.max_hold) s = OgTrackState{0.f, 0.f, 0, 0, 0, 0};
+    }
+    if (!s.has) {
+        box[0] = box[1] = box[2] = box[3] = -1;
+        return;
+    }
+    const int hw = og_floor_half(s.w), hh = og_floor_half(s.h);
+    const int bx = og_track_clamp(s.cx, hw, W - hw), by = og_track_clamp(s.cy, hh, H - hh);
+    const int xs = og_slice_end(bx - hw, W), xe = og_slice_end(bx + hw, W);
+    const int ys = og_slice_end(by - hh, H), ye = og_slice_end(by + hh, H);
+    const bool empty = xe <= xs || ye <= ys;
+    box[0] = empty ? 0 : xs;
+    box[1] = empty ? 0 : ys;
+    box[2] = empty ? 0 : xe;
+    box[3] = empty ? 0 : ye;
+}
+
+__host__ __device__ inline void og_track_step(OgTrackState& s, const float* row, int W, int H, const OgTrackParams& p, int box[4]) {
+    float cx, cy;
+    int w, h;
+    const bool det = og_track_measure(row, p.padding, cx, cy, w, h);
+    og_track_advance(s, det, cx, cy, w, h, W, H, p, box);
+}
+
+// ONE workgroup.  Per block of 256 frames: a lane per frame measures its `best` row into LDS; after the barrier lane 0 walks the
+// block in frame order through og_track_advance, from the state words in device memory (the previous launch's last state: the
+// stream orders the launches) and back into them; then every lane stores its frame's box.  resets (may be null): a nonzero byte
+// clears the state before that frame.
+__global__ __launch_bounds__(256) void k_track_boxes(const float* __restrict__ best, const uint8_t* __restrict__ resets, int B, int W, int H,
+                                                     float max_shift, int padding, int max_hold, OgTrackState* __restrict__ state,
+                                                     int32_t* __restrict__ boxes) {
+    __shared__ float s_cx[256], s_cy[256];
+    __shared__ int s_w[256], s_h[256], s_flag[256];   // flag: bit 0 has-detection, bit 1 reset before the frame
+    __shared__ int s_box[256][4];
+    __shared__ OgTrackState s_state;
+    const int tid = threadIdx.x;
+    const OgTrackParams p{max_shift, padding, max_hold};
+    if (tid == 0) s_state = *state;
+    for (int b0 = 0; b0 < B; b0 += 256) {
+        const int nb = B - b0 < 256 ? B - b0 : 256;
+        if (tid < nb) {
+            float row[5];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) row[k] = best[(long long)(b0 + tid) * 5 + k];
+            float cx, cy;
+            int w, h;
+            const bool det = og_track_measure(row, padding, cx, cy, w, h);
+            s_cx[tid] = cx;
+            s_cy[tid] = cy;
+            s_w[tid] = w;
+            s_h[tid] = h;
+            s_flag[tid] = (det ? 1 : 0) | ((resets != nullptr && resets[b0 + tid] != 0) ? 2 : 0);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            OgTrackState s = s_state;
+            for (int i = 0; i < nb; ++i) {
+                if (s_flag[i] & 2) s = OgTrackState{0.f, 0.f, 0, 0, 0, 0};
+                og_track_advance(s, (s_flag[i] & 1) != 0, s_cx[i], s_cy[i], s_w[i], s_h[i], W, H, p, s_box[i]);
+            }
+            s_state = s;
+        }
+        __syncthreads();
+        if (tid < nb) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) boxes[(long long)(b0 + tid) * 4 + k] = s_box[tid][k];
+        }
+        __syncthreads();   // (the next block's measurements overwrite the arrays lane 0 has just read)
+    }
+    if (tid == 0) *state = s_state;
+}

@@ -86,6 +86,18 @@ class TemporalDetector:
         cy = int(np.clip(self._centre[1], hh, H - hh))
         return (cx - hw, cy - hh, cx + hw, cy + hh)
 
+    def track(self, best, W: int, H: int, resets=None) -> np.ndarray:
+        """``update`` over a block (an extension): ``best [n,5]`` f32 rows ``x1, y1, x2, y2, conf`` (``conf < 0``: no detection,
+        as ``YoloV8Detector.detect_frames`` returns them) → ``boxes [n,4]`` int32 as ``utils.normalize_box`` leaves them
+        (``-1``: ``None``).  The native host twin of the device tracker (``og_track_host``: the same state machine, the same f32
+        arithmetic); continues from and leaves this object's state.  ``resets [n]``: nonzero resets before that frame."""
+        from . import gated
+
+        st = gated.state_of_detector(self)
+        boxes = gated.track_host(st, gated.params_of(self.max_shift, self.padding, self.max_hold_frames), best, W, H, resets)
+        gated.state_to_detector(st, self)
+        return boxes
+
     def crop(self, frame: np.ndarray, box):
         if box is None:
             return frame

@@ -171,8 +171,87 @@ def _shape_runs(frames):
     return runs
 
 
-def area_waveform(frames, detector, model, device=None, threshold: float = 0.5) -> np.ndarray:
+def _u8_frames_of_one_shape(frames) -> bool:
+    if isinstance(frames, np.ndarray):
+        return frames.dtype == np.uint8 and len(frames) > 0 and (frames.ndim == 3 or (frames.ndim == 4 and frames.shape[3] == 3))
+    f0 = frames[0] if len(frames) else None
+    if not isinstance(f0, np.ndarray) or f0.dtype != np.uint8 or not (f0.ndim == 2 or (f0.ndim == 3 and f0.shape[2] == 3)):
+        return False
+    return all(isinstance(f, np.ndarray) and f.dtype == np.uint8 and f.shape == f0.shape for f in frames)
+
+
+def gated_engine_for(frames, detector, model, policy: bool = True):
+    """The device engine (``gated.GatedEngine``) when ``area_waveform(engine="auto")`` may take it for this call, else
+    ``None``: a plain ``TemporalDetector`` (no method replaced on the instance, parameters plain numbers) on the native detector
+    backend whose ``detect_frames`` is not overridden on the instance, a native ``UNet`` whose streamed entries are not overridden on
+    the instance either, u8 gray or BGR frames of one shape, and -- unless ``policy`` is False, which is what ``engine="device"``
+    passes -- a frame size at which the engine was measured ahead and a length at which both passes give the same bits.  The
+    engine is kept on the detector backend and rebuilt when either network handle has changed."""
+    from .detector import TemporalDetector
+    from .unet import UNet
+    from .yolo import YoloV8Detector
+
+    if type(detector) is not TemporalDetector or type(detector.model) is not YoloV8Detector or type(model) is not UNet:
+        return None
+    if {"update", "detect", "reset", "track"} & set(vars(detector)) or "detect_frames" in vars(detector.model):
+        return None
+    if {"segment", "segment_stream", "segment_resized"} & set(vars(model)):
+        return None   # an entry of the staged pass replaced on the model object: whoever did that wants to see its calls
+    if not (isinstance(detector.max_shift, (int, float)) and isinstance(detector.padding, int) and isinstance(detector.max_hold_frames, int)):
+        return None
+    if not _u8_frames_of_one_shape(frames):
+        return None
+    if not policy:
+        return _cached_gated_engine(detector.model, model)
+    if tuple(frames[0].shape[:2]) == (NET_SIZE, NET_SIZE):
+        # measured (DESIGN §16, profiles/gated_engine.json): at network size the staged pass already hides the detector under a
+        # U-Net pass that runs on two lanes, and the engine's single-lane U-Net entry ends level with it or 2 % behind
+        return None
+    blk = gated_block(model)
+    if blk % 256 == 1 or (len(frames) % blk) % 256 == 1:
+        # the staged pass would hand a frame to the detector alone (its blocks go to the network 256 frames at a time), on the
+        # one-frame latency kernels, whose sums run in another order; the engine runs every frame on the batched kernels.  Same
+        # bits first: such a video stays staged.
+        return None
+    return _cached_gated_engine(detector.model, model)
+
+
+def _cached_gated_engine(yolo, model):
+    from .gated import GatedEngine
+
+    cache = yolo.__dict__.setdefault("_gated_engines", {})     # on the backend: TemporalDetector objects come and go per video
+    eng = cache.get(id(model))
+    if eng is None or not eng.valid_for(model, yolo):
+        model._require()
+        if len(cache) >= 4:
+            cache.clear()
+        eng = cache[id(model)] = GatedEngine(model, yolo, hold_yolo=False)
+    return eng
+
+
+def _gated_device_pass(eng, frames, detector, threshold: float) -> np.ndarray:
+    """The whole video through the device engine in one call (it streams micro-batches itself); the Python detector is left in
+    the state the staged pass would have left it in, so ``crop_size`` and a following ``detect()`` behave as before."""
+    from . import gated
+
+    detector.reset()
+    eng.reset()
+    eng.set_params(detector.max_shift, detector.padding, detector.max_hold_frames)
+    src = frames if isinstance(frames, np.ndarray) and frames.flags.c_contiguous else list(frames)
+    try:
+        out = eng.run(src, conf=detector.conf, threshold=threshold, net=NET_SIZE, want_boxes=False)
+    finally:
+        gated.state_to_detector(eng.get_state(), detector)
+    return out["area"].astype(np.float64)
+
+
+def area_waveform(frames, detector, model, device=None, threshold: float = 0.5, engine: str = "auto") -> np.ndarray:
     """The frame loop of features.py:234-245 as batched device passes over blocks of the video.
+
+    ``engine``: ``"staged"`` is the host-stitched gated pass described below; ``"auto"`` (the default) takes the device engine of
+    DESIGN §16 -- one upload per frame, detector, tracker and U-Net in one device pass, the same bits -- when
+    ``gated_engine_for`` allows it, and the staged pass otherwise (mixed shapes, other dtypes, scripted or wrapped detectors, frames
+    at network size, where the engine was measured level or behind); ``"device"`` insists on the engine and raises where it cannot run.
 
     U-Net-only (``detector is None``): area = #(mask>0) per frame.  Gated: the sequential TemporalDetector pass produces
     one box per frame first (the U-Net does not depend on it), then the fused kernel counts inside the boxes.  Frames at
@@ -180,8 +259,22 @@ def area_waveform(frames, detector, model, device=None, threshold: float = 0.5) 
     the device — so no per-frame host work is left and device memory does not grow with the video.  Frames of any other size
     (each run of one shape inside a mixed block) take the same engine with the two resizes of utils.py:234,239-240 on the device.
     """
+    if engine not in ("auto", "staged", "device"):
+        raise ValueError(f"engine must be 'auto', 'staged' or 'device', not {engine!r}")
     if device is not None and getattr(model, "_device", None) is None:
         model.to(device)
+    if engine == "device" and detector is None:
+        raise OpenGlottalHipError("engine='device' is the gated pass: it needs a detector")
+    if engine != "staged" and detector is not None:
+        if isinstance(frames, str) and frames.endswith(".npy") and os.path.exists(frames):
+            frames = np.load(frames, mmap_mode="r")
+        elif not isinstance(frames, (np.ndarray, list, tuple)):
+            frames = load_frames_bgr(frames)   # (decoded once, whichever path takes them)
+        eng = gated_engine_for(frames, detector, model, policy=engine == "auto")
+        if eng is not None:
+            return _gated_device_pass(eng, frames, detector, threshold)
+        if engine == "device":
+            raise OpenGlottalHipError("engine='device': this detector, model or video cannot take the device engine (gated_engine_for)")
     if detector is not None:
         detector.reset()
     out = []

@@ -1,5 +1,6 @@
 """Helper module of the classical-family tests (tests/test_classic_host.py, tests/test_gpu_classic_*.py): the named masks of the blob
-filter, an independent scipy statement of the filter, and a numpy statement of the Otsu rule."""
+filter, the hard masks at any side (spiral, serpentine, nested rings, ...) and the window cases built from them, an independent
+scipy statement of the filter, the contour statement the fixture's generator uses, and a numpy statement of the Otsu rule."""
 import numpy as np
 
 NS = (1, 2, 3, 8)
@@ -7,6 +8,126 @@ NS = (1, 2, 3, 8)
 
 def _canvas(h, w):
     return np.zeros((h, w), np.uint8)
+
+
+def spiral(S):
+    """A square spiral walking inward from (0, 0), one pixel wide with a one-pixel channel: ONE 8-connected component (one long
+    union chain) whose background is ONE 4-connected component, open to the border at (1, 0) -- no hole.  The walker turns right
+    when the next pixel is outside or set, or the one after it is set (that keeps the channel); it stops when it cannot move
+    after a turn (at an even side the last steps close a 2 x 2 end in the centre).  S * (S + 2) / 2 pixels at an even side."""
+    m = _canvas(S, S)
+
+    def can(y, x, dy, dx):
+        ny, nx, ay, ax = y + dy, x + dx, y + 2 * dy, x + 2 * dx
+        if not (0 <= ny < S and 0 <= nx < S) or m[ny, nx]:
+            return False
+        return not (0 <= ay < S and 0 <= ax < S and m[ay, ax])
+
+    y = x = 0
+    dy, dx = 0, 1
+    m[0, 0] = 1
+    while True:
+        if not can(y, x, dy, dx):
+            dy, dx = dx, -dy
+            if not can(y, x, dy, dx):
+                return m
+        y, x = y + dy, x + dx
+        m[y, x] = 1
+
+
+def hard_masks(S):
+    """(name, mask u8 {0,1}) pairs at side S, the shapes a union-find labelling is slowest or most contended on; each also
+    transposed (``-T``), rotated by 180 degrees (``-rot``) and inverted (``-inv``)."""
+    yy, xx = np.indices((S, S))
+    base = [("spiral", spiral(S))]
+    serp = _canvas(S, S)                   # full rows on even lines, joined alternately at the right and the left end
+    serp[0::2] = 1
+    for y in range(1, S - 1, 2):
+        serp[y, S - 1 if (y // 2) % 2 == 0 else 0] = 1
+    base.append(("serpentine", serp))
+    rings = _canvas(S, S)                  # concentric one-pixel square rings two apart: a hole in a hole in a hole
+    for o in range(0, (S + 1) // 2, 2):
+        rings[o, o:S - o] = rings[S - 1 - o, o:S - o] = 1
+        rings[o:S - o, o] = rings[o:S - o, S - 1 - o] = 1
+    base.append(("rings", rings))
+    base.append(("specks", ((yy % 2 == 0) & (xx % 2 == 0)).astype(np.uint8)))       # key 0 each: the tie rule alone orders them
+    base.append(("stairs", ((yy + xx) % 3 == 0).astype(np.uint8)))                  # chains 8-connected by diagonal steps only
+    base.append(("checkerboard", ((yy + xx) % 2).astype(np.uint8)))
+    comb = _canvas(S, S)
+    comb[S - 2, 1:S - 1] = 1
+    comb[0:S - 2, 1:S - 1:2] = 1
+    base.append(("comb", comb))
+    out = []
+    for name, m in base:
+        out += [(name, m), (name + "-T", np.ascontiguousarray(m.T)), (name + "-rot", np.ascontiguousarray(m[::-1, ::-1])),
+                (name + "-inv", (1 - m).astype(np.uint8))]
+    return out
+
+
+WINDOW_FRAME = (40, 56)                    # H, W of the frames of the window cases
+WINDOW_AT = (4, 11)                        # the 33 x 33 hard masks sit at rows 4:37, columns 11:44
+WINDOW_BOXES = (
+    (11, 4, 44, 37), (0, 0, 56, 40),                                             # the square, the frame
+    (0, 0, 30, 20), (26, 0, 56, 20), (0, 20, 30, 40), (26, 20, 56, 40),          # the four corners: two frame edges each
+    (0, 10, 30, 30), (20, 0, 40, 40),                                            # one edge; top and bottom
+    (12, 5, 13, 36), (11, 20, 44, 21), (20, 20, 21, 21),                         # one column, one row, one pixel
+    (10, 3, 45, 38), (12, 5, 43, 36),                                            # one pixel larger, one pixel smaller than the square
+    (-45, -36, -12, -3),                                                         # counted from the far edge
+    (30, 30, 90, 70),                                                            # leaves the frame
+)
+
+
+def window_cases():
+    """(name, mask [40,56] u8 {0,1}) pairs: every 33 x 33 hard mask inside the frame, once with nothing set outside the square and
+    once (``+dark``) with EVERYTHING outside it set -- whatever of that lies outside a box must be ignored."""
+    H, W = WINDOW_FRAME
+    y0, x0 = WINDOW_AT
+    out = []
+    for name, m in hard_masks(33):
+        for dark in (0, 1):
+            f = np.full((H, W), dark, np.uint8)
+            f[y0:y0 + 33, x0:x0 + 33] = m
+            out.append((name + ("+dark" if dark else ""), f))
+    return out
+
+
+def roi_of(box, H, W):
+    """The pixels of ``m[y1:y2, x1:x2]`` (Python slices) as a bool [H,W]; nothing for ``None``."""
+    roi = np.zeros((H, W), bool)
+    if box is not None:
+        roi[box[1]:box[3], box[0]:box[2]] = True
+    return roi
+
+
+LADDER_SIDES = (32, 64, 128, 256)          # the worst case climbs these, smallest first
+LADDER_MASKS = ("spiral", "spiral-T", "serpentine", "rings")
+LADDER_LIMIT_S = 2.0                       # no rung is launched whose predicted time exceeds this
+
+
+def ladder_masks(S):
+    by = dict(hard_masks(S))
+    return [(name, by[name]) for name in LADDER_MASKS]
+
+
+def ladder_prediction(times):
+    """The time to expect of the next rung (the side doubles: four times the pixels) from the rungs already run: the last time
+    times the last growth factor, at least 4."""
+    growth = times[-1] / times[-2] if len(times) > 1 and times[-2] > 0 else 4.0
+    return times[-1] * max(4.0, growth)
+
+
+_SCIPY = {}
+
+
+def scipy_blobs_cached(mask, n):
+    """``scipy_blobs`` computed once per (mask, n) and shared among the tests of a run; the arrays are read-only."""
+    m = np.ascontiguousarray(mask, dtype=np.uint8)
+    key = (m.tobytes(), m.shape, n)
+    if key not in _SCIPY:
+        out, area = scipy_blobs(m, n)
+        out.setflags(write=False)
+        _SCIPY[key] = (out, area)
+    return _SCIPY[key]
 
 
 def named_masks():
@@ -36,29 +157,10 @@ def named_masks():
     out.append(("corner-touch", sq))
     cb = (np.indices((10, 11)).sum(0) % 2).astype(np.uint8)
     out.append(("checkerboard", cb))
-    sp = _canvas(21, 21)                   # a square spiral, one pixel wide: one long union chain
-    y = x = 0
-    dy, dx = 0, 1
-    lo_y, hi_y, lo_x, hi_x = 0, 20, 0, 20
-    sp[0, 0] = 1
-    for _ in range(400):
-        ny, nx = y + dy, x + dx
-        if not (lo_y <= ny <= hi_y and lo_x <= nx <= hi_x):
-            if (dy, dx) == (0, 1):
-                lo_y += 2
-            elif (dy, dx) == (1, 0):
-                hi_x -= 2
-            elif (dy, dx) == (0, -1):
-                hi_y -= 2
-            else:
-                lo_x += 2
-            dy, dx = dx, -dy
-            ny, nx = y + dy, x + dx
-            if not (lo_y <= ny <= hi_y and lo_x <= nx <= hi_x):
-                break
-        y, x = ny, nx
-        sp[y, x] = 1
-    out.append(("spiral", sp))
+    top = _canvas(21, 21)                  # what a spiral walker that never turns leaves: the top row
+    top[0, :] = 1
+    out.append(("top-row", top))
+    out.append(("spiral", spiral(21)))
     comb = _canvas(10, 15)                 # teeth up to the top border: the pockets between them are open, not holes
     comb[8, 1:14] = 1
     comb[0:8, 1:14:2] = 1
@@ -148,6 +250,36 @@ def scipy_blobs(mask, n):
     order = sorted(range(1, k + 1), key=lambda l: (key[l], first[l]), reverse=True)[:n]      # ties: the later first pixel wins
     out = np.isin(lab, order)
     return (out * 255).astype(np.uint8), int(out.sum())
+
+
+_CONTOURS = {}
+
+
+def contour_blobs(mask, n):
+    """The blob filter as the reference's ``_nblobs`` composes it, over the cv2 stand-ins of tests/golden/gen_golden_vft.py:
+    external contours by border following, sorted by the shoelace area (stable, largest first), the first n filled as polygons.
+    -> (mask u8 {0,255}, area).  Pure Python: for sides up to 64."""
+    import importlib.util
+    import os
+    import sys
+
+    if "module" not in _CONTOURS:
+        path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gen_golden_vft.py")
+        spec = importlib.util.spec_from_file_location("gen_golden_vft", path)
+        _CONTOURS["module"] = importlib.util.module_from_spec(spec)
+        keep = list(sys.path)                                  # the generator prepends its own directories: not for the suite
+        spec.loader.exec_module(_CONTOURS["module"])
+        sys.path[:] = keep
+    G = _CONTOURS["module"]
+    m = np.ascontiguousarray(mask, dtype=np.uint8)
+    H, W = m.shape
+    key = (m.tobytes(), m.shape)
+    if key not in _CONTOURS:
+        _CONTOURS[key] = sorted(G.find_external(m), key=G.contour_area, reverse=True)       # the order does not depend on n
+    out = np.zeros((H, W), np.uint8)
+    for c in _CONTOURS[key][:n]:
+        out[G.polygon_fill([tuple(v) for v in c.reshape(-1, 2)], H, W)] = 255
+    return out, int((out > 0).sum())
 
 
 def otsu_numpy(hist):

@@ -105,6 +105,13 @@ def find_external(m):
     return found[::-1]
 
 
+def contour_area(c):
+    """The shoelace formula over a contour as ``find_external`` returns it."""
+    p = c.reshape(-1, 2).astype(np.int64)
+    q = np.roll(p, -1, axis=0)
+    return abs(int((p[:, 0] * q[:, 1] - q[:, 0] * p[:, 1]).sum())) / 2.0
+
+
 def install_cv2(blur):
     import gen_golden as G
     from openglottal_amd.utils import bgr_to_gray_numpy
@@ -116,11 +123,6 @@ def install_cv2(blur):
     cv2.absdiff = lambda a, b: np.abs(a - b)
     cv2.GaussianBlur = blur
     cv2.findContours = lambda m, mode, method: (find_external(m), None)
-
-    def contour_area(c):
-        p = c.reshape(-1, 2).astype(np.int64)
-        q = np.roll(p, -1, axis=0)
-        return abs(int((p[:, 0] * q[:, 1] - q[:, 0] * p[:, 1]).sum())) / 2.0
 
     def draw_contours(img, contours, idx, color, thickness):
         assert idx == -1 and thickness == cv2.FILLED

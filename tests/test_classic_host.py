@@ -137,11 +137,85 @@ def test_what_the_named_masks_are_there_for():
     comb = masks["comb"]
     assert CL.blobs_host(comb, 1)[1] == int(comb.sum())              # open pockets are not holes
     assert CL.blobs_host(masks["spiral"], 1)[1] == int(masks["spiral"].sum())
+    assert CL.blobs_host(masks["top-row"], 1)[1] == int(masks["top-row"].sum()) == 21
+    # the spiral IS one: it turns (pixels below row 0), it is one 8-connected chain, its channel is one 4-connected background open
+    # to the border (no hole), and it has the pixel count of a spiral at every side the tests use
+    from scipy import ndimage
+
+    for S, count in ((21, 241), (64, 2112), (128, 8320), (256, 33024)):
+        sp = K.spiral(S)
+        assert int(sp.sum()) == count and int(sp[1:].sum()) == count - S, S
+        assert ndimage.label(sp, structure=np.ones((3, 3), int))[1] == 1, S
+        assert ndimage.label(sp == 0)[1] == 1 and sp[1, 0] == 0, S
+        assert dict(K.hard_masks(S))["spiral"].tobytes() == sp.tobytes()
+    assert np.array_equal(masks["spiral"], K.spiral(21)) and int(masks["spiral"][1:].sum()) == 220
     spk, area = CL.blobs_host(masks["specks+blob"], 2)
     assert area == 17 and spk[13, 15] == 255 and spk[0, 3] == 0      # key 0 ties: the speck that comes last in raster order
     tie, area = CL.blobs_host(masks["key-tie"], 1)
     assert area == 12 and tie[8, 13] == 255 and tie[2, 2] == 0       # equal keys: the later rectangle
     assert CL.blobs_host(masks["empty"], 2)[1] == 0 and CL.blobs_host(masks["full"], 2)[1] == 99
+
+
+@pytest.mark.parametrize("S", (33, 64, 96, 128, 256))
+def test_blob_filter_equals_scipy_on_the_hard_masks(S):
+    """Spiral, serpentine, nested rings, S*S/4 specks of key 0, diagonal-only chains, checkerboard, comb; each also transposed,
+    rotated and inverted."""
+    masks = K.hard_masks(S)
+    assert len(masks) == 28 and len({name for name, _ in masks}) == 28 and all(m.shape == (S, S) and m.max() <= 1 for _, m in masks)
+    for name, m in masks:
+        for n in K.NS:
+            want_mask, want_area = K.scipy_blobs_cached(m, n)
+            got_mask, got_area = CL.blobs_host(m, n)
+            assert got_area == want_area and np.array_equal(got_mask, want_mask), (name, S, n, got_area, want_area)
+            assert CL.blobs_host(m * 255, n, want_mask=False) == (None, want_area)
+    by = dict(masks)
+    half = (S + 1) // 2
+    assert CL.blobs_host(by["rings"], 1)[1] == S * S                                  # a hole in a hole in a hole: all filled
+    assert CL.blobs_host(by["spiral"], 8)[1] == int(by["spiral"].sum())               # one blob without a hole
+    assert CL.blobs_host(by["serpentine"], 8)[1] == int(by["serpentine"].sum()) == half * S + (S - 1) // 2
+    spk, area = CL.blobs_host(by["specks"], 8)                                        # half * half blobs of key 0: the last eight
+    assert int(by["specks"].sum()) == half * half and area == 8
+    assert np.array_equal(np.flatnonzero(spk), np.flatnonzero(by["specks"])[-8:])
+    assert CL.blobs_host(by["stairs"], 1)[1] < int(by["stairs"].sum())                # separate diagonals, not one blob
+    cb = by["checkerboard"]                                                           # one blob; every inner gap is a hole
+    open_gaps = (cb[0] == 0).sum() + (cb[-1] == 0).sum() + (cb[1:-1, 0] == 0).sum() + (cb[1:-1, -1] == 0).sum()
+    assert CL.blobs_host(cb, 1)[1] == S * S - int(open_gaps)                          # all but the gaps on the border
+    assert CL.blobs_host(by["comb"], 1)[1] == int(by["comb"].sum())                   # open pockets
+
+
+@pytest.mark.parametrize("S", (33, 64))
+def test_blob_filter_equals_the_contour_statement_on_the_hard_masks(S):
+    """Three statements by three algorithms: union-find over 2x2 windows (the library), scipy's labelling, and border following +
+    shoelace + polygon fill composed as the reference's ``_nblobs`` (tests/golden/gen_golden_vft.py)."""
+    for name, m in K.hard_masks(S):
+        for n in (1, 8):
+            c_mask, c_area = K.contour_blobs(m, n)
+            s_mask, s_area = K.scipy_blobs_cached(m, n)
+            h_mask, h_area = CL.blobs_host(m, n)
+            assert c_area == s_area == h_area, (name, S, n, c_area, s_area, h_area)
+            assert np.array_equal(c_mask, s_mask) and np.array_equal(c_mask, h_mask), (name, S, n)
+
+
+def test_window_cases_through_the_host_composition():
+    """Every 33 x 33 hard mask inside a 40 x 56 frame, bright and dark outside the square, under boxes that touch zero, one and two
+    frame edges, a column, a row, a pixel, negative coordinates and a box leaving the frame: ``guided_vft_host`` at beta 1 and
+    threshold 128 (the cut stays at 128; the frame is 0 where the mask is set and 255 elsewhere) equals scipy on ``mask & roi``."""
+    H, W = K.WINDOW_FRAME
+    boxes = list(K.WINDOW_BOXES)
+    rois = [K.roi_of(b, H, W) for b in boxes]
+    assert len(boxes) == 15 and all(r.any() for r in rois)
+    checked = 0
+    for name, m in K.window_cases():
+        frame = np.where(m > 0, 0, 255).astype(np.uint8)
+        for n in (1, 2, 8):
+            masks, areas, ths, last = CL.guided_vft_host([frame] * len(boxes), boxes, 128.0, beta=1.0, n_components=n)
+            assert last == 128.0 and (ths == 128.0).all()
+            for i, roi in enumerate(rois):
+                want_mask, want_area = K.scipy_blobs_cached(m * roi, n)
+                assert areas[i] == want_area and np.array_equal(masks[i], want_mask), (name, n, boxes[i], int(areas[i]), want_area)
+                assert not masks[i][~roi].any()
+                checked += 1
+    assert checked == 56 * 3 * 15
 
 
 def test_blobs_host_refuses_bad_arguments():

@@ -170,6 +170,14 @@ GATED_PROTOTYPES = {
     "og_gated_stream_frames_u8": (C.c_int, _GATED_STREAM),
 }
 
+# name -> (restype, argtypes); the complete export list of openglottal_hip_classic_tiled.h (the tiled blob filter: frames of any size)
+TILED_PROTOTYPES = {
+    "og_classic_set_tiled": (C.c_int, [C.c_void_p, C.c_int]),
+    "og_classic_tiled_limit": (C.c_longlong, [C.c_int]),
+    "og_blobs_host_any": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "og_classic_plan_tiled": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
+}
+
 
 def lib() -> C.CDLL:
     """Load the HIP library once; fail loudly if it is not built."""
@@ -192,7 +200,7 @@ def lib() -> C.CDLL:
         except OSError as e:  # missing libamdhip64 etc.
             raise OpenGlottalHipError(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in (list(PROTOTYPES.items()) + list(CROP_PROTOTYPES.items()) + list(CLASSIC_PROTOTYPES.items())
-                                  + list(GATED_PROTOTYPES.items())):
+                                  + list(GATED_PROTOTYPES.items()) + list(TILED_PROTOTYPES.items())):
             fn = getattr(l, name)  # AttributeError if a symbol is missing: also loud
             fn.restype = res
             fn.argtypes = args

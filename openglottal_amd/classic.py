@@ -45,15 +45,27 @@ def boxes_array(boxes, B: int, W: int, H: int) -> np.ndarray:
     return np.array([normalize_box(b, W, H) for b in boxes], np.int32).reshape(B, 4)
 
 
-class Classic:
-    """One ``og_classic`` handle.  The device is the current one at the first call that touches it."""
+TILED_MODES = {"off": 0, "auto": 1, "always": 2}
 
-    def __init__(self, beta: float = 0.7, percentile: float = 30, n_components: int = 2, chunk: int = 128):
+
+def _tiled_mode(tiled) -> int:
+    if tiled not in TILED_MODES:
+        raise OpenGlottalHipError(f"tiled must be one of {sorted(TILED_MODES)}, got {tiled!r}")
+    return TILED_MODES[tiled]
+
+
+class Classic:
+    """One ``og_classic`` handle.  The device is the current one at the first call that touches it.  ``tiled``
+    (include/openglottal_hip_classic_tiled.h): ``"off"`` keeps the one-workgroup blob filter and its 65 536-pixel limit, ``"auto"``
+    takes the tiled filter above that size, ``"always"`` at every size."""
+
+    def __init__(self, beta: float = 0.7, percentile: float = 30, n_components: int = 2, chunk: int = 128, tiled: str = "off"):
         self._h = lib().og_classic_create()
         if not self._h:
             raise OpenGlottalHipError("og_classic_create failed")
         self.reset(beta, percentile, n_components)
         self.set_chunk(chunk)
+        self.set_tiled(tiled)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -69,6 +81,10 @@ class Classic:
     def set_chunk(self, chunk: int) -> None:
         check(lib().og_classic_set_chunk(self._h, int(chunk)), "og_classic_set_chunk")
         self.chunk = int(chunk)
+
+    def set_tiled(self, tiled: str) -> None:
+        check(lib().og_classic_set_tiled(self._h, _tiled_mode(tiled)), "og_classic_set_tiled")
+        self.tiled = tiled
 
     def sync(self) -> None:
         check(lib().og_classic_sync(self._h), "og_classic_sync")
@@ -175,7 +191,10 @@ def blobs_host(mask, n: int, want_mask: bool = True):
     H, W = m.shape
     out = np.empty((H, W), np.uint8) if want_mask else None
     area = C.c_int32()
-    check(lib().og_blobs_host(ptr(m), H, W, int(n), ptr(out), C.byref(area)), "og_blobs_host")
+    if H * W > lib().og_classic_limit(0):
+        check(lib().og_blobs_host_any(ptr(m), H, W, int(n), ptr(out), C.byref(area)), "og_blobs_host_any")
+    else:
+        check(lib().og_blobs_host(ptr(m), H, W, int(n), ptr(out), C.byref(area)), "og_blobs_host")
     return out, area.value
 
 
@@ -201,13 +220,17 @@ def guided_vft_host(frames, boxes, thresh: float, beta: float = 0.7, percentile:
     return masks, np.array(areas, np.int32), np.array(ths, np.float64), thresh
 
 
-def plan(B: int, H: int, W: int, channels: int, chunk: int = 128):
+def plan(B: int, H: int, W: int, channels: int, chunk: int = 128, tiled: str = "off"):
     """Dry run of the streamed guided-VFT pass: ``(records, workspace_bytes)``; a record is a dict of the plan line's fields."""
     out = C.create_string_buffer(1 << 20)
     ws = C.c_longlong()
-    n = lib().og_classic_plan(B, H, W, channels, chunk, out, len(out), C.byref(ws))
+    mode = _tiled_mode(tiled)
+    if mode:
+        n = lib().og_classic_plan_tiled(B, H, W, channels, chunk, mode, out, len(out), C.byref(ws))
+    else:
+        n = lib().og_classic_plan(B, H, W, channels, chunk, out, len(out), C.byref(ws))
     if n < 0:
-        check(n, "og_classic_plan")
+        check(n, "og_classic_plan_tiled" if mode else "og_classic_plan")
     names = ("kernel", "gx", "gy", "gz", "block", "lds", "workspace", "counters", "writes")
     recs = []
     for line in out.value.decode().splitlines():

@@ -3,8 +3,11 @@
 // the workspace of ONE micro-batch, two pinned host slots.  Per micro-batch of the guided-VFT pass: k_box_hist (ROI histograms),
 // k_vft_thresholds (percentiles, then the recurrence in frame order from the handle's running threshold) and k_blobs (raw mask,
 // hole fill, labelling, keys, top-n, paint, count: one workgroup per frame).  Everything is ordered by the one stream, so the
-// threshold carried from micro-batch to micro-batch needs nothing else.
+// threshold carried from micro-batch to micro-batch needs nothing else.  A handle in tiled mode (og_classic_set_tiled,
+// include/openglottal_hip_classic_tiled.h) sends frames above 65 536 pixels, or all, through the k_tblob_* launches in k_blobs' place:
+// many workgroups per frame, a launch boundary wherever they must see each other's results (classic_tblob_batch).
 #include "../../include/openglottal_hip_classic.h"
+#include "../../include/openglottal_hip_classic_tiled.h"
 
 struct og_classic {
     int device = -1;
@@ -12,11 +15,12 @@ struct og_classic {
     hipStream_t stream = nullptr;
     double beta = 0.7, percentile = 30.0;
     int n_comp = 2, chunk = 128;
+    int tiled = 0;   // og_classic_set_tiled: 0 off, 1 auto, 2 always
     bool seeded = false;
     double* d_state = nullptr;   // the running threshold
     // workspace of one micro-batch
     size_t cap_nb = 0, cap_px = 0, cap_in = 0;   // frames; pixels and source bytes of the whole micro-batch
-    bool cap_mask = false;
+    bool cap_mask = false, cap_sel = false;
     uint8_t* d_in = nullptr;
     uint8_t* d_mask = nullptr;
     int* d_la = nullptr;
@@ -27,6 +31,7 @@ struct og_classic {
     int32_t* d_cut = nullptr;
     int32_t* d_T = nullptr;
     int32_t* d_area = nullptr;
+    int32_t* d_sel = nullptr;   // the tiled blob filter: the roots taken per frame
     struct Slot {
         uint8_t* h_in = nullptr;
         uint8_t* h_mask = nullptr;
@@ -43,13 +48,24 @@ inline bool og_skip_device(const og_classic* h) { return !h || !h->ready; }
 namespace {
 
 constexpr long long kClassicMaxPixels = 1ll << 16;   // 256 x 256: the largest frame k_blobs has been measured on (DESIGN section 15)
+// the tiled blob filter (DESIGN section 18): the largest frame whose worst-case ladder has been launched and timed
+constexpr long long kTiledMaxPixels = 1ll << 22;   // 2048 x 2048
 constexpr int kClassicMaxChunk = 1024;
 constexpr long long kClassicUploadBytes = 64ll << 20;
 
 // bytes of device workspace per frame of a micro-batch (the header's MEMORY paragraph)
-long long classic_frame_bytes(int H, int W, int ch, bool with_in, bool with_mask) {
+long long classic_frame_bytes(int H, int W, int ch, bool with_in, bool with_mask, bool tiled = false) {
     const long long HW = (long long)H * W;
-    return (with_in ? HW * ch : 0) + (with_mask ? HW : 0) + 8 * HW + 1024 + 16 + 8 + 4 + 4 + 4;
+    return (with_in ? HW * ch : 0) + (with_mask ? HW : 0) + 8 * HW + 1024 + 16 + 8 + 4 + 4 + 4 + (tiled ? 4 * kSelWords : 0);
+}
+
+// whether a frame of H x W goes through the tiled blob filter in this mode
+bool classic_tiled(int mode, int H, int W) { return mode == 2 || (mode == 1 && (long long)H * W > kClassicMaxPixels); }
+long long classic_max_pixels(int mode) { return mode ? kTiledMaxPixels : kClassicMaxPixels; }
+// blocks per frame of k_box_hist: kHistBlocks up to 65 536 pixels, growing with the frame in the tiled modes
+int classic_hist_blocks(int mode, int H, int W) {
+    const long long HW = (long long)H * W;
+    return (mode && HW > kClassicMaxPixels) ? (int)(kHistBlocks * ((HW + kClassicMaxPixels - 1) / kClassicMaxPixels)) : kHistBlocks;
 }
 
 int classic_chunk(int chunk, int H, int W, int ch) {
@@ -60,7 +76,7 @@ int classic_chunk(int chunk, int H, int W, int ch) {
 int check_classic(og_classic* h, int B, int H, int W, int ch) {
     if (!h) return fail(OG_EINVAL, "null handle");
     if (B < 0 || H <= 0 || W <= 0) return fail(OG_EINVAL, "bad B/H/W");
-    if ((long long)H * W > kClassicMaxPixels) return fail(OG_EINVAL, "H*W above " + std::to_string(kClassicMaxPixels) + " pixels");
+    if ((long long)H * W > classic_max_pixels(h->tiled)) return fail(OG_EINVAL, "H*W above " + std::to_string(classic_max_pixels(h->tiled)) + " pixels");
     if (ch != 1 && ch != 3) return fail(OG_EINVAL, "channels must be 1 (gray) or 3 (BGR)");
     return OG_OK;
 }
@@ -75,13 +91,13 @@ int classic_ready(og_classic* h) {
 }
 
 void classic_free_ws(og_classic* h) {
-    void* dev[] = {h->d_in, h->d_mask, h->d_la, h->d_lb, h->d_hist, h->d_boxes, h->d_thresh, h->d_cut, h->d_T, h->d_area};
+    void* dev[] = {h->d_in, h->d_mask, h->d_la, h->d_lb, h->d_hist, h->d_boxes, h->d_thresh, h->d_cut, h->d_T, h->d_area, h->d_sel};
     for (void* p : dev)
         if (p) (void)hipFree(p);
     h->d_in = h->d_mask = nullptr;
     h->d_la = h->d_lb = nullptr;
     h->d_hist = nullptr;
-    h->d_boxes = h->d_cut = h->d_T = h->d_area = nullptr;
+    h->d_boxes = h->d_cut = h->d_T = h->d_area = h->d_sel = nullptr;
     h->d_thresh = nullptr;
     for (auto& s : h->slots) {
         void* host[] = {s.h_in, s.h_mask, s.h_boxes, s.h_area, s.h_T, s.h_thresh};
@@ -95,19 +111,22 @@ void classic_free_ws(og_classic* h) {
         s.b0 = -1;
     }
     h->cap_nb = h->cap_px = h->cap_in = 0;
-    h->cap_mask = false;
+    h->cap_mask = h->cap_sel = false;
 }
 
 // the workspace of one micro-batch of nb frames; `in`: bytes of source frames per frame (0: resident frames), `host`: pinned slots too.
 // Capacities are kept in BYTES of the micro-batch (nb * pixels, nb * in), never as separate maxima of nb and of the frame size: a
 // handle that has seen many small frames and then a few large ones holds the larger of the two micro-batches, not their product.
 int classic_ensure(og_classic* h, int nb, int H, int W, size_t in, bool want_mask, bool host) {
+    const bool want_sel = classic_tiled(h->tiled, H, W);
     const size_t px = (size_t)nb * H * W, inb = (size_t)nb * in;
     const bool have_host = h->slots[0].ev_out != nullptr;
-    if ((size_t)nb <= h->cap_nb && px <= h->cap_px && inb <= h->cap_in && (!want_mask || h->cap_mask) && (!host || have_host)) return OG_OK;
+    if ((size_t)nb <= h->cap_nb && px <= h->cap_px && inb <= h->cap_in && (!want_mask || h->cap_mask) && (!want_sel || h->cap_sel) &&
+        (!host || have_host))
+        return OG_OK;
     HIPCHK(hipStreamSynchronize(h->stream));
     const size_t n = std::max((size_t)nb, h->cap_nb), p = std::max(px, h->cap_px), i = std::max(inb, h->cap_in);
-    const bool m = want_mask || h->cap_mask, hs = host || have_host;
+    const bool m = want_mask || h->cap_mask, hs = host || have_host, sl = want_sel || h->cap_sel;
     classic_free_ws(h);
     auto dev = [&](void** q, size_t bytes) { return hipMalloc(q, bytes ? bytes : 1); };
     hipError_t e = hipSuccess;
@@ -121,6 +140,7 @@ int classic_ensure(og_classic* h, int nb, int H, int W, size_t in, bool want_mas
     if (e == hipSuccess) e = dev((void**)&h->d_cut, n * 4);
     if (e == hipSuccess) e = dev((void**)&h->d_T, n * 4);
     if (e == hipSuccess) e = dev((void**)&h->d_area, n * 4);
+    if (sl && e == hipSuccess) e = dev((void**)&h->d_sel, n * 4 * kSelWords);
     for (auto& s : h->slots) {
         if (!hs) break;
         if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_in, i ? i : 1, hipHostMallocDefault);
@@ -139,6 +159,7 @@ int classic_ensure(og_classic* h, int nb, int H, int W, size_t in, bool want_mas
     h->cap_px = p;
     h->cap_in = i;
     h->cap_mask = m;
+    h->cap_sel = sl;
     return OG_OK;
 }
 
@@ -151,12 +172,14 @@ struct ClassicWs {
     double* thresh;
     int32_t* cut;
     int32_t* T;
+    int32_t* sel = nullptr;   // tiled blob filter only
+    int mode = 0;             // og_classic_set_tiled
 };
-ClassicWs classic_ws(const og_classic* h) { return {h->d_hist, h->d_la, h->d_lb, h->d_state, h->d_thresh, h->d_cut, h->d_T}; }
+ClassicWs classic_ws(const og_classic* h) { return {h->d_hist, h->d_la, h->d_lb, h->d_state, h->d_thresh, h->d_cut, h->d_T, h->d_sel, h->tiled}; }
 
-int enqueue_box_hist(hipStream_t st, int ch, const uint8_t* src, int nb, int H, int W, const int32_t* boxes, uint32_t* hist) {
+int enqueue_box_hist(hipStream_t st, int mode, int ch, const uint8_t* src, int nb, int H, int W, const int32_t* boxes, uint32_t* hist) {
     if (!g_plan) HIPCHK(hipMemsetAsync(hist, 0, (size_t)nb * 1024, st));
-    const dim3 grid((unsigned)kHistBlocks, (unsigned)nb);
+    const dim3 grid((unsigned)classic_hist_blocks(mode, H, W), (unsigned)nb);
     if (ch == 3)
         OG_LAUNCH(k_box_hist<3>, grid, dim3(256), 0, st, src, H, W, boxes, hist);
     else
@@ -164,12 +187,43 @@ int enqueue_box_hist(hipStream_t st, int ch, const uint8_t* src, int nb, int H, 
     return OG_OK;
 }
 
+// the tiled blob filter over one micro-batch (the launch list of og_kernels.hpp): every launch boundary is a hand-off between the
+// workgroups of a frame.  Grids: tiles x frames for the tile kernels, pixels x frames for the rest.
+int classic_tblob_batch(hipStream_t st, const ClassicWs& ws, int n_comp, int ch, const uint8_t* src, int nb, int H, int W, const int32_t* boxes,
+                        uint8_t* mask, int32_t* area) {
+    const long long HW = (long long)H * W;
+    const unsigned tiles = (unsigned)(((W + kBlobTile - 1) / kBlobTile) * (long long)((H + kBlobTile - 1) / kBlobTile));
+    const dim3 gt(tiles, (unsigned)nb), gp((unsigned)((HW + 255) / 256), (unsigned)nb);
+    const dim3 gk((unsigned)(((long long)(H + 1) * (W + 1) + 255) / 256), (unsigned)nb);
+    plan_need((long long)nb * HW * 8 + (long long)nb * 4 * kSelWords, 0);   // the two label arrays and the roots taken, per frame
+    if (ch == 3)
+        OG_LAUNCH(k_tblob_background<3>, gt, dim3(kTileThreads), 0, st, src, H, W, boxes, ws.cut, ws.la);
+    else
+        OG_LAUNCH(k_tblob_background<1>, gt, dim3(kTileThreads), 0, st, src, H, W, boxes, ws.cut, ws.la);
+    OG_LAUNCH(k_tblob_seams<false>, gt, dim3(kTileThreads), 0, st, H, W, boxes, ws.la, ws.lb);
+    OG_LAUNCH(k_tblob_flatten, gp, dim3(256), 0, st, H, W, boxes, ws.la);
+    OG_LAUNCH(k_tblob_border, gp, dim3(256), 0, st, H, W, boxes, ws.la);
+    OG_LAUNCH(k_tblob_fill, gt, dim3(kTileThreads), 0, st, H, W, boxes, ws.la, ws.lb);
+    OG_LAUNCH(k_tblob_seams<true>, gt, dim3(kTileThreads), 0, st, H, W, boxes, ws.la, ws.lb);
+    OG_LAUNCH(k_tblob_flatten, gp, dim3(256), 0, st, H, W, boxes, ws.lb);
+    OG_LAUNCH(k_tblob_keys, gk, dim3(256), 0, st, H, W, boxes, ws.la, ws.lb);
+    OG_LAUNCH(k_tblob_select, dim3((unsigned)nb), dim3(kBlobThreads), 0, st, H, W, boxes, n_comp, ws.la, ws.lb, ws.sel);
+    if (!g_plan) HIPCHK(hipMemsetAsync(area, 0, (size_t)nb * 4, st));
+    OG_LAUNCH(k_tblob_paint, gp, dim3(256), 0, st, H, W, boxes, ws.lb, ws.sel, mask, area);
+    if (g_plan) {
+        plan_write("mask", mask, (long long)nb * HW);
+        plan_write("area", area, (long long)nb * 4);
+    }
+    return OG_OK;
+}
+
 // one micro-batch of nb resident frames of the guided-VFT pass; thresholds and cuts are left in ws
 int classic_vft_batch(hipStream_t st, const ClassicWs& ws, double beta, double q, int n_comp, int ch, const uint8_t* src, int nb, int H, int W,
                       const int32_t* boxes, uint8_t* mask, int32_t* area) {
-    int rc = enqueue_box_hist(st, ch, src, nb, H, W, boxes, ws.hist);
+    int rc = enqueue_box_hist(st, ws.mode, ch, src, nb, H, W, boxes, ws.hist);
     if (rc) return rc;
     OG_LAUNCH(k_vft_thresholds, dim3(1), dim3(256), 0, st, ws.hist, nb, q, beta, ws.state, ws.thresh, ws.cut);
+    if (classic_tiled(ws.mode, H, W)) return classic_tblob_batch(st, ws, n_comp, ch, src, nb, H, W, boxes, mask, area);
     plan_need((long long)nb * H * W * 8, 0);   // the two label arrays of each frame
     if (ch == 3)
         OG_LAUNCH(k_blobs<3>, dim3((unsigned)nb), dim3(kBlobThreads), 0, st, src, H, W, boxes, ws.cut, n_comp, ws.la, ws.lb, mask, area);
@@ -185,7 +239,7 @@ int classic_vft_batch(hipStream_t st, const ClassicWs& ws, double beta, double q
 // one micro-batch of the Otsu pass; T is left in ws (area must be zero on entry: zeroed here)
 int classic_otsu_batch(hipStream_t st, const ClassicWs& ws, int ch, const uint8_t* src, int nb, int H, int W, const int32_t* boxes,
                        uint8_t* mask, int32_t* area) {
-    int rc = enqueue_box_hist(st, ch, src, nb, H, W, boxes, ws.hist);
+    int rc = enqueue_box_hist(st, ws.mode, ch, src, nb, H, W, boxes, ws.hist);
     if (rc) return rc;
     HIPCHK(hipMemsetAsync(area, 0, (size_t)nb * 4, st));
     OG_LAUNCH(k_otsu_thresholds, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, st, ws.hist, nb, ws.T, ws.cut);
@@ -373,8 +427,8 @@ int og_vft_step_host(double thresh, double beta, const uint32_t* hist256, double
     return OG_OK;
 }
 
-int og_blobs_host(const uint8_t* mask, int H, int W, int n_components, uint8_t* out_mask_or_null, int32_t* area) {
-    if (!mask || !area || H < 1 || W < 1 || (long long)H * W > kClassicMaxPixels) return fail(OG_EINVAL, "bad argument");
+// the body of og_blobs_host and og_blobs_host_any: H * W fits an int
+int blobs_host_impl(const uint8_t* mask, int H, int W, int n_components, uint8_t* out_mask_or_null, int32_t* area) {
     if (n_components < 1 || n_components > kBlobMax) return fail(OG_EINVAL, "n_components must be 1.." + std::to_string(kBlobMax));
     OG_ALIGN(area);
     const int N = H * W;
@@ -431,6 +485,25 @@ int og_blobs_host(const uint8_t* mask, int H, int W, int n_components, uint8_t* 
         cnt += on ? 1 : 0;
     }
     *area = cnt;
+    return OG_OK;
+}
+
+int og_blobs_host(const uint8_t* mask, int H, int W, int n_components, uint8_t* out_mask_or_null, int32_t* area) {
+    if (!mask || !area || H < 1 || W < 1 || (long long)H * W > kClassicMaxPixels) return fail(OG_EINVAL, "bad argument");
+    return blobs_host_impl(mask, H, W, n_components, out_mask_or_null, area);
+}
+
+int og_blobs_host_any(const uint8_t* mask, int H, int W, int n_components, uint8_t* out_mask_or_null, int32_t* area) {
+    if (!mask || !area || H < 1 || W < 1 || (long long)H * W > (1ll << 30)) return fail(OG_EINVAL, "bad argument");
+    return blobs_host_impl(mask, H, W, n_components, out_mask_or_null, area);
+}
+
+long long og_classic_tiled_limit(int which) { return which == 0 ? kTiledMaxPixels : which == 1 ? kBlobTile : -1; }
+
+int og_classic_set_tiled(og_classic* h, int mode) {
+    if (!h) return fail(OG_EINVAL, "null handle");
+    if (mode < 0 || mode > 2) return fail(OG_EINVAL, "tiled mode must be 0 (off), 1 (auto) or 2 (always)");
+    h->tiled = mode;
     return OG_OK;
 }
 
@@ -515,7 +588,7 @@ int og_vft_guided_init_u8(og_classic* h, const uint8_t* frames, int n, int H, in
     memcpy(s.h_in, frames + (size_t)(n - 1) * fb, fb);
     HIPCHK(hipMemcpyAsync(h->d_in, s.h_in, fb, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(h->d_boxes, s.h_boxes, 16, hipMemcpyHostToDevice, h->stream));
-    rc = enqueue_box_hist(h->stream, channels, h->d_in, 1, H, W, h->d_boxes, h->d_hist);
+    rc = enqueue_box_hist(h->stream, h->tiled, channels, h->d_in, 1, H, W, h->d_boxes, h->d_hist);
     if (!rc) {
         hipLaunchKernelGGL(k_vft_seed, dim3(1), dim3(1), 0, h->stream, h->d_hist, h->percentile, h->d_state);
         const hipError_t le = hipGetLastError();
@@ -559,19 +632,23 @@ int og_otsu_in_box_u8_dev(og_classic* h, const uint8_t* frames_dev, int B, int H
     return classic_dev_impl(h, true, frames_dev, B, H, W, channels, boxes_dev, mask_dev_or_null, area_dev, nullptr, T_dev);
 }
 
-int og_classic_plan(int B, int H, int W, int channels, int chunk, char* out, size_t cap, long long* workspace_bytes) {
+}  // extern "C"
+
+namespace {
+int classic_plan_impl(int B, int H, int W, int channels, int chunk, int mode, char* out, size_t cap, long long* workspace_bytes) {
     if (!out || cap == 0 || B < 1) return fail(OG_EINVAL, "bad argument");
     og_classic tmp;
+    tmp.tiled = mode;
     int rc = check_classic(&tmp, B, H, W, channels);
     if (rc) return rc;
     if (chunk < 1 || chunk > kClassicMaxChunk) return fail(OG_EINVAL, "chunk must be 1.." + std::to_string(kClassicMaxChunk));
     const int mb = classic_chunk(chunk, H, W, channels), cb = mb < B ? mb : B;
-    if (workspace_bytes) *workspace_bytes = (long long)cb * classic_frame_bytes(H, W, channels, true, true) + 8;
+    if (workspace_bytes) *workspace_bytes = (long long)cb * classic_frame_bytes(H, W, channels, true, true, classic_tiled(mode, H, W)) + 8;
     const uintptr_t gap = (uintptr_t)1 << 40;   // placeholder bases: nothing dereferences them in a dry run
     uint8_t* mask = (uint8_t*)(1 * gap);
     int32_t* area = (int32_t*)(2 * gap);
     const ClassicWs ws = {(uint32_t*)(3 * gap), (int*)(4 * gap), (int*)(5 * gap), (double*)(6 * gap), (double*)(7 * gap), (int32_t*)(8 * gap),
-                          (int32_t*)(9 * gap)};
+                          (int32_t*)(9 * gap), (int32_t*)(12 * gap), mode};
     Plan plan;
     plan.bases = {{"mask", mask}, {"area", area}};
     g_plan = &plan;
@@ -588,6 +665,18 @@ int og_classic_plan(int B, int H, int W, int channels, int chunk, char* out, siz
     if (txt.size() + 1 > cap) return fail(OG_EINVAL, "plan text does not fit the buffer");
     memcpy(out, txt.c_str(), txt.size() + 1);
     return (int)plan.recs.size();
+}
+}  // namespace
+
+extern "C" {
+
+int og_classic_plan(int B, int H, int W, int channels, int chunk, char* out, size_t cap, long long* workspace_bytes) {
+    return classic_plan_impl(B, H, W, channels, chunk, 0, out, cap, workspace_bytes);
+}
+
+int og_classic_plan_tiled(int B, int H, int W, int channels, int chunk, int mode, char* out, size_t cap, long long* workspace_bytes) {
+    if (mode != 1 && mode != 2) return fail(OG_EINVAL, "tiled mode must be 1 (auto) or 2 (always)");
+    return classic_plan_impl(B, H, W, channels, chunk, mode, out, cap, workspace_bytes);
 }
 
 }  // extern "C"

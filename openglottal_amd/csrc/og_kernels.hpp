@@ -5292,7 +5292,7 @@ __device__ inline int og_uf_find(int* L, int x) {
 }
 __device__ inline void og_uf_union(int* L, int a0, int b0) {
     int a = a0, b = b0;
-    for (;;) {
+    for (;;) {   // a retry continues from a parent below the one it failed on: parents only decrease, so it ends
         a = og_uf_find(L, a);
         b = og_uf_find(L, b);
         if (a == b) break;
@@ -5460,6 +5460,305 @@ __global__ __launch_bounds__(kBlobThreads) void k_blobs(const uint8_t* __restric
     if ((tid & 63) == 0 && cnt) atomicAdd(&s_cnt, cnt);
     __syncthreads();
     if (tid == 0) area[f] = s_cnt;
+}
+
+// --- the tiled blob filter (include/openglottal_hip_classic_tiled.h) ------------------------------------
+// The labelling of k_blobs spread over MANY workgroups of one frame: the frame is cut into tiles of kBlobTile x kBlobTile pixels,
+// grid (tiles of the frame, frames of the micro-batch).  What k_blobs separates with og_blob_sync is here either work of one
+// tile's workgroup on labels in LDS, or a LAUNCH BOUNDARY on the one stream: the boundary is the ordering between workgroups (and
+// between XCDs); inside a launch the label arrays are touched by element-sized agent-scope atomics only (OG_LD, OG_ST, atomicMin,
+// atomicOr, atomicAdd), and no kernel waits for another workgroup.
+// Labels are window-linear indices as in k_blobs, and within one tile the window-linear order IS the tile's raster order, so the
+// minimum of a tile component is its raster-first pixel.  After a tile's local pass every pixel is ONE step from its tile root;
+// the seam kernels then join tile roots with og_uf_union over the pixel pairs that straddle a tile edge, so a walk in global
+// memory is bounded by the tiles a component crosses, not by its pixels.
+// The launches of one micro-batch, in order: k_tblob_background (raw mask, 4-connected background of the tile -> LA),
+// k_tblob_seams<false> (LA across tile edges), k_tblob_flatten (LA), k_tblob_border (border flags), k_tblob_fill (hole fill,
+// 8-connected labelling of the filled tile -> LB), k_tblob_seams<true> (LB across edges and corners; LA zeroed for the keys),
+// k_tblob_flatten (LB), k_tblob_keys, k_tblob_select (one workgroup per frame), k_tblob_paint (mask and area, whole frame).
+constexpr int kBlobTile = 32;
+constexpr int kTileThreads = 256;
+constexpr int kSelWords = kBlobMax + 1;   // per frame: the roots taken, then how many
+
+struct OgBlobWindow {   // the window of k_blobs: the ROI grown by one pixel, cut to the frame
+    int r[4];
+    int x0, y0, ww, wh;
+    bool ok;
+};
+__device__ inline OgBlobWindow og_blob_window(const int32_t* __restrict__ boxes, int f, int H, int W) {
+    OgBlobWindow w;
+    w.ok = og_roi(boxes[f * 4], boxes[f * 4 + 1], boxes[f * 4 + 2], boxes[f * 4 + 3], H, W, w.r);
+    w.x0 = w.r[0] > 0 ? w.r[0] - 1 : 0;
+    w.y0 = w.r[1] > 0 ? w.r[1] - 1 : 0;
+    w.ww = (w.r[2] < W ? w.r[2] + 1 : W) - w.x0;
+    w.wh = (w.r[3] < H ? w.r[3] + 1 : H) - w.y0;
+    return w;
+}
+// the frame coordinates of this workgroup's tile; false when the tile misses the window (uniform over the workgroup)
+__device__ inline bool og_tile_origin(const OgBlobWindow& w, int W, int& tx0, int& ty0) {
+    const int ntx = (W + kBlobTile - 1) / kBlobTile;
+    ty0 = ((int)blockIdx.x / ntx) * kBlobTile;
+    tx0 = ((int)blockIdx.x - ((int)blockIdx.x / ntx) * ntx) * kBlobTile;
+    return w.ok && tx0 < w.x0 + w.ww && tx0 + kBlobTile > w.x0 && ty0 < w.y0 + w.wh && ty0 + kBlobTile > w.y0;
+}
+// tile-local index i -> window-linear index, or -1 outside the window
+__device__ inline int og_tile_to_window(const OgBlobWindow& w, int tx0, int ty0, int i) {
+    const int y = ty0 + i / kBlobTile - w.y0, x = tx0 + (i & (kBlobTile - 1)) - w.x0;
+    return (x >= 0 && x < w.ww && y >= 0 && y < w.wh) ? y * w.ww + x : -1;
+}
+
+// raw mask and the 4-connected background of one tile: LA[p] = -1 where set, else the window index of the tile component's first pixel
+template <int C>
+__global__ __launch_bounds__(kTileThreads) void k_tblob_background(const uint8_t* __restrict__ src, int H, int W, const int32_t* __restrict__ boxes,
+                                                                   const int32_t* __restrict__ cut, int* __restrict__ la_all) {
+    __shared__ int lab[kBlobTile * kBlobTile];
+    const int f = blockIdx.y, tid = threadIdx.x;
+    const OgBlobWindow w = og_blob_window(boxes, f, H, W);
+    int tx0, ty0;
+    if (!og_tile_origin(w, W, tx0, ty0)) return;
+    const uint8_t* frame = src + (long long)f * H * W * C;
+    int* LA = la_all + (long long)f * H * W;
+    const int c = cut[f];
+    for (int i = tid; i < kBlobTile * kBlobTile; i += kTileThreads) {   // i only increases
+        const int y = ty0 + i / kBlobTile, x = tx0 + (i & (kBlobTile - 1));
+        const bool in = og_tile_to_window(w, tx0, ty0, i) >= 0;
+        const bool on = in && x >= w.r[0] && x < w.r[2] && y >= w.r[1] && y < w.r[3] && og_gray_at<C>(frame, (long long)y * W + x) < c;
+        lab[i] = (in && !on) ? i : -1;
+    }
+    __syncthreads();
+    // (og_uf_find, og_uf_union on LDS: parents only decrease, so every walk and every retry ends)
+    for (int i = tid; i < kBlobTile * kBlobTile; i += kTileThreads) {   // i only increases
+        if (OG_LD(&lab[i]) < 0) continue;
+        if ((i & (kBlobTile - 1)) > 0 && OG_LD(&lab[i - 1]) >= 0) og_uf_union(lab, i, i - 1);
+        if (i >= kBlobTile && OG_LD(&lab[i - kBlobTile]) >= 0) og_uf_union(lab, i, i - kBlobTile);
+    }
+    __syncthreads();
+    for (int i = tid; i < kBlobTile * kBlobTile; i += kTileThreads) {   // i only increases; lab is only read from here on
+        const int p = og_tile_to_window(w, tx0, ty0, i);
+        if (p < 0) continue;
+        OG_ST(&LA[p], lab[i] < 0 ? -1 : og_tile_to_window(w, tx0, ty0, og_uf_find(lab, i)));
+    }
+}
+
+// og_uf_union over the pixel pairs that straddle this tile's left and top edge: the pixel beside, and with EIGHT the two diagonals
+// (which also cover both diagonals across a four-tile corner).  EIGHT: on LB, and LA becomes the zeroed key array; else on LA.
+template <bool EIGHT>
+__global__ __launch_bounds__(kTileThreads) void k_tblob_seams(int H, int W, const int32_t* __restrict__ boxes, int* __restrict__ la_all,
+                                                              int* __restrict__ lb_all) {
+    const int f = blockIdx.y, tid = threadIdx.x;
+    const OgBlobWindow w = og_blob_window(boxes, f, H, W);
+    int tx0, ty0;
+    if (!og_tile_origin(w, W, tx0, ty0)) return;
+    int* L = (EIGHT ? lb_all : la_all) + (long long)f * H * W;
+    if (EIGHT) {
+        int* LA = la_all + (long long)f * H * W;
+        for (int i = tid; i < kBlobTile * kBlobTile; i += kTileThreads) {   // i only increases
+            const int p = og_tile_to_window(w, tx0, ty0, i);
+            if (p >= 0) OG_ST(&LA[p], 0);
+        }
+    }
+    if (tid >= 2 * kBlobTile) return;
+    const bool left = tid < kBlobTile;   // lanes 0..T-1: the left column; T..2T-1: the top row
+    const int x = (left ? tx0 : tx0 + tid - kBlobTile) - w.x0, y = (left ? ty0 + tid : ty0) - w.y0;
+    if (x < 0 || x >= w.ww || y < 0 || y >= w.wh || (left ? x : y) == 0) return;   // outside the window, or no neighbour across the edge
+    const int p = y * w.ww + x;
+    if (OG_LD(&L[p]) < 0) return;
+    // (every og_uf_union: parents only decrease; a retry starts from a smaller parent than the one before, so it ends)
+    if (left) {
+        if (OG_LD(&L[p - 1]) >= 0) og_uf_union(L, p, p - 1);
+        if (EIGHT && y > 0 && OG_LD(&L[p - 1 - w.ww]) >= 0) og_uf_union(L, p, p - 1 - w.ww);
+        if (EIGHT && y < w.wh - 1 && OG_LD(&L[p - 1 + w.ww]) >= 0) og_uf_union(L, p, p - 1 + w.ww);
+    } else {
+        if (OG_LD(&L[p - w.ww]) >= 0) og_uf_union(L, p, p - w.ww);
+        if (EIGHT && x > 0 && OG_LD(&L[p - w.ww - 1]) >= 0) og_uf_union(L, p, p - w.ww - 1);
+        if (EIGHT && x < w.ww - 1 && OG_LD(&L[p - w.ww + 1]) >= 0) og_uf_union(L, p, p - w.ww + 1);
+    }
+}
+
+// grid (ceil(H*W / 256), nb), a lane per window pixel: every labelled pixel gets its root
+__global__ __launch_bounds__(256) void k_tblob_flatten(int H, int W, const int32_t* __restrict__ boxes, int* __restrict__ l_all) {
+    const int f = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
+    const OgBlobWindow w = og_blob_window(boxes, f, H, W);
+    if (!w.ok || p >= w.ww * w.wh) return;
+    int* L = l_all + (long long)f * H * W;
+    if (OG_LD(&L[p]) >= 0) OG_ST(&L[p], og_uf_find(L, p));   // (parents only decrease: the walk ends at a root)
+}
+
+// grid as k_tblob_flatten: border contact of a background component, the top bit of the root's own entry
+__global__ __launch_bounds__(256) void k_tblob_border(int H, int W, const int32_t* __restrict__ boxes, int* __restrict__ la_all) {
+    const int f = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
+    const OgBlobWindow w = og_blob_window(boxes, f, H, W);
+    if (!w.ok || p >= w.ww * w.wh) return;
+    const int y = p / w.ww, x = p - y * w.ww;
+    if (x != 0 && y != 0 && x != w.ww - 1 && y != w.wh - 1) return;
+    int* LA = la_all + (long long)f * H * W;
+    const int l = OG_LD(&LA[p]);
+    if (l == -1) return;
+    atomicOr((unsigned*)&LA[l & 0x7fffffff], 0x80000000u);
+}
+
+// holes join the mask; the 8-connected components of one filled tile: LB[p] = -1 where empty, else the tile component's first pixel
+__global__ __launch_bounds__(kTileThreads) void k_tblob_fill(int H, int W, const int32_t* __restrict__ boxes, int* __restrict__ la_all,
+                                                             int* __restrict__ lb_all) {
+    __shared__ int lab[kBlobTile * kBlobTile];
+    const int f = blockIdx.y, tid = threadIdx.x;
+    const OgBlobWindow w = og_blob_window(boxes, f, H, W);
+    int tx0, ty0;
+    if (!og_tile_origin(w, W, tx0, ty0)) return;
+    int* LA = la_all + (long long)f * H * W;   // only read here: another tile's workgroup may still need a root's flag
+    int* LB = lb_all + (long long)f * H * W;
+    for (int i = tid; i < kBlobTile * kBlobTile; i += kTileThreads) {   // i only increases
+        const int p = og_tile_to_window(w, tx0, ty0, i);
+        bool filled = false;
+        if (p >= 0) {
+            const int l = OG_LD(&LA[p]);
+            filled = l == -1 || OG_LD(&LA[l & 0x7fffffff]) >= 0;   // set, or background whose root never met the border
+        }
+        lab[i] = filled ? i : -1;
+    }
+    __syncthreads();
+    // (og_uf_find, og_uf_union on LDS: parents only decrease, so every walk and every retry ends)
+    for (int i = tid; i < kBlobTile * kBlobTile; i += kTileThreads) {   // i only increases
+        if (OG_LD(&lab[i]) < 0) continue;
+        const int x = i & (kBlobTile - 1);
+        if (x > 0 && OG_LD(&lab[i - 1]) >= 0) og_uf_union(lab, i, i - 1);
+        if (i >= kBlobTile) {
+            if (OG_LD(&lab[i - kBlobTile]) >= 0) og_uf_union(lab, i, i - kBlobTile);
+            if (x > 0 && OG_LD(&lab[i - kBlobTile - 1]) >= 0) og_uf_union(lab, i, i - kBlobTile - 1);
+            if (x < kBlobTile - 1 && OG_LD(&lab[i - kBlobTile + 1]) >= 0) og_uf_union(lab, i, i - kBlobTile + 1);
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < kBlobTile * kBlobTile; i += kTileThreads) {   // i only increases; lab is only read from here on
+        const int p = og_tile_to_window(w, tx0, ty0, i);
+        if (p < 0) continue;
+        OG_ST(&LB[p], lab[i] < 0 ? -1 : og_tile_to_window(w, tx0, ty0, og_uf_find(lab, i)));
+    }
+}
+
+// grid (ceil((H+1)*(W+1) / 256), nb), a lane per 2x2 window of the window padded by one background ring: keys into LA (zero on entry)
+__global__ __launch_bounds__(256) void k_tblob_keys(int H, int W, const int32_t* __restrict__ boxes, int* __restrict__ la_all,
+                                                    int* __restrict__ lb_all) {
+    const int f = blockIdx.y, q = blockIdx.x * 256 + threadIdx.x;
+    const OgBlobWindow w = og_blob_window(boxes, f, H, W);
+    if (!w.ok) return;   // (uniform over the workgroup)
+    int* LA = la_all + (long long)f * H * W;
+    int* LB = lb_all + (long long)f * H * W;
+    int filled = 0, root = -1;
+    if (q < (w.wh + 1) * (w.ww + 1)) {
+        const int wy = q / (w.ww + 1), wx = q - wy * (w.ww + 1);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int y = wy - 1 + (k >> 1), x = wx - 1 + (k & 1);
+            if (y < 0 || y >= w.wh || x < 0 || x >= w.ww) continue;
+            const int l = OG_LD(&LB[y * w.ww + x]);
+            if (l >= 0) {
+                ++filled;
+                root = l;
+            }
+        }
+    }
+    const int key = og_window_key(filled);
+    // neighbouring windows mostly lie in ONE blob: the lanes of a wave that share the root of the wave's first keyed lane add once
+    // (integer sums: the same total in any order); every other keyed lane adds for itself
+    const unsigned long long keyed = __ballot(key != 0);
+    if (keyed == 0) return;   // (uniform over the wave)
+    const int lead = __ffsll((long long)keyed) - 1;
+    const int lead_root = __shfl(root, lead);
+    const bool shared = key != 0 && root == lead_root;
+    int sum = shared ? key : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if ((int)(threadIdx.x & 63) == lead)
+        atomicAdd(&LA[lead_root], sum);
+    else if (key != 0 && !shared)
+        atomicAdd(&LA[root], key);
+}
+
+// ONE workgroup per frame: the n_comp greatest ranks among the roots -> sel[f] = {roots taken ..., how many}.  One pass over the window
+// in which every lane keeps its own kBlobMax greatest ranks (rank + 1, so that 0 is "none"), then n_comp rounds over those.
+__global__ __launch_bounds__(kBlobThreads) void k_tblob_select(int H, int W, const int32_t* __restrict__ boxes, int n_comp, int* __restrict__ la_all,
+                                                               int* __restrict__ lb_all, int32_t* __restrict__ sel_all) {
+    __shared__ unsigned long long s_part[kBlobThreads / 64];
+    __shared__ unsigned long long s_pick;
+    const int f = blockIdx.x, tid = threadIdx.x;
+    int32_t* sel = sel_all + f * kSelWords;
+    const OgBlobWindow w = og_blob_window(boxes, f, H, W);
+    if (!w.ok) {   // (uniform over the workgroup)
+        if (tid == 0) sel[kBlobMax] = 0;
+        return;
+    }
+    int* LA = la_all + (long long)f * H * W;
+    int* LB = lb_all + (long long)f * H * W;
+    const int N = w.ww * w.wh;
+    unsigned long long top[kBlobMax];
+#pragma unroll
+    for (int k = 0; k < kBlobMax; ++k) top[k] = 0;
+    for (int p = tid; p < N; p += kBlobThreads) {   // p only increases
+        if (OG_LD(&LB[p]) != p) continue;
+        unsigned long long v = og_blob_rank((unsigned)OG_LD(&LA[p]), (unsigned)p) + 1;
+#pragma unroll
+        for (int k = 0; k < kBlobMax; ++k)   // top stays sorted, greatest first
+            if (v > top[k]) {
+                const unsigned long long t = top[k];
+                top[k] = v;
+                v = t;
+            }
+    }
+    unsigned long long lim = ~0ull;
+    int n_sel = 0;
+    for (int k = 0; k < n_comp; ++k) {   // k only increases, n_comp <= kBlobMax
+        unsigned long long best = 0;
+#pragma unroll
+        for (int j = 0; j < kBlobMax; ++j)
+            if (top[j] < lim && top[j] > best) best = top[j];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long t = __shfl_down(best, o);
+            best = t > best ? t : best;
+        }
+        if ((tid & 63) == 0) s_part[tid >> 6] = best;
+        __syncthreads();
+        if (tid == 0) {
+            unsigned long long m = 0;
+            for (int i = 0; i < kBlobThreads / 64; ++i) m = s_part[i] > m ? s_part[i] : m;
+            s_pick = m;
+            if (m) sel[k] = (int)og_blob_rank_first(m - 1);
+        }
+        __syncthreads();
+        lim = s_pick;
+        if (lim == 0) break;
+        ++n_sel;
+    }
+    if (tid == 0) sel[kBlobMax] = n_sel;
+}
+
+// grid (ceil(H*W / 256), nb): paint the whole frame (mask may be null) and count: area (zero on entry), one 64-lane reduction and one
+// atomicAdd per wave as in k_threshold_in_box.  A frame without a ROI has nothing taken: zero mask, area 0.
+__global__ __launch_bounds__(256) void k_tblob_paint(int H, int W, const int32_t* __restrict__ boxes, int* __restrict__ lb_all,
+                                                     const int32_t* __restrict__ sel_all, uint8_t* __restrict__ mask, int32_t* __restrict__ area) {
+    const int f = blockIdx.y, q = blockIdx.x * 256 + threadIdx.x;
+    const int32_t* sel = sel_all + f * kSelWords;
+    const int n_sel = sel[kBlobMax];
+    int cnt = 0;
+    if (q < H * W) {
+        bool on = false;
+        if (n_sel > 0) {
+            const OgBlobWindow w = og_blob_window(boxes, f, H, W);
+            const int y = q / W - w.y0, x = q - (q / W) * W - w.x0;
+            if (y >= 0 && y < w.wh && x >= 0 && x < w.ww) {
+                const int l = OG_LD(&lb_all[(long long)f * H * W + y * w.ww + x]);
+#pragma unroll
+                for (int k = 0; k < kBlobMax; ++k) on |= (k < n_sel && l == sel[k]);
+                on &= l >= 0;
+            }
+        }
+        if (mask != nullptr) mask[(long long)f * H * W + q] = on ? 255 : 0;
+        cnt = on ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&area[f], cnt);
 }
 
 // =======================================================================================

@@ -180,7 +180,7 @@ def _classical_rows(agg, patient_dice, grays, gts, boxes, patients, unet_model) 
     mask = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
     area = torch.empty(n, dtype=torch.int32, device=dev)
     stats = torch.empty((n, 3), dtype=torch.int32, device=dev)
-    eng = Classic(YGVFT_PARAMS["beta"], YGVFT_PARAMS["glottal_percentile"], YGVFT_PARAMS["max_glottal_components"])
+    eng = Classic(YGVFT_PARAMS["beta"], YGVFT_PARAMS["glottal_percentile"], YGVFT_PARAMS["max_glottal_components"], tiled="auto")
 
     def count(lo, hi):   # confusion counts of mask[lo:hi] against the ground truth -> (dice, iou) per frame
         eng.sync()

@@ -376,7 +376,7 @@ def guided_vft_area_waveform(frames, detector, ygvft_init: int = YGVFT_INIT, par
     if ygvft_init < 1:
         raise ValueError("ygvft_init must be at least 1")
     p = dict(YGVFT_PARAMS, **(params or {}))
-    eng = Classic(p["beta"], p["glottal_percentile"], p["max_glottal_components"])
+    eng = Classic(p["beta"], p["glottal_percentile"], p["max_glottal_components"], tiled="auto")
     detector.reset()
     out, seen, first_box, seeded = [], 0, None, False
     for blk, boxes in _blocks_with_boxes(frames, detector):

@@ -24,7 +24,7 @@ class YOLOGuidedVFT:
         self.n_comp = max_glottal_components
         self.prev = None
         self.lmap = None
-        self._engine = Classic(beta, glottal_percentile, max_glottal_components)
+        self._engine = Classic(beta, glottal_percentile, max_glottal_components, tiled="auto")
         self._seeded = False
 
     @property

@@ -1,4 +1,5 @@
-"""``python -m openglottal_amd.cli run <video> --pipeline {guided-vft,unet,unet-only,yolo-crop+unet}``.
+"""``python -m openglottal_amd.cli run <video> --pipeline {guided-vft,unet,unet-only,yolo-crop+unet}`` and
+``python -m openglottal_amd.cli infer --input DIR --mode {avi,images,npy} ...`` (annotated videos and ``features.csv``, below).
 
 Counterpart of the ``guided-vft`` branch and the two U-Net branches of `openglottal/cli.py:46-103` (`_cmd_run`), plus the
 ``yolo-crop+unet`` pipeline of `scripts/infer.py:222-248` (``--crop-weights``: the crop-trained U-Net checkpoint, `infer.py
@@ -17,9 +18,140 @@ import os
 import sys
 
 
+def _precision_flags(r) -> None:
+    r.add_argument("--precision", choices=["f32", "split", "f16"], default="f32", help="arithmetic of the U-Net, as for `run`")
+    r.add_argument("--detector-precision", choices=["f32", "f16"], default="f32", help="arithmetic of the detector, as for `run`")
+
+
+def add_infer_parser(sub):
+    """`scripts/infer.py`'s flags, by name."""
+    r = sub.add_parser("infer", help="annotated videos (mask fill and outline, detector box) and features.csv")
+    r.add_argument("--input", required=True, help="a directory of videos (avi: *.avi, npy: *.npy frame stacks [B,H,W,3] u8), one .npy "
+                                                  "file, or with --mode images a directory of images that are ONE sequence")
+    r.add_argument("--mode", choices=["avi", "images", "npy"], default="avi")
+    r.add_argument("--pipeline", choices=["vft", "guided-vft", "unet", "unet-only", "yolo-crop+unet"], default="unet")
+    r.add_argument("--yolo-weights", default=None)
+    r.add_argument("--unet-weights", default=None)
+    r.add_argument("--crop-weights", default=None)
+    r.add_argument("--output-dir", default="results")
+    r.add_argument("--capture-fps", type=float, default=4000.0, help="capture frame rate in Hz: f0 is multiplied by it")
+    r.add_argument("--max-hold-frames", type=int, default=3)
+    r.add_argument("--overlay-style", choices=["fill", "contour", "none"], default="fill")
+    r.add_argument("--device", default="cuda")
+    r.add_argument("--frames", choices=["npy", "png"], default="npy", help="png: additionally a directory of PNGs per video (Pillow)")
+    r.add_argument("--label", action="store_true",
+                   help="draw `area=N` at (4, 14) on the host after the device pass, with Pillow's built-in font: the glyphs are NOT "
+                        "OpenCV's Hershey glyphs, so the label's pixels differ from the reference's")
+    _precision_flags(r)
+    return r
+
+
+def _infer_jobs(a):
+    """``(stem, frames)`` per video; frames: a memory-mapped array, or a list of BGR frames."""
+    import numpy as np
+
+    if a.mode == "npy":
+        paths = [a.input] if os.path.isfile(a.input) else sorted(os.path.join(a.input, f) for f in os.listdir(a.input) if f.endswith(".npy"))
+        for p in paths:
+            yield os.path.splitext(os.path.basename(p))[0], np.load(p, mmap_mode="r")
+    elif a.mode == "images":
+        from PIL import Image
+
+        exts = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff")
+        paths = sorted(os.path.join(a.input, f) for f in os.listdir(a.input) if f.lower().endswith(exts))
+        if not paths:
+            raise SystemExit(f"No images found in {a.input}")
+        frames = [np.ascontiguousarray(np.asarray(Image.open(p).convert("RGB"))[..., ::-1]) for p in paths]
+        yield os.path.basename(os.path.normpath(a.input)), frames
+    else:
+        from .features import load_frames_bgr
+
+        paths = sorted(os.path.join(a.input, f) for f in os.listdir(a.input) if f.endswith(".avi"))
+        if not paths:
+            raise SystemExit(f"No .avi files found in {a.input}")
+        for p in paths:
+            yield os.path.splitext(os.path.basename(p))[0], load_frames_bgr(p)
+
+
+def _cmd_infer(ap, a) -> int:
+    from . import infer as I
+
+    if a.pipeline == "vft":
+        ap.error(I.VFT_REFUSAL)
+    if a.pipeline in ("unet", "unet-only") and not a.unet_weights:
+        ap.error("--unet-weights is required for the unet and unet-only pipelines")
+    if a.pipeline == "yolo-crop+unet" and not a.crop_weights:
+        ap.error("--crop-weights is required for the yolo-crop+unet pipeline")
+    if a.pipeline != "unet-only" and not a.yolo_weights:
+        ap.error("--yolo-weights is required for the guided-vft, unet and yolo-crop+unet pipelines")
+    import numpy as np
+
+    from . import TemporalDetector, UNet
+    from .overlay import label_host
+
+    detector = model = None
+    if a.pipeline != "unet-only":
+        detector = TemporalDetector(a.yolo_weights, max_hold_frames=a.max_hold_frames, precision=a.detector_precision)
+    if a.pipeline != "guided-vft":
+        import torch
+
+        model = UNet(1, 1, (32, 64, 128, 256)).to(a.device)
+        model.load_state_dict(torch.load(a.crop_weights if a.pipeline == "yolo-crop+unet" else a.unet_weights, map_location="cpu",
+                                         weights_only=True))
+        model.eval()
+        if a.precision != "f32":
+            model.set_option("precision", {"split": 1, "f16": 2}[a.precision])
+    try:
+        import cv2
+    except ImportError:
+        cv2 = None
+        print("OpenCV is not importable: annotated videos are written as <stem>_out.npy ([B,H,W,3] u8, BGR), not .avi")
+    os.makedirs(a.output_dir, exist_ok=True)
+    rows = []
+    for stem, frames in _infer_jobs(a):
+        print(f"\n[{stem}]  {len(frames)} frames")
+        if not len(frames):
+            print("  WARNING: no frames loaded, skipping.")
+            continue
+        out_npy = os.path.join(a.output_dir, f"{stem}_out.npy")
+        w = I.NpyWriter(out_npy, len(frames))
+        avi = None
+        wave, at = [], 0
+        for blk, area in I.iter_pipeline(frames, detector, a.pipeline, model, a.device, a.overlay_style):
+            if a.label:
+                blk = np.stack([label_host(f, v) for f, v in zip(blk, area)])
+            w.write(blk)
+            if a.frames == "png":
+                I.write_pngs(os.path.join(a.output_dir, f"{stem}_out"), at, blk)
+            if cv2 is not None:
+                if avi is None:
+                    avi = cv2.VideoWriter(os.path.join(a.output_dir, f"{stem}_out.avi"), cv2.VideoWriter_fourcc(*"MJPG"), 25.0,
+                                          (blk.shape[2], blk.shape[1]))
+                for f in blk:
+                    avi.write(f)
+            wave.append(area)
+            at += len(blk)
+        w.close()
+        if avi is not None:
+            avi.release()
+        print(f"  Wrote {out_npy}")
+        row = I.features_row(stem, np.concatenate(wave), a.capture_fps)
+        if not row["area_mean"]:
+            print("  WARNING: silent waveform — no glottis detected.")
+        rows.append(row)
+        for c in I.FEATURE_COLS:
+            if row[c] != "":
+                print(f"  {c}: {row[c]}")
+    path = os.path.join(a.output_dir, "features.csv")
+    I.write_features_csv(path, rows)
+    print(f"\nFeatures saved to {path}")
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="openglottal_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
+    add_infer_parser(sub)
     r = sub.add_parser("run")
     r.add_argument("video")
     r.add_argument("--pipeline", choices=["vft", "guided-vft", "unet", "unet-only", "yolo-crop+unet"], default="unet-only")
@@ -39,6 +171,8 @@ def main(argv=None) -> int:
                         "f32 (default) or the opt-in f16 mode (f16 weights and activations, f32 accumulation, f32 logits; the "
                         "throughput mode of batched calls)")
     a = ap.parse_args(argv)
+    if a.cmd == "infer":
+        return _cmd_infer(ap, a)
     crop = a.pipeline == "yolo-crop+unet"
     if a.pipeline == "vft":
         ap.error("--pipeline vft is not provided: its ROI comes from thresholding a Gaussian-blurred f32 motion map, which cannot be "

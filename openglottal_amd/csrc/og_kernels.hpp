@@ -5540,6 +5540,38 @@ __global__ __launch_bounds__(kTileThreads) void k_tblob_background(const uint8_t
     }
 }
 
+// k_tblob_background for a caller's MASK in the place of gray against a cut (the overlay's outline): set = mask
+// byte nonzero anywhere in the window, which the overlay makes the whole frame.  The local pass and what it leaves in LA are those above.
+__global__ __launch_bounds__(kTileThreads) void k_tblob_background_mask(const uint8_t* __restrict__ masks, int H, int W,
+                                                                        const int32_t* __restrict__ boxes, int* __restrict__ la_all) {
+    __shared__ int lab[kBlobTile * kBlobTile];
+    const int f = blockIdx.y, tid = threadIdx.x;
+    const OgBlobWindow w = og_blob_window(boxes, f, H, W);
+    int tx0, ty0;
+    if (!og_tile_origin(w, W, tx0, ty0)) return;
+    const uint8_t* m = masks + (long long)f * H * W;
+    int* LA = la_all + (long long)f * H * W;
+    for (int i = tid; i < kBlobTile * kBlobTile; i += kTileThreads) {   // i only increases
+        const int y = ty0 + i / kBlobTile, x = tx0 + (i & (kBlobTile - 1));
+        const bool in = og_tile_to_window(w, tx0, ty0, i) >= 0;
+        const bool on = in && m[(long long)y * W + x] != 0;
+        lab[i] = (in && !on) ? i : -1;
+    }
+    __syncthreads();
+    // (og_uf_find, og_uf_union on LDS: parents only decrease, so every walk and every retry ends)
+    for (int i = tid; i < kBlobTile * kBlobTile; i += kTileThreads) {   // i only increases
+        if (OG_LD(&lab[i]) < 0) continue;
+        if ((i & (kBlobTile - 1)) > 0 && OG_LD(&lab[i - 1]) >= 0) og_uf_union(lab, i, i - 1);
+        if (i >= kBlobTile && OG_LD(&lab[i - kBlobTile]) >= 0) og_uf_union(lab, i, i - kBlobTile);
+    }
+    __syncthreads();
+    for (int i = tid; i < kBlobTile * kBlobTile; i += kTileThreads) {   // i only increases; lab is only read from here on
+        const int p = og_tile_to_window(w, tx0, ty0, i);
+        if (p < 0) continue;
+        OG_ST(&LA[p], lab[i] < 0 ? -1 : og_tile_to_window(w, tx0, ty0, og_uf_find(lab, i)));
+    }
+}
+
 // og_uf_union over the pixel pairs that straddle this tile's left and top edge: the pixel beside, and with EIGHT the two diagonals
 // (which also cover both diagonals across a four-tile corner).  EIGHT: on LB, and LA becomes the zeroed key array; else on LA.
 template <bool EIGHT>
@@ -5905,4 +5937,119 @@ __global__ __launch_bounds__(256) void k_track_boxes(const float* __restrict__ b
         __syncthreads();   // (the next block's measurements overwrite the arrays lane 0 has just read)
     }
     if (tid == 0) *state = s_state;
+}
+
+// =======================================================================================
+// Annotated frames (scripts/infer.py:91-124, _draw_overlay; include/openglottal_hip_overlay.h): source, green
+// fill, green outline and yellow box, one BGR pixel at a time.  Every rule is ONE inline function below, called by k_overlay, by
+// the host twins (og_outline_host, og_overlay_host) and through them by the CPU tests.  A later rule overwrites an earlier one.
+//   * og_overlay_source: a BGR pixel is copied, a one-channel pixel replicated to B = G = R.
+//   * og_overlay_draws: without boxes every frame draws its mask and no rectangle; with boxes a frame whose box has x1 < 0 (None
+//     as utils.normalize_box leaves it) draws neither.
+//   * og_overlay_fill: G = min(255, G + 102) where the mask byte is nonzero -- cv2.addWeighted(out, 1, green, 0.4, 0) on u8:
+//     0.4f * 255 is 102.0000015, so no tie can occur.  Masks here are {0, 255}; ANY nonzero byte counts as 255.
+//   * og_outline_at: a set pixel on the frame's edge, or with a 4-neighbour in the OUTSIDE background (the union of the
+//     4-connected background components that touch the frame's edge).  It is what findContours(RETR_EXTERNAL) + drawContours(1)
+//     paint; checked against Moore border following, UNPINNED against OpenCV as every cv2 row of this project.
+//   * og_overlay_on_box: x1 <= x <= x2 and y in {y1, y2}, or x in {x1, x2} and y1 <= y <= y2, both corners inclusive; what lies
+//     off the frame (the detector's x2 == W column) is simply not there.
+// The text label is not drawn here: its glyphs are OpenCV's Hershey table.
+// =======================================================================================
+constexpr int kOverlayNone = 0, kOverlayContour = 1, kOverlayFill = 2, kOverlayStyles = 3;
+
+template <int C>
+__host__ __device__ __forceinline__ void og_overlay_source(const uint8_t* __restrict__ frame, long long p, uint8_t bgr[3]) {
+    if (C == 3) {
+        bgr[0] = frame[p * 3];
+        bgr[1] = frame[p * 3 + 1];
+        bgr[2] = frame[p * 3 + 2];
+    } else {
+        bgr[0] = bgr[1] = bgr[2] = frame[p];
+    }
+}
+__host__ __device__ inline bool og_overlay_draws(const int32_t* box4_or_null) { return box4_or_null == nullptr || box4_or_null[0] >= 0; }
+__host__ __device__ inline uint8_t og_overlay_fill(uint8_t g) { return (uint8_t)(g > 255 - 102 ? 255 : g + 102); }
+__host__ __device__ inline bool og_overlay_on_box(int x, int y, int x1, int y1, int x2, int y2) {
+    return ((y == y1 || y == y2) && x >= x1 && x <= x2) || ((x == x1 || x == x2) && y >= y1 && y <= y2);
+}
+// outside(p): whether pixel p (frame-linear, not set) lies in the outside background; asked only for in-frame neighbours of a set pixel
+template <class F>
+__host__ __device__ __forceinline__ bool og_outline_at(bool set, int x, int y, int H, int W, F outside) {
+    if (!set) return false;
+    if (x == 0 || y == 0 || x == W - 1 || y == H - 1) return true;
+    const int p = y * W + x;
+    return outside(p - 1) || outside(p + 1) || outside(p - W) || outside(p + W);
+}
+// one pixel of one frame: frame [H,W,C], mask [H,W] or null, box4 or null, style kOverlay*
+template <int C, class F>
+__host__ __device__ __forceinline__ void og_overlay_px(const uint8_t* __restrict__ frame, const uint8_t* __restrict__ mask_or_null,
+                                                       const int32_t* box4_or_null, int style, int x, int y, int H, int W, F outside,
+                                                       uint8_t bgr[3]) {
+    const int p = y * W + x;
+    og_overlay_source<C>(frame, p, bgr);
+    if (!og_overlay_draws(box4_or_null)) return;
+    if (mask_or_null != nullptr && style != kOverlayNone && mask_or_null[p] != 0) {
+        if (style == kOverlayFill) bgr[1] = og_overlay_fill(bgr[1]);
+        if (og_outline_at(true, x, y, H, W, outside)) {
+            bgr[0] = 0;
+            bgr[1] = 255;
+            bgr[2] = 0;
+        }
+    }
+    if (box4_or_null != nullptr && og_overlay_on_box(x, y, box4_or_null[0], box4_or_null[1], box4_or_null[2], box4_or_null[3])) {
+        bgr[0] = 0;
+        bgr[1] = 220;
+        bgr[2] = 255;
+    }
+}
+
+// the outside background from the labels k_tblob_background_mask, k_tblob_seams<false>, k_tblob_flatten and k_tblob_border leave over
+// whole-frame windows: -1 where set, else the component's root, whose own entry carries the border flag in its top bit
+struct OgOverlayOutside {
+    const int* LA;
+    __device__ __forceinline__ bool operator()(int p) const {
+        const int l = OG_LD(&LA[p]);
+        return l != -1 && OG_LD(&LA[l & 0x7fffffff]) < 0;
+    }
+};
+
+// One pass over the out bytes of a micro-batch, nb * H * W * 3 of them taken as ONE run: a lane writes one ALIGNED dword of it, so
+// a wave writes 256 contiguous bytes per store whatever H * W * 3 is modulo 4 and wherever `out` starts (a u8 buffer: any
+// address).  A dword always spans two pixels (3-byte pixels), which the lane evaluates both; the up to 3 bytes in front of the
+// first aligned dword and behind the last are written bytewise by the lane after the last dword's.  grid ceil((dwords + 1) / 256).
+// labels: null when nothing is outlined (style none, or no masks).
+template <int C>
+__global__ __launch_bounds__(256) void k_overlay(const uint8_t* __restrict__ src, const uint8_t* __restrict__ masks_or_null,
+                                                 const int32_t* __restrict__ boxes_or_null, const int* __restrict__ labels_or_null, int nb, int H,
+                                                 int W, int style, uint8_t* __restrict__ out) {
+    const long long HW = (long long)H * W, N = (long long)nb * HW * 3;
+    long long head = (long long)((4 - ((uintptr_t)out & 3)) & 3);
+    if (head > N) head = N;
+    const long long nd = (N - head) / 4, g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g > nd) return;
+    const bool dword = g < nd;   // else: this lane writes the bytes [0, head) and [head + 4 nd, N)
+    auto pixel = [&](long long q, uint8_t bgr[3]) {
+        const int f = (int)(q / HW), p = (int)(q - f * HW), y = p / W, x = p - y * W;
+        // (without labels no mask is drawn: og_overlay.inc labels whenever masks are given and the style draws them)
+        const uint8_t* m = (masks_or_null != nullptr && labels_or_null != nullptr) ? masks_or_null + f * HW : nullptr;
+        og_overlay_px<C>(src + f * HW * C, m, boxes_or_null != nullptr ? boxes_or_null + f * 4 : nullptr, style, x, y, H, W,
+                         OgOverlayOutside{labels_or_null != nullptr ? labels_or_null + f * HW : nullptr}, bgr);
+    };
+    if (dword) {
+        const long long k0 = head + 4 * g, q0 = k0 / 3;
+        const int c0 = (int)(k0 - q0 * 3);
+        uint8_t a[6];
+        pixel(q0, a);
+        pixel(q0 + 1, a + 3);   // k0 + 3 < N, so q0 + 1 <= (N - 1) / 3 is a pixel of the micro-batch
+        const uint32_t v = (uint32_t)a[c0] | ((uint32_t)a[c0 + 1] << 8) | ((uint32_t)a[c0 + 2] << 16) | ((uint32_t)a[c0 + 3] << 24);
+        *reinterpret_cast<uint32_t*>(out + k0) = v;
+        return;
+    }
+    for (int j = 0; j < 6; ++j) {
+        const long long k = j < 3 ? j : head + 4 * nd + (j - 3);
+        if (j < 3 ? k >= head : k >= N) continue;
+        uint8_t a[3];
+        pixel(k / 3, a);
+        out[k] = a[k % 3];
+    }
 }

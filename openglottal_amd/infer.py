@@ -1,0 +1,182 @@
+"""Annotated videos: the frame loops of `scripts/infer.py:129-265` (``_run_pipeline``) as batched device passes.  Each block of the
+video is uploaded ONCE; the pipeline's existing ``*_dev`` entry leaves the mask and the area next to it, ``Overlay.annotate_dev``
+draws, and only the annotated frames and 4 bytes of area per frame come back.  Device memory is that of
+one block, not of the video.
+
+Which mask is displayed follows the reference: the full-frame U-Net mask for ``unet`` (not cut to the box; none on a frame without a
+box), the pasted crop mask for ``yolo-crop+unet``, every frame's mask and no rectangle for ``unet-only``, and for ``guided-vft`` no
+mask on the seed frames, whose box is still drawn.  The text label is not drawn here (``overlay.label_host``).
+"""
+from __future__ import annotations
+
+import csv
+import os
+
+import numpy as np
+
+from ._lib import OpenGlottalHipError
+from .features import YGVFT_INIT, YGVFT_PARAMS, _blocks_with_boxes, _kinematic_features, iter_frame_blocks
+from .utils import NET_SIZE
+
+PIPELINES = ("guided-vft", "unet", "unet-only", "yolo-crop+unet")
+VFT_REFUSAL = ("--pipeline vft is not provided: its ROI comes from thresholding a Gaussian-blurred f32 motion map, which cannot be "
+               "pinned without OpenCV (DESIGN.md section 15); use --pipeline guided-vft")
+FEATURE_COLS = ["area_mean", "area_std", "area_range", "open_quotient", "f0", "periodicity", "cv"]
+
+
+def _block_array(blk) -> np.ndarray:
+    a = blk if isinstance(blk, np.ndarray) else np.stack([np.asarray(f) for f in blk])
+    if a.dtype != np.uint8 or not (a.ndim == 3 or (a.ndim == 4 and a.shape[3] == 3)):
+        raise OpenGlottalHipError(f"run_pipeline expects u8 frames [H,W] or [H,W,3] of one shape, got {a.dtype} {a.shape[1:]}")
+    return np.ascontiguousarray(a)
+
+
+def iter_pipeline(frames_bgr, detector, pipeline, model, device=None, overlay_style="fill", threshold: float = 0.5,
+                  crop_size: int = NET_SIZE, ygvft_init: int = YGVFT_INIT, overlay=None):
+    """``(annotated [n,H,W,3] u8, area float64 [n])`` block by block, in order."""
+    import torch
+
+    from .overlay import Overlay, _style
+
+    if pipeline == "vft":
+        raise OpenGlottalHipError(VFT_REFUSAL)
+    if pipeline not in PIPELINES:
+        raise OpenGlottalHipError(f"pipeline must be one of {PIPELINES}, got {pipeline!r}")
+    _style(overlay_style)
+    if pipeline != "guided-vft":
+        if model is None:
+            raise OpenGlottalHipError(f"--pipeline {pipeline} needs a U-Net")
+        if device is not None and getattr(model, "_device", None) is None:
+            model.to(device)
+    if pipeline != "unet-only":
+        if detector is None:
+            raise OpenGlottalHipError(f"--pipeline {pipeline} needs a detector")
+        detector.reset()
+    dev = torch.device("cuda" if device is None else device)
+    if dev.type == "cuda" and dev.index is None and getattr(model, "_device", None) is not None:
+        dev = torch.device("cuda", model._device)
+    ov = overlay if overlay is not None else Overlay()
+    eng = None
+    if pipeline == "guided-vft":
+        from .classic import Classic
+
+        if ygvft_init < 1:
+            raise ValueError("ygvft_init must be at least 1")
+        p = dict(YGVFT_PARAMS)
+        eng = Classic(p["beta"], p["glottal_percentile"], p["max_glottal_components"], tiled="auto")
+    seen, first_box, seeded = 0, None, False
+
+    if pipeline == "unet-only":
+        pairs = ((b, None) for b in iter_frame_blocks(frames_bgr) if len(b))
+    else:
+        pairs = _blocks_with_boxes(frames_bgr, detector, model)
+    with torch.cuda.device(dev):
+        for blk, boxes in pairs:
+            a = _block_array(blk)
+            n, H, W = a.shape[:3]
+            ch = 3 if a.ndim == 4 else 1
+            src = torch.from_numpy(a).to(dev)                             # the block's one upload
+            bx = None if boxes is None else torch.from_numpy(np.ascontiguousarray(boxes, dtype=np.int32)).to(dev)
+            area = torch.zeros(n, dtype=torch.int32, device=dev)
+            mask = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
+            out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize(dev)                                   # (the handles below run on streams of their own)
+            lo0 = 0                                                       # frames [0, lo0): no mask (guided-vft's seed frames)
+            if pipeline in ("unet", "unet-only"):
+                if (H, W) == (NET_SIZE, NET_SIZE):
+                    gray = src
+                    if ch == 3:
+                        gray = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
+                        model.bgr2gray_dev(src, n, H, W, gray)
+                    model.segment_dev(gray, n, H, W, area, threshold, boxes_dev=bx, mask_dev=mask)
+                else:
+                    model.segment_resized_dev(src, n, H, W, ch, NET_SIZE, NET_SIZE, area, threshold, boxes_dev=bx, mask_dev=mask)
+                model.sync()
+            elif pipeline == "yolo-crop+unet":
+                tiles = torch.empty((n, crop_size, crop_size), dtype=torch.uint8, device=dev)
+                tmask = torch.empty_like(tiles)
+                model.segment_crops_dev(src, n, H, W, ch, bx, crop_size, tiles, tmask, area_dev=area, mask_dev=mask, threshold=threshold)
+                model.sync()
+            else:
+                if not seeded:
+                    lo0 = min(n, ygvft_init - seen)
+                    for i in range(lo0):
+                        if first_box is None and boxes[i][0] >= 0:
+                            first_box = tuple(int(v) for v in boxes[i])
+                    seen += lo0
+                    if seen >= ygvft_init:
+                        eng.init([a[lo0 - 1]], first_box)
+                        seeded = True
+                if seeded and lo0 < n:
+                    eng.guided_vft_dev(src[lo0:], n - lo0, H, W, ch, bx[lo0:], area[lo0:], mask_dev=mask[lo0:])
+                    eng.sync()
+            if lo0:
+                ov.annotate_dev(src, lo0, H, W, ch, None, bx, out, overlay_style)
+            if lo0 < n:
+                ov.annotate_dev(src[lo0:], n - lo0, H, W, ch, mask[lo0:], None if bx is None else bx[lo0:], out[lo0:], overlay_style)
+            ov.sync()
+            yield out.cpu().numpy(), area.cpu().numpy().astype(np.float64)
+
+
+def run_pipeline(frames_bgr, detector, pipeline, model, device=None, overlay_style="fill", **kw):
+    """``_run_pipeline``: ``(annotated [B,H,W,3] u8, area_wave float64 [B])`` for u8 frames of one shape (BGR, or gray, which is
+    drawn on as B = G = R).  ``vft`` is refused with the sentence the CLI uses."""
+    frames, waves = [], []
+    for f, a in iter_pipeline(frames_bgr, detector, pipeline, model, device, overlay_style, **kw):
+        frames.append(f)
+        waves.append(a)
+    if not frames:
+        return np.zeros((0, 0, 0, 3), np.uint8), np.zeros(0, np.float64)
+    return np.concatenate(frames), np.concatenate(waves)
+
+
+# ── outputs of `cli infer` ────────────────────────────────────────────────────────────────────────────────────────────
+class NpyWriter:
+    """``<path>`` as ``np.save`` would write ``[B,H,W,3]`` u8, block by block through ``np.lib.format.open_memmap``."""
+
+    def __init__(self, path: str, n_frames: int):
+        self.path, self.n, self.at, self._mm = path, int(n_frames), 0, None
+
+    def write(self, block: np.ndarray) -> None:
+        if self._mm is None:
+            self._mm = np.lib.format.open_memmap(self.path, mode="w+", dtype=np.uint8, shape=(self.n,) + tuple(block.shape[1:]))
+        self._mm[self.at:self.at + len(block)] = block
+        self.at += len(block)
+
+    def close(self) -> None:
+        if self._mm is not None:
+            if self.at != self.n:
+                raise OpenGlottalHipError(f"{self.path}: {self.at} of {self.n} frames written")
+            self._mm.flush()
+            self._mm = None
+
+
+def features_row(stem: str, area_wave, capture_fps: float) -> dict:
+    """One row of ``features.csv`` (`infer.py:436-445`): floats with four decimals, ``f0`` in Hz; every cell empty for a silent
+    waveform.  The ``f0`` cell is left empty when ``f0`` is ``None`` (the reference raises there)."""
+    feats = _kinematic_features([float(v) for v in area_wave])
+    if feats is None:
+        return {"source": stem, **{c: "" for c in FEATURE_COLS}}
+    feats = dict(feats)
+    feats["f0"] = None if feats["f0"] is None else feats["f0"] * capture_fps
+    row = {"source": stem}
+    for c in FEATURE_COLS:
+        v = feats[c]
+        row[c] = "" if v is None else (f"{v:.4f}" if isinstance(v, float) else v)
+    return row
+
+
+def write_features_csv(path: str, rows) -> None:
+    with open(path, "w", newline="") as f:
+        w = csv.DictWriter(f, fieldnames=["source"] + FEATURE_COLS)
+        w.writeheader()
+        for r in rows:
+            w.writerow(r)
+
+
+def write_pngs(directory: str, start: int, block: np.ndarray) -> None:
+    from PIL import Image
+
+    os.makedirs(directory, exist_ok=True)
+    for i, f in enumerate(block):
+        Image.fromarray(np.ascontiguousarray(f[..., ::-1])).save(os.path.join(directory, f"{start + i:06d}.png"))   # BGR -> RGB

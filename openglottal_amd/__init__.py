@@ -10,10 +10,11 @@ from ._lib import OpenGlottalHipError  # noqa: F401
 from .detector import TemporalDetector  # noqa: F401
 from .features import (_kinematic_features, extract_features_unet, extract_features_unet_crop,  # noqa: F401
                        extract_features_yolo_guided_vft)
+from .sweep import Sweep, conf_sweep, hold_ablation, sweep_host  # noqa: F401
 from .tracker import YOLOGuidedVFT  # noqa: F401
 from .unet import UNet  # noqa: F401
 from .utils import dice, iou, unet_segment_frame  # noqa: F401
 
 __all__ = ["UNet", "TemporalDetector", "extract_features_unet", "extract_features_unet_crop", "extract_features_yolo_guided_vft",
            "YOLOGuidedVFT", "unet_segment_frame", "dice", "iou",
-           "OpenGlottalHipError"]
+           "OpenGlottalHipError", "Sweep", "sweep_host", "hold_ablation", "conf_sweep"]

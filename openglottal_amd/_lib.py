@@ -1,6 +1,6 @@
 """ctypes binding of ``libopenglottal_hip.so`` (include/openglottal_hip.h, include/openglottal_hip_crops.h,
 include/openglottal_hip_classic.h, include/openglottal_hip_gated.h, include/openglottal_hip_classic_tiled.h,
-include/openglottal_hip_overlay.h).
+include/openglottal_hip_overlay.h, include/openglottal_hip_sweep.h).
 
 cffi is not installed in the build image, so the thin C-ABI layer
 the north-star asks for is bound with ctypes; the declarations below are the
@@ -195,6 +195,24 @@ OVERLAY_PROTOTYPES = {
     "og_overlay_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
 }
 
+# name -> (restype, argtypes); the complete export list of openglottal_hip_sweep.h (detector ablation sweeps)
+_SWEEP_ARGS = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+               C.c_float, C.c_int, C.c_int]
+_SWEEP_OUT = [C.c_void_p, C.c_void_p, C.c_void_p]
+SWEEP_PROTOTYPES = {
+    "og_sweep_limit": (C.c_longlong, [C.c_int]),
+    "og_sweep_host": (C.c_int, _SWEEP_ARGS + [C.c_void_p] + _SWEEP_OUT),
+    "og_sweep_create": (C.c_void_p, []),
+    "og_sweep_destroy": (None, [C.c_void_p]),
+    "og_sweep_sync": (C.c_int, [C.c_void_p]),
+    "og_sweep_set_chunk": (C.c_int, [C.c_void_p, C.c_int]),
+    "og_sweep_reset": (C.c_int, [C.c_void_p]),
+    "og_sweep_get_state": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "og_sweep_counts_u8_dev": (C.c_int, [C.c_void_p] + _SWEEP_ARGS + _SWEEP_OUT),
+    "og_sweep_counts_u8": (C.c_int, [C.c_void_p] + _SWEEP_ARGS + _SWEEP_OUT),
+    "og_sweep_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
+}
+
 
 def lib() -> C.CDLL:
     """Load the HIP library once; fail loudly if it is not built."""
@@ -217,7 +235,8 @@ def lib() -> C.CDLL:
         except OSError as e:  # missing libamdhip64 etc.
             raise OpenGlottalHipError(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in (list(PROTOTYPES.items()) + list(CROP_PROTOTYPES.items()) + list(CLASSIC_PROTOTYPES.items())
-                                  + list(GATED_PROTOTYPES.items()) + list(TILED_PROTOTYPES.items()) + list(OVERLAY_PROTOTYPES.items())):
+                                  + list(GATED_PROTOTYPES.items()) + list(TILED_PROTOTYPES.items()) + list(OVERLAY_PROTOTYPES.items())
+                                  + list(SWEEP_PROTOTYPES.items())):
             fn = getattr(l, name)  # AttributeError if a symbol is missing: also loud
             fn.restype = res
             fn.argtypes = args

@@ -1,5 +1,7 @@
 """``python -m openglottal_amd.cli run <video> --pipeline {guided-vft,unet,unet-only,yolo-crop+unet}`` and
-``python -m openglottal_amd.cli infer --input DIR --mode {avi,images,npy} ...`` (annotated videos and ``features.csv``, below).
+``python -m openglottal_amd.cli infer --input DIR --mode {avi,images,npy} ...`` (annotated videos and ``features.csv``, below), and
+``python -m openglottal_amd.cli sweep --kind {hold,conf} --frames F.npy --gts G.npy ...`` (the paper's two ablations from one
+inference pass, `openglottal_amd/sweep.py`).
 
 Counterpart of the ``guided-vft`` branch and the two U-Net branches of `openglottal/cli.py:46-103` (`_cmd_run`), plus the
 ``yolo-crop+unet`` pipeline of `scripts/infer.py:222-248` (``--crop-weights``: the crop-trained U-Net checkpoint, `infer.py
@@ -148,10 +150,67 @@ def _cmd_infer(ap, a) -> int:
     return 0
 
 
+def add_sweep_parser(sub):
+    """The paper's two ablations from ONE inference pass (openglottal_amd/sweep.py)."""
+    r = sub.add_parser("sweep", help="hold-duration ablation (eval_girafe.py --max-hold-frames, every value at once) or confidence "
+                                     "sweep (scripts/sweep_bagls_conf.py): the networks run once")
+    r.add_argument("--kind", choices=["hold", "conf"], required=True)
+    r.add_argument("--frames", required=True, help=".npy: [N,H,W,3] / [N,H,W] u8 frames (conf: also an object array of mixed sizes)")
+    r.add_argument("--gts", required=True, help=".npy: ground-truth masks, one per frame")
+    r.add_argument("--patients", default=None, help=".npy: one id per frame (hold: the tracker is reset at every change)")
+    r.add_argument("--unet-weights", required=True)
+    r.add_argument("--yolo-weights", required=True)
+    r.add_argument("--crop-weights", default=None, help="conf: adds the yolo-crop+unet row")
+    r.add_argument("--conf", type=float, default=0.25, help="hold: the detector's confidence threshold")
+    r.add_argument("--canvas", type=int, default=256, help="conf: frames are letterboxed to this size")
+    r.add_argument("--output-json", default=None)
+    r.add_argument("--device", default="cuda")
+    _precision_flags(r)
+    return r
+
+
+def _cmd_sweep(a) -> int:
+    import numpy as np
+    import torch
+
+    from . import TemporalDetector, UNet, sweep
+
+    def unet(path):
+        m = UNet(1, 1, (32, 64, 128, 256)).to(a.device)
+        m.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))
+        m.eval()
+        if a.precision != "f32":
+            m.set_option("precision", {"split": 1, "f16": 2}[a.precision])
+        return m
+
+    frames = list(np.load(a.frames, allow_pickle=True))
+    gts = list(np.load(a.gts, allow_pickle=True))
+    if len(frames) != len(gts):
+        raise SystemExit(f"{a.frames} holds {len(frames)} frames, {a.gts} {len(gts)} masks")
+    model = unet(a.unet_weights)
+    detector = TemporalDetector(a.yolo_weights, conf=a.conf, precision=a.detector_precision)
+    if a.kind == "conf":
+        res = sweep.conf_sweep(frames, gts, model, detector, crop_model=unet(a.crop_weights) if a.crop_weights else None, canvas=a.canvas,
+                               output_json=a.output_json)
+        sweep.print_conf_table(res)
+    else:
+        patients = None if a.patients is None else list(np.load(a.patients, allow_pickle=True))
+        res = sweep.hold_ablation(frames, gts, model, detector, patients=patients)
+        sweep.print_hold_table(res)
+        if a.output_json:
+            os.makedirs(os.path.dirname(os.path.abspath(a.output_json)), exist_ok=True)
+            with open(a.output_json, "w") as f:
+                json.dump({"inf" if h is None else str(h): r["summary"] for h, r in res.items()}, f, indent=2)
+    if a.output_json:
+        print(f"Results saved → {a.output_json}")
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="openglottal_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
     add_infer_parser(sub)
+    add_sweep_parser(sub)
     r = sub.add_parser("run")
     r.add_argument("video")
     r.add_argument("--pipeline", choices=["vft", "guided-vft", "unet", "unet-only", "yolo-crop+unet"], default="unet-only")
@@ -173,7 +232,9 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     if a.cmd == "infer":
         return _cmd_infer(ap, a)
-    crop = a.pipeline == "yolo-crop+unet"
+    if a.cmd == "sweep":
+        return _cmd_sweep(a)
+    crop =a.pipeline == "yolo-crop+unet"
     if a.pipeline == "vft":
         ap.error("--pipeline vft is not provided: its ROI comes from thresholding a Gaussian-blurred f32 motion map, which cannot be "
                  "pinned without OpenCV (DESIGN.md section 15); use --pipeline guided-vft")

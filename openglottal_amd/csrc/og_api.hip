@@ -1657,6 +1657,7 @@ static void bgr2gray_host_loop(const uint8_t* __restrict__ bgr, long long n, uin
 #include "og_classic.inc"
 #include "og_gated.inc"
 #include "og_overlay.inc"
+#include "og_sweep.inc"
 
 extern "C" {
 

@@ -9,7 +9,7 @@ __version__ = "0.1.0"
 from ._lib import OpenGlottalHipError  # noqa: F401
 from .detector import TemporalDetector  # noqa: F401
 from .features import (_kinematic_features, extract_features_unet, extract_features_unet_crop,  # noqa: F401
-                       extract_features_yolo_guided_vft)
+                       extract_features_yolo_guided_vft, extract_gaw_features)
 from .sweep import Sweep, conf_sweep, hold_ablation, sweep_host  # noqa: F401
 from .tracker import YOLOGuidedVFT  # noqa: F401
 from .unet import UNet  # noqa: F401
@@ -17,4 +17,4 @@ from .utils import dice, iou, unet_segment_frame  # noqa: F401
 
 __all__ = ["UNet", "TemporalDetector", "extract_features_unet", "extract_features_unet_crop", "extract_features_yolo_guided_vft",
            "YOLOGuidedVFT", "unet_segment_frame", "dice", "iou",
-           "OpenGlottalHipError", "Sweep", "sweep_host", "hold_ablation", "conf_sweep"]
+           "extract_gaw_features", "OpenGlottalHipError", "Sweep", "sweep_host", "hold_ablation", "conf_sweep"]

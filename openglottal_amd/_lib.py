@@ -1,6 +1,6 @@
 """ctypes binding of ``libopenglottal_hip.so`` (include/openglottal_hip.h, include/openglottal_hip_crops.h,
 include/openglottal_hip_classic.h, include/openglottal_hip_gated.h, include/openglottal_hip_classic_tiled.h,
-include/openglottal_hip_overlay.h, include/openglottal_hip_sweep.h).
+include/openglottal_hip_overlay.h, include/openglottal_hip_sweep.h, include/openglottal_hip_gate.h).
 
 cffi is not installed in the build image, so the thin C-ABI layer
 the north-star asks for is bound with ctypes; the declarations below are the
@@ -213,6 +213,19 @@ SWEEP_PROTOTYPES = {
     "og_sweep_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
 }
 
+# name -> (restype, argtypes); the complete export list of openglottal_hip_gate.h (the U-Net on the kept frames only)
+GATE_PROTOTYPES = {
+    "og_gate_select_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "og_gate_select_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "og_gate_gather_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
+    "og_gate_scatter_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "og_gated_segment_kept_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "og_gated_stream_kept_u8": (C.c_int, _GATED_STREAM + [C.c_void_p]),
+    "og_gated_stream_kept_frames_u8": (C.c_int, _GATED_STREAM + [C.c_void_p]),
+    "og_gate_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
+}
+
 
 def lib() -> C.CDLL:
     """Load the HIP library once; fail loudly if it is not built."""
@@ -236,7 +249,7 @@ def lib() -> C.CDLL:
             raise OpenGlottalHipError(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in (list(PROTOTYPES.items()) + list(CROP_PROTOTYPES.items()) + list(CLASSIC_PROTOTYPES.items())
                                   + list(GATED_PROTOTYPES.items()) + list(TILED_PROTOTYPES.items()) + list(OVERLAY_PROTOTYPES.items())
-                                  + list(SWEEP_PROTOTYPES.items())):
+                                  + list(SWEEP_PROTOTYPES.items()) + list(GATE_PROTOTYPES.items())):
             fn = getattr(l, name)  # AttributeError if a symbol is missing: also loud
             fn.restype = res
             fn.argtypes = args

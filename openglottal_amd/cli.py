@@ -41,6 +41,8 @@ def add_infer_parser(sub):
     r.add_argument("--overlay-style", choices=["fill", "contour", "none"], default="fill")
     r.add_argument("--device", default="cuda")
     r.add_argument("--frames", choices=["npy", "png"], default="npy", help="png: additionally a directory of PNGs per video (Pillow)")
+    r.add_argument("--skip-unboxed", action="store_true",
+                   help="--pipeline unet: run the U-Net only on the frames the detector gave a box (the same frames and areas)")
     r.add_argument("--label", action="store_true",
                    help="draw `area=N` at (4, 14) on the host after the device pass, with Pillow's built-in font: the glyphs are NOT "
                         "OpenCV's Hershey glyphs, so the label's pixels differ from the reference's")
@@ -80,6 +82,8 @@ def _cmd_infer(ap, a) -> int:
 
     if a.pipeline == "vft":
         ap.error(I.VFT_REFUSAL)
+    if a.skip_unboxed and a.pipeline != "unet":
+        ap.error("--skip-unboxed goes with --pipeline unet only: no other pipeline runs the U-Net on frames without a box")
     if a.pipeline in ("unet", "unet-only") and not a.unet_weights:
         ap.error("--unet-weights is required for the unet and unet-only pipelines")
     if a.pipeline == "yolo-crop+unet" and not a.crop_weights:
@@ -119,7 +123,7 @@ def _cmd_infer(ap, a) -> int:
         w = I.NpyWriter(out_npy, len(frames))
         avi = None
         wave, at = [], 0
-        for blk, area in I.iter_pipeline(frames, detector, a.pipeline, model, a.device, a.overlay_style):
+        for blk, area in I.iter_pipeline(frames, detector, a.pipeline, model, a.device, a.overlay_style, skip_unboxed=a.skip_unboxed):
             if a.label:
                 blk = np.stack([label_host(f, v) for f, v in zip(blk, area)])
             w.write(blk)
@@ -220,6 +224,8 @@ def main(argv=None) -> int:
     r.add_argument("--device", default="cuda")
     r.add_argument("-o", "--output", default="output")
     r.add_argument("--annotate", action="store_true", help="also write the pipeline and video names into features.json")
+    r.add_argument("--skip-unboxed", action="store_true",
+                   help="--pipeline unet: run the U-Net only on the frames the detector gave a box (the same waveform)")
     r.add_argument("--precision", choices=["f32", "split", "f16"], default="f32",
                    help="f32: exact fp32 kernels (default, the parity reference); split: opt-in f16 hi/lo split precision "
                         "(2.5x faster, same reference fixtures and tolerance; fails loudly if an activation leaves the f16 range); "
@@ -235,6 +241,8 @@ def main(argv=None) -> int:
     if a.cmd == "sweep":
         return _cmd_sweep(a)
     crop =a.pipeline == "yolo-crop+unet"
+    if a.skip_unboxed and a.pipeline != "unet":
+        ap.error("--skip-unboxed goes with --pipeline unet only: no other pipeline runs the U-Net on frames without a box")
     if a.pipeline == "vft":
         ap.error("--pipeline vft is not provided: its ROI comes from thresholding a Gaussian-blurred f32 motion map, which cannot be "
                  "pinned without OpenCV (DESIGN.md section 15); use --pipeline guided-vft")
@@ -263,7 +271,7 @@ def main(argv=None) -> int:
         model.set_option("precision", {"split": 1, "f16": 2}[a.precision])
     detector = TemporalDetector(a.yolo_weights, precision=a.detector_precision) if (a.pipeline == "unet" or crop) else None
     return _save(a, extract_features_unet_crop(a.video, detector, model, a.device) if crop
-                 else extract_features_unet(a.video, detector, model, a.device))
+                 else extract_features_unet(a.video, detector, model, a.device, skip_unboxed=a.skip_unboxed))
 
 
 def _save(a, feats) -> int:

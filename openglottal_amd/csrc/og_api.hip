@@ -1656,6 +1656,7 @@ static void bgr2gray_host_loop(const uint8_t* __restrict__ bgr, long long n, uin
 #include "og_crops.inc"
 #include "og_classic.inc"
 #include "og_gated.inc"
+#include "og_gate.inc"
 #include "og_overlay.inc"
 #include "og_sweep.inc"
 

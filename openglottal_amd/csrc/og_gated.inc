@@ -6,6 +6,8 @@
 //   unet stream  waits ev_det; og_unet_segment_resized_u8_dev on the same device frames  -> ev_seg
 //   s_d2h        waits ev_seg; area / boxes / best / mask down                           -> ev_out
 // The tracker's state goes from micro-batch to micro-batch, and from call to call, by the order of the detector's stream alone.
+// The *_kept_* entries of og_gate.inc run the same loop with the U-Net step replaced by select / gather / network on the kept frames /
+// scatter (gated_stream_impl's `kept` flag; off, the loop below enqueues exactly what it always did).
 #include "../../include/openglottal_hip_gated.h"
 
 static_assert(sizeof(og_track_state) == sizeof(OgTrackState) && sizeof(og_track_state) == 24, "og_track_state is OgTrackState");
@@ -27,6 +29,14 @@ struct og_gated {
         hipEvent_t ev_up = nullptr, ev_det = nullptr, ev_seg = nullptr, ev_out = nullptr;
         int b0 = -1, nb = 0;
     } slots[2];
+    // og_gate.inc (include/openglottal_hip_gate.h): the dense buffers of the kept entries, one set per slot and one for
+    // og_gated_segment_kept_dev; nothing of it exists until a kept entry is first used
+    struct Gate {
+        uint8_t *d_dense = nullptr, *d_mask = nullptr;
+        int32_t *d_keep = nullptr, *d_boxes = nullptr, *d_area = nullptr, *d_count = nullptr, *h_count = nullptr;
+        hipEvent_t ev_cnt = nullptr;
+        size_t cap_n = 0, cap_in = 0, cap_mask = 0;   // frames, bytes of dense frames, bytes of dense masks
+    } gate[3];
 };
 inline bool og_skip_device(const og_gated* g) { return !g || !g->ready; }
 
@@ -53,6 +63,13 @@ int check_gated_shape(int B, int H, int W, int ch) {
     if (ch != 1 && ch != 3) return fail(OG_EINVAL, "channels must be 1 (gray) or 3 (BGR)");
     return OG_OK;
 }
+
+// og_gate.inc: the U-Net step of a micro-batch on the kept frames only, and the release of what it allocated
+int gate_ensure(og_gated* g, og_gated::Gate& k, int nb, size_t in, size_t mask1);
+int gate_select_enqueue(og_gated* g, og_gated::Gate& k, const int32_t* boxes, int B, hipStream_t st);
+int gate_segment_enqueue(og_gated* g, og_gated::Gate& k, const uint8_t* src, int B, int H, int W, int ch, int Hn, int Wn, float thr,
+                         const int32_t* boxes, uint8_t* mask, int32_t* area, int* n_out);
+void gate_free(og_gated* g);
 
 int check_track_params(const og_track_params* p) {
     if (!p) return fail(OG_EINVAL, "params is null");
@@ -136,20 +153,25 @@ int gated_track_launch(og_gated* g, const float* best, const uint8_t* resets, in
 }
 
 int gated_stream_impl(og_gated* g, const uint8_t* frames, const uint8_t* const* frame_ptrs, int B, int H, int W, int ch, int imgsz, int Hn,
-                      int Wn, float conf, float thr, const uint8_t* resets, int32_t* area, int32_t* boxes, float* best, uint8_t* mask) {
+                      int Wn, float conf, float thr, const uint8_t* resets, int32_t* area, int32_t* boxes, float* best, uint8_t* mask,
+                      bool kept = false, int32_t* n_kept = nullptr) {
     int rc = check_gated_shape(B, H, W, ch);   // (the checks that need no handle come first: they can be tested without a device)
     if (rc) return rc;
     OG_ALIGN(frame_ptrs);
     OG_ALIGN(area);
     OG_ALIGN(boxes);
     OG_ALIGN(best);
+    OG_ALIGN(n_kept);
     if (!g) return fail(OG_EINVAL, "null handle");
     if (!g->unet->finalized || !g->yolo->finalized) return fail(OG_ESTATE, "a borrowed handle is not finalized");
     YGeo geo;
     if ((rc = y_check_resized(g->yolo, B, H, W, ch, imgsz, geo))) return rc;
     if ((rc = check_resized(g->unet, B, H, W, ch, Hn, Wn))) return rc;
     if (g->yolo->pend_B) return fail(OG_EINVAL, "a begin / end call is in flight on the detector handle");
-    if (B == 0) return OG_OK;
+    if (B == 0) {
+        if (n_kept) *n_kept = 0;
+        return OG_OK;
+    }
     if (!frames && !frame_ptrs) return fail(OG_EINVAL, "frames is null");
     if (!area) return fail(OG_EINVAL, "area is null");
     if (frame_ptrs)
@@ -159,6 +181,10 @@ int gated_stream_impl(og_gated* g, const uint8_t* frames, const uint8_t* const* 
     const size_t HW = (size_t)H * W, fb = HW * ch;
     const int chunk = gated_cap(H, W, ch, g->stage_kib);
     if ((rc = gated_ensure(g, chunk, fb, mask ? HW : 0))) return rc;
+    if (kept)
+        for (int i = 0; i < 2; ++i)
+            if ((rc = gate_ensure(g, g->gate[i], chunk, fb, mask ? HW : 0))) return rc;
+    long long total_kept = 0;
     const bool pinned = frames != nullptr && is_pinned_host(frames);
     const hipStream_t sy = g->yolo->stream, su = g->unet->stream;
 
@@ -173,7 +199,7 @@ int gated_stream_impl(og_gated* g, const uint8_t* frames, const uint8_t* const* 
         if (mask) memcpy(mask + b0 * HW, s.h_mask, nb * HW);
         return OG_OK;
     };
-    auto fill = [&](og_gated::Slot& s, int b0, int nb) -> int {
+    auto fill = [&](og_gated::Slot& s, og_gated::Gate& k, int b0, int nb) -> int {
         const uint8_t* src = frames ? frames + (size_t)b0 * fb : s.h_in;
         if (frame_ptrs) {
             for (int j = 0; j < nb; ++j) memcpy(s.h_in + (size_t)j * fb, frame_ptrs[b0 + j], fb);
@@ -196,11 +222,20 @@ int gated_stream_impl(og_gated* g, const uint8_t* frames, const uint8_t* const* 
         g->yolo->latency_batch = lb;
         if (!rc2) rc2 = gated_track_launch(g, s.d_best, resets ? s.d_resets : nullptr, nb, W, H, s.d_boxes);
         if (rc2) return rc2;
-        HIPCHK(hipEventRecord(s.ev_det, sy));
-        HIPCHK(hipStreamWaitEvent(su, s.ev_det, 0));
-        if ((rc2 = og_unet_segment_resized_u8_dev(g->unet, s.d_in, nb, H, W, ch, Hn, Wn, thr, s.d_boxes, mask ? s.d_mask : nullptr, s.d_area,
-                                                  nullptr, nullptr, nullptr)))
-            return rc2;
+        if (kept) {   // select and the count's copy ride the detector's stream; the host waits for the count (the U-Net pass of the
+                      // micro-batch before this one is already enqueued), then enqueues gather, network and scatter on the U-Net's
+            if ((rc2 = gate_select_enqueue(g, k, s.d_boxes, nb, sy))) return rc2;
+            int n = 0;
+            if ((rc2 = gate_segment_enqueue(g, k, s.d_in, nb, H, W, ch, Hn, Wn, thr, s.d_boxes, mask ? s.d_mask : nullptr, s.d_area, &n)))
+                return rc2;
+            total_kept += n;
+        } else {
+            HIPCHK(hipEventRecord(s.ev_det, sy));
+            HIPCHK(hipStreamWaitEvent(su, s.ev_det, 0));
+            if ((rc2 = og_unet_segment_resized_u8_dev(g->unet, s.d_in, nb, H, W, ch, Hn, Wn, thr, s.d_boxes, mask ? s.d_mask : nullptr,
+                                                      s.d_area, nullptr, nullptr, nullptr)))
+                return rc2;
+        }
         HIPCHK(hipEventRecord(s.ev_seg, su));
         HIPCHK(hipStreamWaitEvent(g->s_d2h, s.ev_seg, 0));
         HIPCHK(hipMemcpyAsync(s.h_area, s.d_area, (size_t)nb * 4, hipMemcpyDeviceToHost, g->s_d2h));
@@ -217,7 +252,7 @@ int gated_stream_impl(og_gated* g, const uint8_t* frames, const uint8_t* const* 
     for (int b0 = 0; b0 < B && !rc; b0 += chunk, ++k) {
         og_gated::Slot& s = g->slots[k & 1];
         if ((rc = retire(s))) break;   // micro-batch k - 2 is complete and delivered: the slot's buffers are free
-        rc = fill(s, b0, (B - b0 < chunk) ? B - b0 : chunk);
+        rc = fill(s, g->gate[k & 1], b0, (B - b0 < chunk) ? B - b0 : chunk);
     }
     for (int i = 0; i < 2; ++i) {   // in age order; on an error still wait for what is in flight
         const int rc2 = retire(g->slots[(k + i) & 1]);
@@ -225,6 +260,7 @@ int gated_stream_impl(og_gated* g, const uint8_t* frames, const uint8_t* const* 
     }
     gated_drain(g);   // a caller-pinned source may still be read by a copy whose micro-batch failed later; cheap when all is done
     if (rc) return rc;
+    if (n_kept) *n_kept = (int32_t)total_kept;
     if ((rc = y_check_range(g->yolo))) return rc;
     return check_range(g->unet);
 }
@@ -317,6 +353,7 @@ void og_gated_destroy(og_gated* g) {
     if (g->s_h2d) (void)hipStreamSynchronize(g->s_h2d);
     if (g->s_d2h) (void)hipStreamSynchronize(g->s_d2h);
     gated_free_slots(g);
+    gate_free(g);
     for (auto& s : g->slots)
         for (hipEvent_t ev : {s.ev_up, s.ev_det, s.ev_seg, s.ev_out})
             if (ev) (void)hipEventDestroy(ev);

@@ -5939,6 +5939,12 @@ __global__ __launch_bounds__(256) void k_track_boxes(const float* __restrict__ b
     if (tid == 0) *state = s_state;
 }
 
+// The gate of the gated pipeline (include/openglottal_hip_gate.h; analyze_gaw.py:86-95, infer.py:250-263): a
+// frame is segmented iff the tracker returned a box for it -- `box is not None` after utils.normalize_box, which leaves
+// (-1,-1,-1,-1) for None and never a negative x1 otherwise.  The empty slice (0,0,0,0) IS a box.  Called by k_gate_select and by
+// og_gate_select_host.
+__host__ __device__ inline bool og_gate_keeps(const int32_t* box) { return box[0] >= 0; }
+
 // =======================================================================================
 // Annotated frames (scripts/infer.py:91-124, _draw_overlay; include/openglottal_hip_overlay.h): source, green
 // fill, green outline and yellow box, one BGR pixel at a time.  Every rule is ONE inline function below, called by k_overlay, by

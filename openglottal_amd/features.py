@@ -229,7 +229,7 @@ def _cached_gated_engine(yolo, model):
     return eng
 
 
-def _gated_device_pass(eng, frames, detector, threshold: float) -> np.ndarray:
+def _gated_device_pass(eng, frames, detector, threshold: float, skip_unboxed: bool = False) -> np.ndarray:
     """The whole video through the device engine in one call (it streams micro-batches itself); the Python detector is left in
     the state the staged pass would have left it in, so ``crop_size`` and a following ``detect()`` behave as before."""
     from . import gated
@@ -239,14 +239,39 @@ def _gated_device_pass(eng, frames, detector, threshold: float) -> np.ndarray:
     eng.set_params(detector.max_shift, detector.padding, detector.max_hold_frames)
     src = frames if isinstance(frames, np.ndarray) and frames.flags.c_contiguous else list(frames)
     try:
-        out = eng.run(src, conf=detector.conf, threshold=threshold, net=NET_SIZE, want_boxes=False)
+        out = eng.run(src, conf=detector.conf, threshold=threshold, net=NET_SIZE, want_boxes=False, skip_unboxed=skip_unboxed)
     finally:
         gated.state_to_detector(eng.get_state(), detector)
     return out["area"].astype(np.float64)
 
 
-def area_waveform(frames, detector, model, device=None, threshold: float = 0.5, engine: str = "auto") -> np.ndarray:
+def _segment_run(model, run, bx, threshold: float, skip_unboxed: bool) -> np.ndarray:
+    """Areas of one run of equal-shape u8 frames through the model's streamed entry for its size.  ``skip_unboxed``: only the frames
+    with a box (``bx[:, 0] >= 0``) are handed to the model, in order, and their areas scattered into zeros -- the same numbers, since
+    a frame's area is a function of the frame and its box alone (analyze_gaw.py:86-95 segments no other frame either)."""
+    at_net = run[0].shape[:2] == (NET_SIZE, NET_SIZE)
+    if skip_unboxed and bx is not None:
+        keep = np.flatnonzero(np.asarray(bx)[:, 0] >= 0)
+        a = np.zeros(len(run), np.float64)
+        if len(keep) == 0:
+            return a
+        if len(keep) < len(run):
+            sub = run[keep] if isinstance(run, np.ndarray) else [run[i] for i in keep]
+            a[keep] = _segment_run(model, sub, np.asarray(bx)[keep], threshold, False)
+            return a
+    if at_net:
+        _, ar = model.segment_stream(run, threshold=threshold, boxes=bx)
+    else:
+        _, ar = model.segment_resized(run, net=NET_SIZE, threshold=threshold, boxes=bx, want_mask=False)
+    return np.asarray(ar).astype(np.float64)
+
+
+def area_waveform(frames, detector, model, device=None, threshold: float = 0.5, engine: str = "auto", skip_unboxed: bool = False) -> np.ndarray:
     """The frame loop of features.py:234-245 as batched device passes over blocks of the video.
+
+    ``skip_unboxed`` (gated pass only): the U-Net runs only on the frames the detector gave a box, as
+    `scripts/analyze_gaw.py:86-95` does; the waveform is the same.  The device engine compacts on the device
+    (``GatedEngine.run(skip_unboxed=True)``), the staged pass on the host per run of one shape.
 
     ``engine``: ``"staged"`` is the host-stitched gated pass described below; ``"auto"`` (the default) takes the device engine of
     DESIGN §16 -- one upload per frame, detector, tracker and U-Net in one device pass, the same bits -- when
@@ -272,7 +297,7 @@ def area_waveform(frames, detector, model, device=None, threshold: float = 0.5, 
             frames = load_frames_bgr(frames)   # (decoded once, whichever path takes them)
         eng = gated_engine_for(frames, detector, model, policy=engine == "auto")
         if eng is not None:
-            return _gated_device_pass(eng, frames, detector, threshold)
+            return _gated_device_pass(eng, frames, detector, threshold, skip_unboxed)
         if engine == "device":
             raise OpenGlottalHipError("engine='device': this detector, model or video cannot take the device engine (gated_engine_for)")
     if detector is not None:
@@ -285,7 +310,8 @@ def area_waveform(frames, detector, model, device=None, threshold: float = 0.5, 
         if n == 0:
             continue
         shapes = {f.shape for f in blk}
-        if len(shapes) == 1 and next(iter(shapes))[:2] == (NET_SIZE, NET_SIZE):
+        skip = skip_unboxed and boxes is not None
+        if len(shapes) == 1 and next(iter(shapes))[:2] == (NET_SIZE, NET_SIZE) and not skip:
             # an array goes up in place; a list of frames (features.py:226's `frames_bgr`) is gathered by the engine itself,
             # frame by frame into its pinned ring -- no np.stack of the block
             _, area = model.segment_stream(blk if isinstance(blk, np.ndarray) else list(blk), threshold=threshold, boxes=boxes)
@@ -298,13 +324,17 @@ def area_waveform(frames, detector, model, device=None, threshold: float = 0.5, 
                 bx = None if boxes is None else boxes[lo:hi]
                 if getattr(f0, "dtype", None) == np.uint8 and (f0.ndim == 2 or (f0.ndim == 3 and f0.shape[2] == 3)):
                     run = run if isinstance(run, np.ndarray) else list(run)
-                    if f0.shape[:2] == (NET_SIZE, NET_SIZE):
+                    if skip:
+                        ar = _segment_run(model, run, bx, threshold, True)
+                    elif f0.shape[:2] == (NET_SIZE, NET_SIZE):
                         _, ar = model.segment_stream(run, threshold=threshold, boxes=bx)
                     else:
                         _, ar = model.segment_resized(run, net=NET_SIZE, threshold=threshold, boxes=bx, want_mask=False)
                     a[lo:hi] = ar
                     continue
                 for i in range(lo, hi):   # not u8 gray / BGR: the per-frame loop of features.py:234-245
+                    if skip and boxes[i][0] < 0:
+                        continue
                     m = unet_segment_frame(bgr_to_gray(blk[i]), model, device, threshold)
                     if boxes is None:
                         a[i] = float(np.sum(m > 0))
@@ -316,12 +346,24 @@ def area_waveform(frames, detector, model, device=None, threshold: float = 0.5, 
     return np.concatenate(out) if out else np.zeros(0, np.float64)
 
 
-def extract_features_unet(avi_path, detector, model, device=None) -> dict | None:
+def extract_features_unet(avi_path, detector, model, device=None, skip_unboxed: bool = False) -> dict | None:
     """Drop-in for `openglottal/features.py:202-247` (U-Net-only when ``detector is None``)."""
-    wave = area_waveform(avi_path, detector, model, device)
+    wave = area_waveform(avi_path, detector, model, device, skip_unboxed=skip_unboxed)
     if len(wave) == 0:
         return None   # features.py:227-228
     return _kinematic_features([float(v) for v in wave])
+
+
+def extract_gaw_features(frames, capture_fps, detector, model, device=None) -> dict | None:
+    """`scripts/analyze_gaw.py:75-100` on top of ``area_waveform``: the detector is reset, the U-Net runs only on the frames with
+    a box (``skip_unboxed=True``; a frame without one contributes area 0), the waveform goes through ``_kinematic_features`` and
+    ``f0`` is scaled from cycles per frame to Hz.  ``None`` for a silent waveform; ``f0`` stays ``None`` where it is ``None``."""
+    detector.reset()
+    wave = area_waveform(frames, detector, model, device, skip_unboxed=True)
+    feats = _kinematic_features([float(v) for v in wave])
+    if feats is not None and feats["f0"] is not None:
+        feats["f0"] *= capture_fps
+    return feats
 
 
 def crop_area_waveform(frames, detector, crop_model, device=None, threshold: float = 0.5, crop_size: int = NET_SIZE) -> np.ndarray:

@@ -71,6 +71,28 @@ def plan(B: int, H: int, W: int, channels: int, stage_kib: int = 65536):
     return mbs, nbytes.value
 
 
+def gate_plan(B: int, H: int, W: int, channels: int, stage_kib: int = 65536, with_mask: bool = False):
+    """Dry run of the ``skip_unboxed`` mode without a device: ``plan``'s micro-batches and the engine's device bytes in this mode."""
+    out = C.create_string_buffer(1 << 20)
+    nbytes = C.c_longlong()
+    n = lib().og_gate_plan(B, H, W, channels, stage_kib, int(bool(with_mask)), out, len(out), C.byref(nbytes))
+    if n < 0:
+        check(n, "og_gate_plan")
+    mbs = [tuple(int(v) for v in line.split("|")) for line in out.value.decode().splitlines()]
+    assert len(mbs) == n
+    return mbs, nbytes.value
+
+
+def select_host(boxes) -> np.ndarray:
+    """``og_gate_select_host``: the indices of the kept frames (``boxes[i][0] >= 0``: the tracker returned a box), ascending."""
+    b = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 4)
+    keep = np.empty(len(b), np.int32)
+    n = lib().og_gate_select_host(ptr(b), len(b), ptr(keep))
+    if n < 0:
+        check(n, "og_gate_select_host")
+    return keep[:n].copy()
+
+
 def _frame_args(frames):
     """``(array | None, keep-alive list | None, pointer array | None, B, H, W, channels)`` of an array or a list of u8 frames."""
     if isinstance(frames, (list, tuple)):
@@ -150,21 +172,44 @@ class GatedEngine:
         check(lib().og_track_boxes_dev(self._h, ptr(best_dev), ptr(resets_dev), int(B), int(W), int(H), ptr(boxes_dev)), "og_track_boxes_dev")
 
     def run(self, frames, conf: float = 0.25, threshold: float = 0.5, resets=None, net=NET_SIZE, want_boxes: bool = True,
-            want_best: bool = False, want_mask: bool = False) -> dict:
+            want_best: bool = False, want_mask: bool = False, skip_unboxed: bool = False) -> dict:
         """The gated frame loop over ``frames`` (``[B,H,W]`` gray / ``[B,H,W,3]`` BGR u8 array, or a list of such frames of one
-        shape) → ``{"area": int32 [B], "boxes": int32 [B,4] | None, "best": f32 [B,5] | None, "mask": u8 [B,H,W] | None}``."""
+        shape) → ``{"area": int32 [B], "boxes": int32 [B,4] | None, "best": f32 [B,5] | None, "mask": u8 [B,H,W] | None}``
+        (plus ``"kept": int`` with ``skip_unboxed``).  ``skip_unboxed``: the U-Net runs only on the frames the tracker gave a box; same ``area``,
+        ``boxes`` and ``best``, the mask of a frame without a box is all zero, and ``"kept"`` counts the frames that were segmented."""
         arr, keep, ptrs, B, H, W, ch = _frame_args(frames)
         net_h, net_w = (int(net), int(net)) if np.isscalar(net) else (int(net[0]), int(net[1]))
         out = {"area": np.zeros(B, np.int32), "boxes": np.empty((B, 4), np.int32) if want_boxes else None,
                "best": np.empty((B, 5), np.float32) if want_best else None, "mask": np.empty((B, H, W), np.uint8) if want_mask else None}
+        if skip_unboxed:
+            out["kept"] = 0
         if B == 0:
             return out
         r = None if resets is None else np.ascontiguousarray(resets, dtype=np.uint8).reshape(B)
-        fn, src = (lib().og_gated_stream_u8, ptr(arr)) if ptrs is None else (lib().og_gated_stream_frames_u8, ptrs)
+        l = lib()
+        if skip_unboxed:
+            fn, src = (l.og_gated_stream_kept_u8, ptr(arr)) if ptrs is None else (l.og_gated_stream_kept_frames_u8, ptrs)
+        else:
+            fn, src = (l.og_gated_stream_u8, ptr(arr)) if ptrs is None else (l.og_gated_stream_frames_u8, ptrs)
+        kept = C.c_int32(0)
+        extra = (C.addressof(kept),) if skip_unboxed else ()
         GatedEngine.passes += 1
         check(fn(self._h, src, B, H, W, ch, self._imgsz, net_h, net_w, float(conf), float(threshold), ptr(r), ptr(out["area"]),
-                 ptr(out["boxes"]), ptr(out["best"]), ptr(out["mask"])), fn.__name__)
+                 ptr(out["boxes"]), ptr(out["best"]), ptr(out["mask"]), *extra), fn.__name__)
+        if skip_unboxed:
+            out["kept"] = int(kept.value)
         return out
+
+    def segment_kept_dev(self, src, B: int, H: int, W: int, ch: int, boxes_dev, area_dev, mask_dev=None, threshold: float = 0.5,
+                         net=NET_SIZE) -> int:
+        """``og_gated_segment_kept_dev`` on resident frames (torch CUDA tensors or raw ints): the U-Net on the frames whose box has
+        ``x1 >= 0`` only; ``area_dev`` / ``mask_dev`` come out in frame order, zero for the others.  Returns the number of kept
+        frames; the work after the count is asynchronous on the U-Net's stream (``sync``)."""
+        net_h, net_w = (int(net), int(net)) if np.isscalar(net) else (int(net[0]), int(net[1]))
+        kept = C.c_int32(0)
+        check(lib().og_gated_segment_kept_dev(self._h, ptr(src), int(B), int(H), int(W), int(ch), net_h, net_w, float(threshold),
+                                              ptr(boxes_dev), ptr(mask_dev), ptr(area_dev), C.addressof(kept)), "og_gated_segment_kept_dev")
+        return int(kept.value)
 
     def close(self) -> None:
         if getattr(self, "_h", None):

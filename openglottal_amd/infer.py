@@ -32,8 +32,10 @@ def _block_array(blk) -> np.ndarray:
 
 
 def iter_pipeline(frames_bgr, detector, pipeline, model, device=None, overlay_style="fill", threshold: float = 0.5,
-                  crop_size: int = NET_SIZE, ygvft_init: int = YGVFT_INIT, overlay=None):
-    """``(annotated [n,H,W,3] u8, area float64 [n])`` block by block, in order."""
+                  crop_size: int = NET_SIZE, ygvft_init: int = YGVFT_INIT, overlay=None, skip_unboxed: bool = False):
+    """``(annotated [n,H,W,3] u8, area float64 [n])`` block by block, in order.  ``skip_unboxed`` (``pipeline="unet"`` with the native
+    detector): the U-Net runs only on the frames with a box (``GatedEngine.segment_kept_dev``), as `infer.py:250-263`
+    does; the annotated frames and the areas are the same bytes."""
     import torch
 
     from .overlay import Overlay, _style
@@ -43,6 +45,15 @@ def iter_pipeline(frames_bgr, detector, pipeline, model, device=None, overlay_st
     if pipeline not in PIPELINES:
         raise OpenGlottalHipError(f"pipeline must be one of {PIPELINES}, got {pipeline!r}")
     _style(overlay_style)
+    kept_eng = None
+    if skip_unboxed:
+        from .features import _cached_gated_engine
+        from .yolo import YoloV8Detector
+
+        if pipeline != "unet":
+            raise OpenGlottalHipError("skip_unboxed goes with pipeline 'unet' only: no other pipeline runs the U-Net on frames without a box")
+        if type(getattr(detector, "model", None)) is not YoloV8Detector:
+            raise OpenGlottalHipError("skip_unboxed needs the native detector backend (YoloV8Detector)")
     if pipeline != "guided-vft":
         if model is None:
             raise OpenGlottalHipError(f"--pipeline {pipeline} needs a U-Net")
@@ -82,7 +93,11 @@ def iter_pipeline(frames_bgr, detector, pipeline, model, device=None, overlay_st
             out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev)
             torch.cuda.synchronize(dev)                                   # (the handles below run on streams of their own)
             lo0 = 0                                                       # frames [0, lo0): no mask (guided-vft's seed frames)
-            if pipeline in ("unet", "unet-only"):
+            if skip_unboxed:
+                kept_eng = kept_eng or _cached_gated_engine(detector.model, model)
+                kept_eng.segment_kept_dev(src, n, H, W, ch, bx, area, mask_dev=mask, threshold=threshold, net=NET_SIZE)
+                model.sync()                                              # (all of it ran on the U-Net's stream; the detector's is the worker's)
+            elif pipeline in ("unet", "unet-only"):
                 if (H, W) == (NET_SIZE, NET_SIZE):
                     gray = src
                     if ch == 3:

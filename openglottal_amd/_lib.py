@@ -1,6 +1,7 @@
 """ctypes binding of ``libopenglottal_hip.so`` (include/openglottal_hip.h, include/openglottal_hip_crops.h,
 include/openglottal_hip_classic.h, include/openglottal_hip_gated.h, include/openglottal_hip_classic_tiled.h,
-include/openglottal_hip_overlay.h, include/openglottal_hip_sweep.h, include/openglottal_hip_gate.h).
+include/openglottal_hip_overlay.h, include/openglottal_hip_sweep.h, include/openglottal_hip_gate.h,
+include/openglottal_hip_mjpeg.h).
 
 cffi is not installed in the build image, so the thin C-ABI layer
 the north-star asks for is bound with ctypes; the declarations below are the
@@ -226,6 +227,24 @@ GATE_PROTOTYPES = {
     "og_gate_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
 }
 
+# name -> (restype, argtypes); the complete export list of openglottal_hip_mjpeg.h (baseline JPEG on the device)
+_MJPEG_ENCODE = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+MJPEG_PROTOTYPES = {
+    "og_mjpeg_limit": (C.c_longlong, [C.c_int]),
+    "og_jpeg_bound": (C.c_longlong, [C.c_int, C.c_int]),
+    "og_jpeg_tables_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "og_jpeg_coefficients_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "og_jpeg_encode_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "og_mjpeg_create": (C.c_void_p, []),
+    "og_mjpeg_destroy": (None, [C.c_void_p]),
+    "og_mjpeg_sync": (C.c_int, [C.c_void_p]),
+    "og_mjpeg_set_chunk": (C.c_int, [C.c_void_p, C.c_int]),
+    "og_mjpeg_set_quality": (C.c_int, [C.c_void_p, C.c_int]),
+    "og_mjpeg_encode_u8_dev": (C.c_int, _MJPEG_ENCODE),
+    "og_mjpeg_encode_stream_u8": (C.c_int, _MJPEG_ENCODE),
+    "og_mjpeg_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
+}
+
 
 def lib() -> C.CDLL:
     """Load the HIP library once; fail loudly if it is not built."""
@@ -249,7 +268,7 @@ def lib() -> C.CDLL:
             raise OpenGlottalHipError(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in (list(PROTOTYPES.items()) + list(CROP_PROTOTYPES.items()) + list(CLASSIC_PROTOTYPES.items())
                                   + list(GATED_PROTOTYPES.items()) + list(TILED_PROTOTYPES.items()) + list(OVERLAY_PROTOTYPES.items())
-                                  + list(SWEEP_PROTOTYPES.items()) + list(GATE_PROTOTYPES.items())):
+                                  + list(SWEEP_PROTOTYPES.items()) + list(GATE_PROTOTYPES.items()) + list(MJPEG_PROTOTYPES.items())):
             fn = getattr(l, name)  # AttributeError if a symbol is missing: also loud
             fn.restype = res
             fn.argtypes = args

@@ -1,5 +1,6 @@
 """``python -m openglottal_amd.cli run <video> --pipeline {guided-vft,unet,unet-only,yolo-crop+unet}`` and
-``python -m openglottal_amd.cli infer --input DIR --mode {avi,images,npy} ...`` (annotated videos and ``features.csv``, below), and
+``python -m openglottal_amd.cli infer --input DIR --mode {avi,images,npy} ...`` (annotated videos and ``features.csv``, below;
+``--avi device`` writes them as Motion-JPEG ``<stem>_out.avi`` coded on the device, openglottal_amd/mjpeg.py), and
 ``python -m openglottal_amd.cli sweep --kind {hold,conf} --frames F.npy --gts G.npy ...`` (the paper's two ablations from one
 inference pass, `openglottal_amd/sweep.py`).
 
@@ -46,6 +47,13 @@ def add_infer_parser(sub):
     r.add_argument("--label", action="store_true",
                    help="draw `area=N` at (4, 14) on the host after the device pass, with Pillow's built-in font: the glyphs are NOT "
                         "OpenCV's Hershey glyphs, so the label's pixels differ from the reference's")
+    r.add_argument("--avi", choices=["opencv", "device"], default="opencv",
+                   help="opencv (default): <stem>_out.avi through OpenCV's MJPG writer when OpenCV is importable, as until now; device: "
+                        "the annotated frames are coded as baseline JPEG on the device and written as a Motion-JPEG <stem>_out.avi at "
+                        "25 fps, no OpenCV needed")
+    r.add_argument("--jpeg-quality", type=int, default=75, help="--avi device: IJG quality 1..100")
+    r.add_argument("--no-npy", action="store_true",
+                   help="--avi device: do not write <stem>_out.npy; the annotated frames then never leave the device uncompressed")
     _precision_flags(r)
     return r
 
@@ -90,6 +98,16 @@ def _cmd_infer(ap, a) -> int:
         ap.error("--crop-weights is required for the yolo-crop+unet pipeline")
     if a.pipeline != "unet-only" and not a.yolo_weights:
         ap.error("--yolo-weights is required for the guided-vft, unet and yolo-crop+unet pipelines")
+    device_avi = a.avi == "device"
+    if device_avi and a.label:
+        ap.error("--label draws on the host after the device pass, so it needs the annotated frames there; with --avi device they are "
+                 "coded on the device before they leave it.  Drop one of the two")
+    if device_avi and not 1 <= a.jpeg_quality <= 100:
+        ap.error("--jpeg-quality must be 1..100")
+    if a.no_npy and not device_avi:
+        ap.error("--no-npy goes with --avi device only: without it the .npy is the only annotated output")
+    if a.no_npy and a.frames == "png":
+        ap.error("--frames png needs the annotated frames on the host, which --no-npy leaves on the device")
     import numpy as np
 
     from . import TemporalDetector, UNet
@@ -107,11 +125,16 @@ def _cmd_infer(ap, a) -> int:
         model.eval()
         if a.precision != "f32":
             model.set_option("precision", {"split": 1, "f16": 2}[a.precision])
-    try:
-        import cv2
-    except ImportError:
-        cv2 = None
-        print("OpenCV is not importable: annotated videos are written as <stem>_out.npy ([B,H,W,3] u8, BGR), not .avi")
+    cv2 = encoder = None
+    if device_avi:
+        from .mjpeg import AviWriter, Mjpeg
+
+        encoder = Mjpeg(a.jpeg_quality)
+    else:
+        try:
+            import cv2
+        except ImportError:
+            print("OpenCV is not importable: annotated videos are written as <stem>_out.npy ([B,H,W,3] u8, BGR), not .avi")
     os.makedirs(a.output_dir, exist_ok=True)
     rows = []
     for stem, frames in _infer_jobs(a):
@@ -120,27 +143,47 @@ def _cmd_infer(ap, a) -> int:
             print("  WARNING: no frames loaded, skipping.")
             continue
         out_npy = os.path.join(a.output_dir, f"{stem}_out.npy")
-        w = I.NpyWriter(out_npy, len(frames))
+        out_avi = os.path.join(a.output_dir, f"{stem}_out.avi")
+        w = None if a.no_npy else I.NpyWriter(out_npy, len(frames))
         avi = None
         wave, at = [], 0
-        for blk, area in I.iter_pipeline(frames, detector, a.pipeline, model, a.device, a.overlay_style, skip_unboxed=a.skip_unboxed):
-            if a.label:
-                blk = np.stack([label_host(f, v) for f, v in zip(blk, area)])
-            w.write(blk)
-            if a.frames == "png":
-                I.write_pngs(os.path.join(a.output_dir, f"{stem}_out"), at, blk)
-            if cv2 is not None:
+        if device_avi:
+            # the block loop of iter_pipeline with the JPEG coder behind the overlay; the frames come back only for the .npy
+            for item in I.iter_pipeline_mjpeg(frames, detector, a.pipeline, model, a.device, a.overlay_style, encoder=encoder,
+                                              frames=not a.no_npy, skip_unboxed=a.skip_unboxed):
+                blob, sizes, area = item[:3]
                 if avi is None:
-                    avi = cv2.VideoWriter(os.path.join(a.output_dir, f"{stem}_out.avi"), cv2.VideoWriter_fourcc(*"MJPG"), 25.0,
-                                          (blk.shape[2], blk.shape[1]))
-                for f in blk:
-                    avi.write(f)
-            wave.append(area)
-            at += len(blk)
-        w.close()
-        if avi is not None:
-            avi.release()
-        print(f"  Wrote {out_npy}")
+                    H, W = np.asarray(frames[0]).shape[:2]
+                    avi = AviWriter(out_avi, W, H, 25.0)
+                avi.write(blob, sizes)
+                if w is not None:
+                    w.write(item[3])
+                    if a.frames == "png":
+                        I.write_pngs(os.path.join(a.output_dir, f"{stem}_out"), at, item[3])
+                wave.append(area)
+                at += len(sizes)
+            if avi is not None:
+                avi.close()
+                print(f"  Wrote {out_avi}")
+        else:
+            for blk, area in I.iter_pipeline(frames, detector, a.pipeline, model, a.device, a.overlay_style, skip_unboxed=a.skip_unboxed):
+                if a.label:
+                    blk = np.stack([label_host(f, v) for f, v in zip(blk, area)])
+                w.write(blk)
+                if a.frames == "png":
+                    I.write_pngs(os.path.join(a.output_dir, f"{stem}_out"), at, blk)
+                if cv2 is not None:
+                    if avi is None:
+                        avi = cv2.VideoWriter(out_avi, cv2.VideoWriter_fourcc(*"MJPG"), 25.0, (blk.shape[2], blk.shape[1]))
+                    for f in blk:
+                        avi.write(f)
+                wave.append(area)
+                at += len(blk)
+            if avi is not None:
+                avi.release()
+        if w is not None:
+            w.close()
+            print(f"  Wrote {out_npy}")
         row = I.features_row(stem, np.concatenate(wave), a.capture_fps)
         if not row["area_mean"]:
             print("  WARNING: silent waveform — no glottis detected.")

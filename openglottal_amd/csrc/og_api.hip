@@ -1659,6 +1659,7 @@ static void bgr2gray_host_loop(const uint8_t* __restrict__ bgr, long long n, uin
 #include "og_gate.inc"
 #include "og_overlay.inc"
 #include "og_sweep.inc"
+#include "og_mjpeg.inc"
 
 extern "C" {
 

@@ -49,7 +49,8 @@ def load_frames_bgr(source) -> list[np.ndarray]:
 
     ``source`` may be an in-memory array/list of frames, a ``.npy``/``.npz`` file
     (``[N,H,W,3]`` BGR or ``[N,H,W]`` gray), a directory of PNG/JPEG frames (Pillow), or a
-    video file when OpenCV is importable (AVI/MJPG decode is host I/O and stays on cv2).
+    video file when OpenCV is importable (AVI/MJPG decode is host I/O and stays on cv2).  Without OpenCV an ``.avi``
+    whose video stream is ``MJPG`` is read by ``mjpeg.read_avi_mjpeg``'s RIFF walk and Pillow; every other codec is still an error.
     """
     if isinstance(source, np.ndarray):
         return list(source)
@@ -75,6 +76,12 @@ def load_frames_bgr(source) -> list[np.ndarray]:
     try:
         import cv2  # noqa: F401
     except ImportError as e:
+        from .mjpeg import avi_stream, decode_jpeg_bgr
+
+        if p.lower().endswith(".avi"):   # Motion-JPEG, what `cli infer --avi device` writes: a RIFF walk and Pillow's decoder
+            handler, chunks = avi_stream(p)
+            if handler is not None and handler.upper() == b"MJPG":
+                return [decode_jpeg_bgr(j) for j in chunks]
         raise OpenGlottalHipError(f"decoding {p} needs OpenCV; pass frames as .npy/.npz or an array instead") from e
     import cv2
 

@@ -6,6 +6,9 @@ one block, not of the video.
 Which mask is displayed follows the reference: the full-frame U-Net mask for ``unet`` (not cut to the box; none on a frame without a
 box), the pasted crop mask for ``yolo-crop+unet``, every frame's mask and no rectangle for ``unet-only``, and for ``guided-vft`` no
 mask on the seed frames, whose box is still drawn.  The text label is not drawn here (``overlay.label_host``).
+
+``iter_pipeline_mjpeg`` is the same loop with ``mjpeg.Mjpeg`` behind the overlay: the annotated frames are
+coded as JPEG files on the device and only those bytes come back, for ``mjpeg.AviWriter`` to put into ``<stem>_out.avi``.
 """
 from __future__ import annotations
 
@@ -31,11 +34,10 @@ def _block_array(blk) -> np.ndarray:
     return np.ascontiguousarray(a)
 
 
-def iter_pipeline(frames_bgr, detector, pipeline, model, device=None, overlay_style="fill", threshold: float = 0.5,
-                  crop_size: int = NET_SIZE, ygvft_init: int = YGVFT_INIT, overlay=None, skip_unboxed: bool = False):
-    """``(annotated [n,H,W,3] u8, area float64 [n])`` block by block, in order.  ``skip_unboxed`` (``pipeline="unet"`` with the native
-    detector): the U-Net runs only on the frames with a box (``GatedEngine.segment_kept_dev``, DESIGN §21), as `infer.py:250-263`
-    does; the annotated frames and the areas are the same bytes."""
+def _iter_annotated_dev(frames_bgr, detector, pipeline, model, device=None, overlay_style="fill", threshold: float = 0.5,
+                        crop_size: int = NET_SIZE, ygvft_init: int = YGVFT_INIT, overlay=None, skip_unboxed: bool = False):
+    """The block loop that `iter_pipeline` and `iter_pipeline_mjpeg` share: ``(annotated [n,H,W,3] u8, area int32 [n])`` as CUDA
+    tensors, block by block, in order; every handle has been waited for."""
     import torch
 
     from .overlay import Overlay, _style
@@ -130,7 +132,31 @@ def iter_pipeline(frames_bgr, detector, pipeline, model, device=None, overlay_st
             if lo0 < n:
                 ov.annotate_dev(src[lo0:], n - lo0, H, W, ch, mask[lo0:], None if bx is None else bx[lo0:], out[lo0:], overlay_style)
             ov.sync()
-            yield out.cpu().numpy(), area.cpu().numpy().astype(np.float64)
+            yield out, area
+
+
+def iter_pipeline(frames_bgr, detector, pipeline, model, device=None, overlay_style="fill", threshold: float = 0.5,
+                  crop_size: int = NET_SIZE, ygvft_init: int = YGVFT_INIT, overlay=None, skip_unboxed: bool = False):
+    """``(annotated [n,H,W,3] u8, area float64 [n])`` block by block, in order.  ``skip_unboxed`` (``pipeline="unet"`` with the native
+    detector): the U-Net runs only on the frames with a box (``GatedEngine.segment_kept_dev``, DESIGN §21), as `infer.py:250-263`
+    does; the annotated frames and the areas are the same bytes."""
+    for out, area in _iter_annotated_dev(frames_bgr, detector, pipeline, model, device, overlay_style, threshold, crop_size, ygvft_init,
+                                         overlay, skip_unboxed):
+        yield out.cpu().numpy(), area.cpu().numpy().astype(np.float64)
+
+
+def iter_pipeline_mjpeg(frames_bgr, detector, pipeline, model, device=None, overlay_style="fill", encoder=None, frames: bool = False,
+                        **kw):
+    """The same loop with the annotated frames coded as JPEG files on the device (``mjpeg.Mjpeg``): ``(blob u8, sizes
+    int32 [n], area float64 [n])`` per block, the block's files back to back in ``blob``.  The frames go from ``Overlay.annotate_dev``
+    into ``Mjpeg.encode_dev`` and never cross to the host uncompressed -- unless ``frames`` asks for them as a fourth item."""
+    from .mjpeg import Mjpeg
+
+    enc = encoder if encoder is not None else Mjpeg()
+    for out, area in _iter_annotated_dev(frames_bgr, detector, pipeline, model, device, overlay_style, **kw):
+        blob, sizes = enc.encode_resident(out)
+        item = (blob, sizes, area.cpu().numpy().astype(np.float64))
+        yield item + (out.cpu().numpy(),) if frames else item
 
 
 def run_pipeline(frames_bgr, detector, pipeline, model, device=None, overlay_style="fill", **kw):

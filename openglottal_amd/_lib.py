@@ -1,7 +1,7 @@
 """ctypes binding of ``libopenglottal_hip.so`` (include/openglottal_hip.h, include/openglottal_hip_crops.h,
 include/openglottal_hip_classic.h, include/openglottal_hip_gated.h, include/openglottal_hip_classic_tiled.h,
 include/openglottal_hip_overlay.h, include/openglottal_hip_sweep.h, include/openglottal_hip_gate.h,
-include/openglottal_hip_mjpeg.h).
+include/openglottal_hip_mjpeg.h, include/decode/openglottal_hip_mjpd.h).
 
 cffi is not installed in the build image, so the thin C-ABI layer
 the north-star asks for is bound with ctypes; the declarations below are the
@@ -245,6 +245,25 @@ MJPEG_PROTOTYPES = {
     "og_mjpeg_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
 }
 
+# name -> (restype, argtypes); the complete export list of decode/openglottal_hip_mjpd.h (baseline JPEG decoded on the device)
+MJPD_PROTOTYPES = {
+    "og_mjpd_limit": (C.c_longlong, [C.c_int]),
+    "og_jpegd_parse_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "og_jpegd_decode_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "og_jpegd_idct_pass_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "og_jpegd_records_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5),
+    "og_mjpd_create": (C.c_void_p, []),
+    "og_mjpd_destroy": (None, [C.c_void_p]),
+    "og_mjpd_sync": (C.c_int, [C.c_void_p]),
+    "og_mjpd_set_chunk": (C.c_int, [C.c_void_p, C.c_int]),
+    "og_mjpd_set_tables": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "og_mjpd_decode_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                        C.c_void_p]),
+    "og_mjpd_decode_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
+    "og_mjpd_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
+}
+
 
 def lib() -> C.CDLL:
     """Load the HIP library once; fail loudly if it is not built."""
@@ -268,7 +287,8 @@ def lib() -> C.CDLL:
             raise OpenGlottalHipError(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in (list(PROTOTYPES.items()) + list(CROP_PROTOTYPES.items()) + list(CLASSIC_PROTOTYPES.items())
                                   + list(GATED_PROTOTYPES.items()) + list(TILED_PROTOTYPES.items()) + list(OVERLAY_PROTOTYPES.items())
-                                  + list(SWEEP_PROTOTYPES.items()) + list(GATE_PROTOTYPES.items()) + list(MJPEG_PROTOTYPES.items())):
+                                  + list(SWEEP_PROTOTYPES.items()) + list(GATE_PROTOTYPES.items()) + list(MJPEG_PROTOTYPES.items())
+                                  + list(MJPD_PROTOTYPES.items())):
             fn = getattr(l, name)  # AttributeError if a symbol is missing: also loud
             fn.restype = res
             fn.argtypes = args

@@ -54,8 +54,16 @@ def add_infer_parser(sub):
     r.add_argument("--jpeg-quality", type=int, default=75, help="--avi device: IJG quality 1..100")
     r.add_argument("--no-npy", action="store_true",
                    help="--avi device: do not write <stem>_out.npy; the annotated frames then never leave the device uncompressed")
+    _decode_flag(r)
     _precision_flags(r)
     return r
+
+
+def _decode_flag(r) -> None:
+    r.add_argument("--decode", choices=["host", "device", "auto"], default="host",
+                   help="host (default): videos are decoded on the host, as until now; device: an MJPG .avi (or a directory of .jpg "
+                        "frames of one size) goes to the device compressed and is decoded there (baseline JPEG only); auto: device, "
+                        "and the host loop, with one line on stderr, when the decoder refuses the first frame")
 
 
 def _infer_jobs(a):
@@ -73,6 +81,19 @@ def _infer_jobs(a):
         paths = sorted(os.path.join(a.input, f) for f in os.listdir(a.input) if f.lower().endswith(exts))
         if not paths:
             raise SystemExit(f"No images found in {a.input}")
+        if a.decode != "host":
+            from .mjpeg import open_compressed
+
+            video = None
+            if all(p.lower().endswith((".jpg", ".jpeg")) for p in paths):
+                video = open_compressed(a.input, a.decode)
+            elif a.decode == "auto":
+                print(f"--decode auto: {a.input} is decoded on the host: it holds images that are no .jpg files", file=sys.stderr)
+            else:
+                raise SystemExit(f"--decode device with --mode images needs a directory of .jpg frames only: {a.input}")
+            if video is not None:
+                yield os.path.basename(os.path.normpath(a.input)), video
+                return
         frames = [np.ascontiguousarray(np.asarray(Image.open(p).convert("RGB"))[..., ::-1]) for p in paths]
         yield os.path.basename(os.path.normpath(a.input)), frames
     else:
@@ -82,7 +103,12 @@ def _infer_jobs(a):
         if not paths:
             raise SystemExit(f"No .avi files found in {a.input}")
         for p in paths:
-            yield os.path.splitext(os.path.basename(p))[0], load_frames_bgr(p)
+            video = None
+            if a.decode != "host":
+                from .mjpeg import open_compressed
+
+                video = open_compressed(p, a.decode)
+            yield os.path.splitext(os.path.basename(p))[0], video if video is not None else load_frames_bgr(p)
 
 
 def _cmd_infer(ap, a) -> int:
@@ -106,6 +132,9 @@ def _cmd_infer(ap, a) -> int:
         ap.error("--jpeg-quality must be 1..100")
     if a.no_npy and not device_avi:
         ap.error("--no-npy goes with --avi device only: without it the .npy is the only annotated output")
+    if a.decode != "host" and a.mode == "npy":
+        ap.error("--decode device and auto are for compressed input (--mode avi, or --mode images with .jpg frames); a .npy holds "
+                 "decoded frames")
     if a.no_npy and a.frames == "png":
         ap.error("--frames png needs the annotated frames on the host, which --no-npy leaves on the device")
     import numpy as np
@@ -278,6 +307,7 @@ def main(argv=None) -> int:
                    help="arithmetic of the YOLOv8 detector (--pipeline unet), independent of --precision (which is the U-Net's): "
                         "f32 (default) or the opt-in f16 mode (f16 weights and activations, f32 accumulation, f32 logits; the "
                         "throughput mode of batched calls)")
+    _decode_flag(r)
     a = ap.parse_args(argv)
     if a.cmd == "infer":
         return _cmd_infer(ap, a)
@@ -295,6 +325,8 @@ def main(argv=None) -> int:
         from . import TemporalDetector, extract_features_yolo_guided_vft
 
         detector = TemporalDetector(a.yolo_weights, precision=a.detector_precision)
+        if a.decode != "host":
+            a.video = _decoded_on_device(a)
         return _save(a, extract_features_yolo_guided_vft(a.video, detector))
     if crop and not a.crop_weights:
         ap.error("--crop-weights is required for --pipeline yolo-crop+unet")
@@ -307,6 +339,8 @@ def main(argv=None) -> int:
 
     if (a.pipeline == "unet" or crop) and not a.yolo_weights:
         ap.error(f"--yolo-weights is required for --pipeline {a.pipeline}")
+    if a.decode != "host":                                                # (after every argument check: this touches the device)
+        a.video = _decoded_on_device(a)
     model = UNet(1, 1, (32, 64, 128, 256)).to(a.device)   # (yolo-crop+unet: the crop model; --precision applies to it)
     model.load_state_dict(torch.load(a.crop_weights if crop else a.unet_weights, map_location="cpu", weights_only=True))
     model.eval()
@@ -315,6 +349,17 @@ def main(argv=None) -> int:
     detector = TemporalDetector(a.yolo_weights, precision=a.detector_precision) if (a.pipeline == "unet" or crop) else None
     return _save(a, extract_features_unet_crop(a.video, detector, model, a.device) if crop
                  else extract_features_unet(a.video, detector, model, a.device, skip_unboxed=a.skip_unboxed))
+
+
+def _decoded_on_device(a):
+    """`run --decode device`: the frames of an MJPG .avi (or a directory of .jpg frames) decoded on the device, block by block, and
+    handed to the feature extractors as the in-memory array they already take.  `auto`: the path itself when the decoder refuses it."""
+    from .mjpeg import open_compressed
+
+    if str(a.video).endswith((".npy", ".npz")):
+        raise SystemExit(f"--decode {a.decode} is for compressed input (an MJPG .avi or a directory of .jpg frames), not {a.video}")
+    video = open_compressed(str(a.video), a.decode)
+    return a.video if video is None else video.frames_host()
 
 
 def _save(a, feats) -> int:

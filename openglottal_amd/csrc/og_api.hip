@@ -1660,6 +1660,7 @@ static void bgr2gray_host_loop(const uint8_t* __restrict__ bgr, long long n, uin
 #include "og_overlay.inc"
 #include "og_sweep.inc"
 #include "og_mjpeg.inc"
+#include "og_mjpd.inc"
 
 extern "C" {
 

@@ -79,16 +79,31 @@ def _iter_annotated_dev(frames_bgr, detector, pipeline, model, device=None, over
         eng = Classic(p["beta"], p["glottal_percentile"], p["max_glottal_components"], tiled="auto")
     seen, first_box, seeded = 0, None, False
 
-    if pipeline == "unet-only":
+    from .features import BLOCK
+    from .mjpeg import CompressedVideo
+
+    if isinstance(frames_bgr, CompressedVideo):
+        # --decode device.  unet-only: the decoded block stays on the device and is `src` below.  With a
+        # detector the video comes back to the host once, for the detector's existing frame loop.
+        if pipeline == "unet-only":
+            pairs = ((b, None) for b in frames_bgr.blocks_resident(BLOCK))
+        else:
+            pairs = _blocks_with_boxes(frames_bgr.frames_host(), detector, model)
+    elif pipeline == "unet-only":
         pairs = ((b, None) for b in iter_frame_blocks(frames_bgr) if len(b))
     else:
         pairs = _blocks_with_boxes(frames_bgr, detector, model)
     with torch.cuda.device(dev):
         for blk, boxes in pairs:
-            a = _block_array(blk)
-            n, H, W = a.shape[:3]
-            ch = 3 if a.ndim == 4 else 1
-            src = torch.from_numpy(a).to(dev)                             # the block's one upload
+            if torch.is_tensor(blk):                                      # decoded on the device: nothing to upload
+                a, src = None, blk.to(dev)
+                n, H, W = (int(v) for v in src.shape[:3])
+                ch = 3
+            else:
+                a = _block_array(blk)
+                n, H, W = a.shape[:3]
+                ch = 3 if a.ndim == 4 else 1
+                src = torch.from_numpy(a).to(dev)                         # the block's one upload
             bx = None if boxes is None else torch.from_numpy(np.ascontiguousarray(boxes, dtype=np.int32)).to(dev)
             area = torch.zeros(n, dtype=torch.int32, device=dev)
             mask = torch.empty((n, H, W), dtype=torch.uint8, device=dev)

@@ -292,3 +292,251 @@ def read_avi_mjpeg(path: str) -> list[np.ndarray]:
     if handler is None or handler.upper() != b"MJPG":
         raise OpenGlottalHipError(f"{path}: the video stream is {handler!r}, only MJPG is decoded without OpenCV")
     return [decode_jpeg_bgr(j) for j in frames]
+
+
+# ── decoding on the device (include/decode/openglottal_hip_mjpd.h) ──────────────────────────────────────────────────────────────────
+STATUS = {0: "ok", 1: "truncated scan", 2: "invalid Huffman code", 3: "coefficient index past 63", 4: "value outside the baseline range",
+          5: "restart marker count or order", 6: "unsupported form", 7: "size, sampling or restart interval differ from the call's"}
+SAMPLING = {0: "gray", 1: "4:4:4", 2: "4:2:2", 3: "4:2:0"}
+
+
+class _Info(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("H", "W", "ncomp", "sampling", "Ri", "M", "nI", "tables")] + \
+               [("scan_offset", C.c_int64), ("scan_length", C.c_int64), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+def decode_limit(which: int) -> int:
+    return int(lib().og_mjpd_limit(which))
+
+
+def _u8(jpeg) -> np.ndarray:
+    return np.frombuffer(jpeg, np.uint8) if isinstance(jpeg, (bytes, bytearray, memoryview)) else np.ascontiguousarray(jpeg, np.uint8).reshape(-1)
+
+
+def parse(jpeg) -> dict:
+    """The headers of one JPEG file: ``H W ncomp sampling Ri M nI tables scan_offset scan_length status`` and, for a file the
+    decoder refuses (``status`` 6), ``why``.  No entropy decoding."""
+    a = _u8(jpeg)
+    info = _Info()
+    check(lib().og_jpegd_parse_host(ptr(a) if a.size else C.c_void_p(C.addressof(info)), a.size, C.addressof(info)), "og_jpegd_parse_host")
+    d = {n: int(getattr(info, n)) for n, _ in _Info._fields_ if n != "reserved"}
+    if d["status"]:
+        d["why"] = (lib().og_last_error() or b"").decode()
+    return d
+
+
+def decode_host(jpeg, statuses: bool = False):
+    """One JPEG file -> ``[H,W,3]`` u8 BGR on the CPU: the bytes the device produces (and, inside the header's bound, Pillow's).
+    ``statuses=True`` returns ``(frame or None, status)`` instead of raising on a non-zero status."""
+    a = _u8(jpeg)
+    info = parse(a)
+    if info["status"]:
+        if statuses:
+            return None, info["status"]
+        raise OpenGlottalHipError(f"the JPEG decoder refuses the file: {info['why']}")
+    out = np.empty((info["H"], info["W"], 3), np.uint8)
+    st = C.c_int(-1)
+    check(lib().og_jpegd_decode_host(ptr(a), a.size, ptr(out), out.size, C.addressof(st)), "og_jpegd_decode_host")
+    if statuses:
+        return out, st.value
+    if st.value:
+        raise OpenGlottalHipError(f"the JPEG file is damaged: {STATUS.get(st.value, st.value)}")
+    return out
+
+
+def _pack(jpegs):
+    """``(blob u8, offsets int64 [B + 1])`` of a list of files."""
+    parts = [_u8(j) for j in jpegs]
+    offsets = np.zeros(len(parts) + 1, np.int64)
+    np.cumsum([p.size for p in parts], out=offsets[1:])
+    blob = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+    return (blob if blob.size else np.zeros(1, np.uint8)), offsets
+
+
+def records_host(jpegs):
+    """What the resident entry needs beside the bytes: ``(blob, offsets, recs int32 [B,8], tabs u8 [nsets, limit(3)], form)`` with
+    ``form = dict(H, W, sampling, Ri)`` of the first file the parser accepts."""
+    blob, offsets = _pack(jpegs)
+    B = offsets.size - 1
+    recs = np.zeros((B, 8), np.int32)
+    tabs = np.zeros((max(B, 1), decode_limit(3)), np.uint8)
+    out = (C.c_int * 5)()
+    p = [C.addressof(out) + 4 * i for i in range(5)]
+    check(lib().og_jpegd_records_host(ptr(blob), ptr(offsets), B, ptr(recs), ptr(tabs), tabs.shape[0], *p), "og_jpegd_records_host")
+    return blob, offsets, recs, tabs[:out[0]].copy(), {"H": out[1], "W": out[2], "sampling": out[3], "Ri": out[4]}
+
+
+class MjpegDecoder:
+    """One ``og_mjpd`` handle: baseline JPEG files in, BGR frames out, decoded on the device.  All files of one call have one size,
+    one sampling form and one restart interval (the first accepted file's)."""
+
+    def __init__(self, chunk: int = 128):
+        self._h = lib().og_mjpd_create()
+        if not self._h:
+            raise OpenGlottalHipError("og_mjpd_create failed")
+        self.set_chunk(chunk)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                lib().og_mjpd_destroy(h)
+            except Exception:
+                pass
+
+    def set_chunk(self, chunk: int) -> None:
+        check(lib().og_mjpd_set_chunk(self._h, int(chunk)), "og_mjpd_set_chunk")
+        self.chunk = int(chunk)
+
+    def sync(self) -> None:
+        check(lib().og_mjpd_sync(self._h), "og_mjpd_sync")
+
+    @staticmethod
+    def _raise(status, jpegs) -> None:
+        bad = np.flatnonzero(status)
+        if bad.size:
+            i = int(bad[0])
+            why = STATUS.get(int(status[i]), str(int(status[i])))
+            if status[i] == 6:
+                why += ": " + parse(jpegs[i]).get("why", "")
+            raise OpenGlottalHipError(f"frame {i} of {len(status)} was not decoded (status {int(status[i])}): {why}")
+
+    def _stream(self, jpegs, to_device: bool, statuses: bool):
+        jpegs = list(jpegs)
+        B = len(jpegs)
+        first = next((i for i in (parse(j) for j in jpegs) if not i["status"]), None)
+        H, W = (first["H"], first["W"]) if first else (0, 0)
+        status = np.zeros(B, np.int32)
+        blob, offsets = _pack(jpegs)
+        if to_device:
+            import torch
+
+            out = torch.empty((B, H, W, 3), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()   # (the handle runs on a stream of its own)
+            host, dev, cap = None, out.data_ptr() if out.numel() else None, out.numel()
+        else:
+            out = np.empty((B, H, W, 3), np.uint8)
+            host, dev, cap = ptr(out) if out.size else None, None, out.size
+        hw = (C.c_int * 2)()
+        if B and first:
+            check(lib().og_mjpd_decode_stream(self._h, ptr(blob), ptr(offsets), B, host, dev, cap, ptr(status), C.addressof(hw),
+                                              C.addressof(hw) + 4), "og_mjpd_decode_stream")
+        elif B:
+            status[:] = 6
+        if statuses:
+            return out, status
+        self._raise(status, jpegs)
+        return out
+
+    def decode(self, jpegs, statuses: bool = False):
+        """A list of JPEG files -> ``[B,H,W,3]`` u8 BGR on the host; only the compressed bytes go up.  Raises on the first frame with
+        a non-zero status unless ``statuses=True``, which returns ``(frames, status int32 [B])``."""
+        return self._stream(jpegs, False, statuses)
+
+    def decode_resident(self, jpegs, statuses: bool = False):
+        """The same, the frames staying on the device: a ``[B,H,W,3]`` u8 CUDA tensor that never visited the host."""
+        return self._stream(jpegs, True, statuses)
+
+    def set_tables(self, tabs, sampling: int, Ri: int) -> None:
+        t = np.ascontiguousarray(tabs, np.uint8)
+        check(lib().og_mjpd_set_tables(self._h, ptr(t), int(t.shape[0]) if t.ndim == 2 else 0, int(sampling), int(Ri)), "og_mjpd_set_tables")
+
+    def decode_dev(self, blob_dev, offsets_dev, recs_dev, B: int, H: int, W: int, frames_dev, cap: int, status_dev) -> None:
+        """Resident, asynchronous variant (torch CUDA tensors or raw ints) after ``set_tables``: see ``records_host``."""
+        check(lib().og_mjpd_decode_u8_dev(self._h, ptr(blob_dev), ptr(offsets_dev), ptr(recs_dev), B, H, W, ptr(frames_dev), int(cap),
+                                          ptr(status_dev)), "og_mjpd_decode_u8_dev")
+
+    def plan(self, B: int, H: int, W: int, sampling: int = 1, Ri: int = 16):
+        return decode_plan(B, H, W, sampling, Ri, self.chunk)
+
+
+def decode_plan(B: int, H: int, W: int, sampling: int = 1, Ri: int = 16, chunk: int = 128):
+    """Dry run of the streamed decode: ``(records, workspace_bytes)`` as ``plan`` gives them."""
+    out = C.create_string_buffer(1 << 20)
+    ws = C.c_longlong()
+    n = lib().og_mjpd_plan(B, H, W, sampling, Ri, chunk, out, len(out), C.byref(ws))
+    if n < 0:
+        check(n, "og_mjpd_plan")
+    names = ("kernel", "gx", "gy", "gz", "block", "lds", "workspace", "counters", "writes")
+    recs = [{k: (v if k in ("kernel", "writes") else int(v)) for k, v in zip(names, line.split("|"))} for line in out.value.decode().splitlines()]
+    assert len(recs) == n
+    return recs, ws.value
+
+
+def jpeg_files(path: str) -> list[bytes]:
+    """The compressed frames of an ``MJPG`` ``.avi`` file, or of a directory of ``.jpg`` / ``.jpeg`` files in name order."""
+    import os
+
+    if os.path.isdir(path):
+        names = sorted(n for n in os.listdir(path) if n.lower().endswith((".jpg", ".jpeg")))
+        if not names:
+            raise OpenGlottalHipError(f"{path} holds no .jpg files")
+        out = []
+        for n in names:
+            with open(os.path.join(path, n), "rb") as f:
+                out.append(f.read())
+        return out
+    handler, frames = avi_stream(path)
+    if handler is None or handler.upper() != b"MJPG":
+        raise OpenGlottalHipError(f"{path}: the video stream is {handler!r}, only MJPG is decoded")
+    return frames
+
+
+class CompressedVideo:
+    """The JPEG files of one video and the decoder that turns them into frames: what ``cli infer --decode device`` hands to the frame
+    loops in place of decoded frames.  ``len`` is the frame count, ``[i]`` one frame decoded by the host twin (for a size or a seed
+    frame), ``blocks_resident`` CUDA blocks that never visit the host, ``frames_host`` the whole video decoded block by block on the
+    device and collected on the host (the detector's frame loop reads host frames)."""
+
+    def __init__(self, files, decoder: MjpegDecoder | None = None):
+        self.files = list(files)
+        self.decoder = decoder if decoder is not None else MjpegDecoder()
+        info = parse(self.files[0]) if self.files else {"H": 0, "W": 0, "status": 0}
+        if info["status"]:
+            raise OpenGlottalHipError(f"the JPEG decoder refuses the first frame: {info['why']}")
+        self.H, self.W = info["H"], info["W"]
+        self.compressed_bytes = sum(len(f) for f in self.files)
+
+    def __len__(self) -> int:
+        return len(self.files)
+
+    def __getitem__(self, i):
+        return decode_host(self.files[i])
+
+    def blocks(self, block: int, resident: bool = False):
+        """``(first frame index, frames)`` per block of ``block`` files: the one loop that hands files to the decoder."""
+        for b0 in range(0, len(self.files), int(block)):
+            part = self.files[b0:b0 + int(block)]
+            yield b0, (self.decoder.decode_resident(part) if resident else self.decoder.decode(part))
+
+    def blocks_resident(self, block: int):
+        for _, frames in self.blocks(block, True):
+            yield frames
+
+    def frames_host(self, block: int = 1024) -> np.ndarray:
+        if not self.files:
+            return np.zeros((0, 0, 0, 3), np.uint8)
+        out = np.empty((len(self.files), self.H, self.W, 3), np.uint8)
+        for b0, frames in self.blocks(block):
+            out[b0:b0 + len(frames)] = frames
+        return out
+
+def iter_avi_blocks(path: str, block: int, decoder: MjpegDecoder, resident: bool = False):
+    """``(first frame index, frames)`` per block of ``block`` frames of an ``MJPG`` AVI (or a directory of ``.jpg`` files), decoded on
+    the device (``CompressedVideo.blocks``); the decoded video is never held in host memory as a whole.  ``resident``: the blocks are
+    CUDA tensors."""
+    return CompressedVideo(jpeg_files(path), decoder).blocks(block, resident)
+
+
+def open_compressed(path: str, mode: str = "device"):
+    """``CompressedVideo`` of an ``MJPG`` ``.avi`` or a directory of ``.jpg`` frames for ``--decode device``; with ``mode="auto"``
+    ``None`` -- and one line on stderr saying why -- when the parser refuses the first frame, so that the caller takes the host loop."""
+    import sys
+
+    try:
+        return CompressedVideo(jpeg_files(path))
+    except OpenGlottalHipError as e:
+        if mode != "auto":
+            raise
+        print(f"--decode auto: {path} is decoded on the host: {e}", file=sys.stderr)
+        return None

@@ -64,6 +64,10 @@ def _decode_flag(r) -> None:
                    help="host (default): videos are decoded on the host, as until now; device: an MJPG .avi (or a directory of .jpg "
                         "frames of one size) goes to the device compressed and is decoded there (baseline JPEG only); auto: device, "
                         "and the host loop, with one line on stderr, when the decoder refuses the first frame")
+    r.add_argument("--decode-split", choices=["off", "auto"], default="off",
+                   help="with --decode device or auto.  off (default): a lane per restart interval, so a file without restart markers "
+                        "(OpenCV's, FFmpeg's and Pillow's default) is one lane per frame; auto: such files are decoded by many lanes "
+                        "that synchronise themselves (the same bytes), files with markers as before")
 
 
 def _infer_jobs(a):
@@ -86,7 +90,7 @@ def _infer_jobs(a):
 
             video = None
             if all(p.lower().endswith((".jpg", ".jpeg")) for p in paths):
-                video = open_compressed(a.input, a.decode)
+                video = open_compressed(a.input, a.decode, a.decode_split)
             elif a.decode == "auto":
                 print(f"--decode auto: {a.input} is decoded on the host: it holds images that are no .jpg files", file=sys.stderr)
             else:
@@ -107,7 +111,7 @@ def _infer_jobs(a):
             if a.decode != "host":
                 from .mjpeg import open_compressed
 
-                video = open_compressed(p, a.decode)
+                video = open_compressed(p, a.decode, a.decode_split)
             yield os.path.splitext(os.path.basename(p))[0], video if video is not None else load_frames_bgr(p)
 
 
@@ -358,7 +362,7 @@ def _decoded_on_device(a):
 
     if str(a.video).endswith((".npy", ".npz")):
         raise SystemExit(f"--decode {a.decode} is for compressed input (an MJPG .avi or a directory of .jpg frames), not {a.video}")
-    video = open_compressed(str(a.video), a.decode)
+    video = open_compressed(str(a.video), a.decode, a.decode_split)
     return a.video if video is None else video.frames_host()
 
 

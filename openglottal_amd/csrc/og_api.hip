@@ -1661,6 +1661,7 @@ static void bgr2gray_host_loop(const uint8_t* __restrict__ bgr, long long n, uin
 #include "og_sweep.inc"
 #include "og_mjpeg.inc"
 #include "og_mjpd.inc"
+#include "og_mjps.inc"
 
 extern "C" {
 

@@ -3,6 +3,8 @@
 // its own: one stream, the workspace of ONE micro-batch, two pinned host slots.  Per micro-batch: k_mjpd_markers (the restart
 // intervals of every frame), k_mjpd_entropy (a lane per interval: coefficients), k_mjpd_idct (component planes), k_mjpd_colour (BGR).
 // All arithmetic is integer: the host twin and the kernels call the same inline functions and agree byte for byte.
+// og_mjps.inc (included after this file) replaces k_mjpd_entropy for calls without restart markers when the handle asks for it; it
+// restarts the bit reader below through og_jpegd_seek / og_jpegd_tell.
 // With OG_MJPD_HOST_ONLY defined the file is a translation unit of its own for a host compiler: the parser and the twin, no HIP
 // (tools/mjpd_host_fuzz.cpp builds it under sanitizers).
 #include "../../include/decode/openglottal_hip_mjpd.h"
@@ -122,6 +124,32 @@ OG_JPEG_HD int og_jpegd_receive(OgJpegdBits& s, int n, int* st) {
     const int v = (int)og_jpegd_peek(s, n);
     s.nb -= n;
     return v < (1 << (n - 1)) ? v - (1 << n) + 1 : v;
+}
+
+// The reader restarted at a position: the next bit is bit `bit` (0 the highest) of data byte p[pos], which is no stuffed 00.
+OG_JPEG_HD void og_jpegd_seek(OgJpegdBits& s, const uint8_t* p, long long n, long long pos, int bit) {
+    s.p = p;
+    s.n = n;
+    s.pos = pos;
+    s.acc = 0;
+    s.nb = 0;
+    if (bit) {
+        og_jpegd_fill(s);
+        s.nb = s.nb > bit ? s.nb - bit : 0;
+    }
+}
+
+// Where the reader stands, in og_jpegd_seek's terms.  The nb bits not yet consumed end the last ceil(nb / 8) data bytes before
+// s.pos; a data byte is never a 00 behind an FF (that 00 was skipped as stuffing), so the walk back steps over such pairs.  It reads
+// only bytes the reader has read.
+OG_JPEG_HD void og_jpegd_tell(const OgJpegdBits& s, long long* pos, int* bit) {
+    long long q = s.pos;
+    for (int left = (s.nb + 7) >> 3; left > 0; --left) {
+        q -= 1;
+        if (q >= 1 && s.p[q] == 0 && s.p[q - 1] == 0xFF) q -= 1;
+    }
+    *pos = q;
+    *bit = (8 - (s.nb & 7)) & 7;
 }
 
 // One restart interval: MCUs [m0, m0 + count) of a frame whose coefficients ([component][block][64] int16, natural order, zero before
@@ -400,6 +428,10 @@ __global__ __launch_bounds__(256) void k_mjpd_colour(const uint8_t* __restrict__
     dst[1] = px[1];
     dst[2] = px[2];
 }
+// og_mjps.inc: a workgroup per frame decodes a scan without restart markers in parallel
+__global__ void k_mjps_entropy(const uint8_t* __restrict__ blob, const long long* __restrict__ offsets, const og_mjpd_rec* __restrict__ recs,
+                               const MjpdTab* __restrict__ tabs, MjpdForm g, int sub, const int* __restrict__ mstat, int16_t* __restrict__ coefs,
+                               int32_t* __restrict__ status);
 #endif   // OG_MJPD_HOST_ONLY
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
@@ -409,6 +441,7 @@ struct og_mjpd {
     bool ready = false;   // the stream exists
     hipStream_t stream = nullptr;
     int chunk = 128;
+    int split = 0, sub = 0;   // og_mjps_set_split (og_mjps.inc): 1 sends calls with Ri == 0 through k_mjps_entropy; sub 0 is the default
     MjpdTab* d_tabs = nullptr;
     size_t cap_tabs = 0;
     int nsets = 0, sampling = -1, Ri = 0;   // what d_tabs holds, and the form of the resident calls
@@ -699,23 +732,12 @@ int mjpd_markers_host(const uint8_t* p, int n, int nI, int* ivl) {
     return (k != nI - 1 || bad) ? 5 : 0;
 }
 
-// the twin of one micro-batch's work on one accepted frame: status and H * W * 3 bytes
-int mjpd_frame_host(const uint8_t* jpeg, const og_jpegd_info& info, const MjpdTab& tab, uint8_t* out) {
-    MjpdForm g;
-    mjpd_form(info.H, info.W, info.sampling, &g);
-    std::vector<int16_t> coefs((size_t)g.blocks * 64, 0);
-    std::vector<int> ivl((size_t)info.nI * 2, 0);
-    const uint8_t* scan = jpeg + info.scan_offset;
-    int st = mjpd_markers_host(scan, (int)info.scan_length, info.nI, ivl.data());
-    if (!st)
-        for (int k = 0; k < info.nI; ++k) {
-            const int m0 = info.Ri ? k * info.Ri : 0, count = info.Ri ? std::min(info.Ri, g.M - m0) : g.M;
-            st = std::max(st, og_jpegd_interval(scan + ivl[2 * k], (long long)ivl[2 * k + 1] - ivl[2 * k], &tab, g, m0, count, coefs.data()));
-        }
+// what k_mjpd_idct and k_mjpd_colour do to one frame's coefficients: H * W * 3 bytes
+void mjpd_pixels_host(const int16_t* coefs, const MjpdTab& tab, const MjpdForm& g, uint8_t* out) {
     std::vector<uint8_t> planes((size_t)g.blocks * 64);
     for (int c = 0; c < g.ncomp; ++c)
         for (int lb = 0; lb < g.bw[c] * g.bh[c]; ++lb) {
-            const int16_t* src = coefs.data() + ((size_t)g.boff[c] + lb) * 64;
+            const int16_t* src = coefs + ((size_t)g.boff[c] + lb) * 64;
             int ws[64], in[8], o[8];
             for (int r = 0; r < 8; ++r) {
                 for (int k = 0; k < 8; ++k) in[k] = (int)src[8 * k + r] * (int)tab.q[c][8 * k + r];
@@ -731,6 +753,22 @@ int mjpd_frame_host(const uint8_t* jpeg, const og_jpegd_info& info, const MjpdTa
         }
     for (int y = 0; y < g.H; ++y)
         for (int x = 0; x < g.W; ++x) og_jpegd_pixel(planes.data(), g, y, x, out + ((size_t)y * g.W + x) * 3);
+}
+
+// the twin of one micro-batch's work on one accepted frame: status and H * W * 3 bytes
+int mjpd_frame_host(const uint8_t* jpeg, const og_jpegd_info& info, const MjpdTab& tab, uint8_t* out) {
+    MjpdForm g;
+    mjpd_form(info.H, info.W, info.sampling, &g);
+    std::vector<int16_t> coefs((size_t)g.blocks * 64, 0);
+    std::vector<int> ivl((size_t)info.nI * 2, 0);
+    const uint8_t* scan = jpeg + info.scan_offset;
+    int st = mjpd_markers_host(scan, (int)info.scan_length, info.nI, ivl.data());
+    if (!st)
+        for (int k = 0; k < info.nI; ++k) {
+            const int m0 = info.Ri ? k * info.Ri : 0, count = info.Ri ? std::min(info.Ri, g.M - m0) : g.M;
+            st = std::max(st, og_jpegd_interval(scan + ivl[2 * k], (long long)ivl[2 * k + 1] - ivl[2 * k], &tab, g, m0, count, coefs.data()));
+        }
+    mjpd_pixels_host(coefs.data(), tab, g, out);
     return st;
 }
 
@@ -791,6 +829,10 @@ int check_mjpd_shape(int H, int W) {
 }
 
 #ifndef OG_MJPD_HOST_ONLY
+// og_mjps.inc: the split entropy pass, its static LDS, and the subsequence length a handle's mode asks for (0: the lane per interval)
+int mjps_lds_bytes();
+int mjps_sub_of(int mode, int sub, int Ri);
+
 int mjpd_ready(og_mjpd* h) {
     if (h->ready) return OG_OK;
     HIPCHK(hipGetDevice(&h->device));
@@ -850,8 +892,9 @@ int mjpd_upload_tabs(og_mjpd* h, const MjpdTab* tabs, int nsets, int sampling, i
 }
 
 // One micro-batch of nb resident files.  ws: the handle's workspace (a placeholder in a dry run).  frames, status: of these nb frames.
+// sub > 0 (only with Ri == 0): the entropy pass is k_mjps_entropy at that subsequence length (og_mjps.inc).
 int mjpd_batch(hipStream_t st, uint8_t* ws, const MjpdTab* tabs, int nsets, const uint8_t* blob, const long long* offsets,
-               const og_mjpd_rec* recs, int nb, const MjpdForm& g, int Ri, uint8_t* frames, int32_t* status) {
+               const og_mjpd_rec* recs, int nb, const MjpdForm& g, int Ri, int sub, uint8_t* frames, int32_t* status) {
     const int nI = mjpd_intervals(g, Ri);
     const long long nblocks = (long long)nb * g.blocks, items = (long long)nb * nI;
     int16_t* coefs = (int16_t*)ws;
@@ -862,10 +905,14 @@ int mjpd_batch(hipStream_t st, uint8_t* ws, const MjpdTab* tabs, int nsets, cons
     plan_need((long long)nb * mjpd_frame_ws(g, nI), 0);
     OG_LAUNCH(k_mjpd_markers, dim3((unsigned)nb), dim3(256), 0, st, blob, offsets, recs, nsets, nI, Ri, ivl, mstat, status);
     if (g_plan) plan_write("status", status, (long long)nb * 4);
-    OG_LAUNCH(k_mjpd_entropy, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, st, blob, offsets, recs, tabs, g, nI, Ri, items, (const int*)ivl, (const int*)mstat,
-              coefs, status);
+    if (sub > 0 && Ri == 0) {
+        OG_LAUNCH(k_mjps_entropy, dim3((unsigned)nb), dim3(256), 0, st, blob, offsets, recs, tabs, g, sub, (const int*)mstat, coefs, status);
+    } else {
+        OG_LAUNCH(k_mjpd_entropy, dim3((unsigned)((items + 63) / 64)), dim3(64), 0, st, blob, offsets, recs, tabs, g, nI, Ri, items, (const int*)ivl,
+                  (const int*)mstat, coefs, status);
+    }
     if (g_plan) {
-        g_plan->recs.back().lds = (unsigned)sizeof(MjpdTab);   // static LDS: stated, so that the plan tells the truth
+        g_plan->recs.back().lds = sub > 0 && Ri == 0 ? (unsigned)mjps_lds_bytes() : (unsigned)sizeof(MjpdTab);   // static LDS: stated, so that the plan tells the truth
         plan_write("status", status, (long long)nb * 4);
     }
     OG_LAUNCH(k_mjpd_idct, dim3((unsigned)((nblocks + 31) / 32)), dim3(256), kMjpdIdctLds, st, (const int16_t*)coefs, nblocks, g, recs, tabs, nsets,
@@ -1028,7 +1075,7 @@ int og_mjpd_decode_u8_dev(og_mjpd* h, const uint8_t* blob_dev, const int64_t* of
     for (int b0 = 0; b0 < B && !rc; b0 += chunk) {
         const int nb = (B - b0 < chunk) ? B - b0 : chunk;
         rc = mjpd_batch(h->stream, h->d_ws, h->d_tabs, h->nsets, blob_dev, (const long long*)offsets_dev + b0, recs_dev + b0, nb, g, h->Ri,
-                        frames_dev + b0 * fb, status_dev + b0);
+                        mjps_sub_of(h->split, h->sub, h->Ri), frames_dev + b0 * fb, status_dev + b0);
     }
     if (rc) mjpd_drain(h);
     return rc;
@@ -1108,7 +1155,8 @@ int og_mjpd_decode_stream(og_mjpd* h, const uint8_t* blob, const int64_t* offset
         HIPCHK(hipMemcpyAsync(h->d_in, s.h_in, head + nbytes, hipMemcpyHostToDevice, st));
         uint8_t* dst = own_out ? h->d_out : frames_out_dev_or_null + (size_t)b0 * fb;
         const int rc2 = mjpd_batch(st, h->d_ws, h->d_tabs, h->nsets, h->d_in + head, (const long long*)h->d_in,
-                                   (const og_mjpd_rec*)(h->d_in + (size_t)(nb + 1) * 8), nb, g, call.Ri, dst, (int32_t*)h->d_status);
+                                   (const og_mjpd_rec*)(h->d_in + (size_t)(nb + 1) * 8), nb, g, call.Ri, mjps_sub_of(h->split, h->sub, call.Ri), dst,
+                                   (int32_t*)h->d_status);
         if (rc2) return rc2;
         if (to_host) HIPCHK(hipMemcpyAsync(s.h_out, dst, (size_t)nb * fb, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(s.h_status, h->d_status, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
@@ -1138,7 +1186,11 @@ int og_mjpd_decode_stream(og_mjpd* h, const uint8_t* blob, const int64_t* offset
     return OG_OK;
 }
 
-int og_mjpd_plan(int B, int H, int W, int sampling, int Ri, int chunk, char* out, size_t cap, long long* workspace_bytes) {
+}  // extern "C"
+
+namespace {
+// og_mjpd_plan, and og_mjps_plan (og_mjps.inc) with a subsequence length
+int mjpd_plan_text(int B, int H, int W, int sampling, int Ri, int chunk, int sub, char* out, size_t cap, long long* workspace_bytes) {
     if (!out || cap == 0 || B < 1) return fail(OG_EINVAL, "bad argument");
     int rc = check_mjpd_shape(H, W);
     if (rc) return rc;
@@ -1161,7 +1213,7 @@ int og_mjpd_plan(int B, int H, int W, int sampling, int Ri, int chunk, char* out
     for (int b0 = 0; b0 < B && !rc; b0 += mb) {
         const int nb = (B - b0 < mb) ? B - b0 : mb;
         rc = mjpd_batch(nullptr, (uint8_t*)(3 * gap), (const MjpdTab*)(4 * gap), 1, (const uint8_t*)(5 * gap), (const long long*)(6 * gap),
-                        (const og_mjpd_rec*)(7 * gap), nb, g, Ri, frames + b0 * fb, status + b0);
+                        (const og_mjpd_rec*)(7 * gap), nb, g, Ri, sub, frames + b0 * fb, status + b0);
     }
     g_plan = nullptr;
     if (rc) return rc;
@@ -1173,6 +1225,13 @@ int og_mjpd_plan(int B, int H, int W, int sampling, int Ri, int chunk, char* out
     if (txt.size() + 1 > cap) return fail(OG_EINVAL, "plan text does not fit the buffer");
     memcpy(out, txt.c_str(), txt.size() + 1);
     return (int)plan.recs.size();
+}
+}  // namespace
+
+extern "C" {
+
+int og_mjpd_plan(int B, int H, int W, int sampling, int Ri, int chunk, char* out, size_t cap, long long* workspace_bytes) {
+    return mjpd_plan_text(B, H, W, sampling, Ri, chunk, 0, out, cap, workspace_bytes);
 }
 #endif   // OG_MJPD_HOST_ONLY
 

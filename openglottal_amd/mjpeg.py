@@ -298,6 +298,7 @@ def read_avi_mjpeg(path: str) -> list[np.ndarray]:
 STATUS = {0: "ok", 1: "truncated scan", 2: "invalid Huffman code", 3: "coefficient index past 63", 4: "value outside the baseline range",
           5: "restart marker count or order", 6: "unsupported form", 7: "size, sampling or restart interval differ from the call's"}
 SAMPLING = {0: "gray", 1: "4:4:4", 2: "4:2:2", 3: "4:2:0"}
+SPLIT = {"off": 0, "auto": 1}   # og_mjps_set_split's mode
 
 
 class _Info(C.Structure):
@@ -344,6 +345,35 @@ def decode_host(jpeg, statuses: bool = False):
     return out
 
 
+def split_limit(which: int) -> int:
+    """``og_mjps_limit``: 0 the default ``sub``, 1 and 2 its bounds, 3 lanes per window, 4 bytes of a window, 5 the kernel's LDS."""
+    return int(lib().og_mjps_limit(which))
+
+
+def decode_split_host(jpeg, sub: int = 0, lanes: int = 256, statuses: bool = False, stats: bool = False):
+    """``decode_host`` through the split entropy pass (include/split/openglottal_hip_mjps.h), the lanes walked in a loop: the same
+    frame and status for every file.  ``sub``: bytes per lane (0: the default), ``lanes``: per window.  ``stats=True`` appends
+    ``dict(lanes, windows, rounds, decodes)`` to the result."""
+    a = _u8(jpeg)
+    info = parse(a)
+    counts = np.zeros(4, np.int32)
+    names = ("lanes", "windows", "rounds", "decodes")
+    if info["status"]:
+        if not statuses:
+            raise OpenGlottalHipError(f"the JPEG decoder refuses the file: {info['why']}")
+        return (None, info["status"], dict(zip(names, [0] * 4))) if stats else (None, info["status"])
+    out = np.empty((info["H"], info["W"], 3), np.uint8)
+    st = C.c_int(-1)
+    check(lib().og_jpegs_decode_host(ptr(a), a.size, int(sub), int(lanes), ptr(out), out.size, C.addressof(st), ptr(counts)),
+          "og_jpegs_decode_host")
+    if not statuses and st.value:
+        raise OpenGlottalHipError(f"the JPEG file is damaged: {STATUS.get(st.value, st.value)}")
+    res = (out, st.value) if statuses else (out,)
+    if stats:
+        res += ({k: int(v) for k, v in zip(names, counts)},)
+    return res if len(res) > 1 else res[0]
+
+
 def _pack(jpegs):
     """``(blob u8, offsets int64 [B + 1])`` of a list of files."""
     parts = [_u8(j) for j in jpegs]
@@ -370,11 +400,12 @@ class MjpegDecoder:
     """One ``og_mjpd`` handle: baseline JPEG files in, BGR frames out, decoded on the device.  All files of one call have one size,
     one sampling form and one restart interval (the first accepted file's)."""
 
-    def __init__(self, chunk: int = 128):
+    def __init__(self, chunk: int = 128, split: str = "off", sub=None):
         self._h = lib().og_mjpd_create()
         if not self._h:
             raise OpenGlottalHipError("og_mjpd_create failed")
         self.set_chunk(chunk)
+        self.set_split(split, sub)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -387,6 +418,14 @@ class MjpegDecoder:
     def set_chunk(self, chunk: int) -> None:
         check(lib().og_mjpd_set_chunk(self._h, int(chunk)), "og_mjpd_set_chunk")
         self.chunk = int(chunk)
+
+    def set_split(self, split: str = "off", sub=None) -> None:
+        """``"off"`` (the default): a lane per restart interval.  ``"auto"``: files WITHOUT restart markers are decoded by
+        ``k_mjps_entropy``, ``sub`` bytes per lane (``None``: the measured default); files with markers are decoded as before."""
+        if split not in SPLIT:
+            raise OpenGlottalHipError(f"split must be one of {sorted(SPLIT)}, got {split!r}")
+        check(lib().og_mjps_set_split(self._h, SPLIT[split], int(sub or 0)), "og_mjps_set_split")
+        self.split, self.sub = split, int(sub or 0)
 
     def sync(self) -> None:
         check(lib().og_mjpd_sync(self._h), "og_mjpd_sync")
@@ -447,16 +486,20 @@ class MjpegDecoder:
                                           ptr(status_dev)), "og_mjpd_decode_u8_dev")
 
     def plan(self, B: int, H: int, W: int, sampling: int = 1, Ri: int = 16):
-        return decode_plan(B, H, W, sampling, Ri, self.chunk)
+        return decode_plan(B, H, W, sampling, Ri, self.chunk, self.split, self.sub)
 
 
-def decode_plan(B: int, H: int, W: int, sampling: int = 1, Ri: int = 16, chunk: int = 128):
-    """Dry run of the streamed decode: ``(records, workspace_bytes)`` as ``plan`` gives them."""
+def decode_plan(B: int, H: int, W: int, sampling: int = 1, Ri: int = 16, chunk: int = 128, split: str = "off", sub: int = 0):
+    """Dry run of the streamed decode: ``(records, workspace_bytes)`` as ``plan`` gives them.  ``split`` other than ``"off"`` goes
+    through ``og_mjps_plan``."""
     out = C.create_string_buffer(1 << 20)
     ws = C.c_longlong()
-    n = lib().og_mjpd_plan(B, H, W, sampling, Ri, chunk, out, len(out), C.byref(ws))
+    if split == "off":
+        n, what = lib().og_mjpd_plan(B, H, W, sampling, Ri, chunk, out, len(out), C.byref(ws)), "og_mjpd_plan"
+    else:
+        n, what = lib().og_mjps_plan(B, H, W, sampling, Ri, chunk, SPLIT.get(split, -1), int(sub or 0), out, len(out), C.byref(ws)), "og_mjps_plan"
     if n < 0:
-        check(n, "og_mjpd_plan")
+        check(n, what)
     names = ("kernel", "gx", "gy", "gz", "block", "lds", "workspace", "counters", "writes")
     recs = [{k: (v if k in ("kernel", "writes") else int(v)) for k, v in zip(names, line.split("|"))} for line in out.value.decode().splitlines()]
     assert len(recs) == n
@@ -528,13 +571,14 @@ def iter_avi_blocks(path: str, block: int, decoder: MjpegDecoder, resident: bool
     return CompressedVideo(jpeg_files(path), decoder).blocks(block, resident)
 
 
-def open_compressed(path: str, mode: str = "device"):
+def open_compressed(path: str, mode: str = "device", split: str = "off"):
     """``CompressedVideo`` of an ``MJPG`` ``.avi`` or a directory of ``.jpg`` frames for ``--decode device``; with ``mode="auto"``
-    ``None`` -- and one line on stderr saying why -- when the parser refuses the first frame, so that the caller takes the host loop."""
+    ``None`` -- and one line on stderr saying why -- when the parser refuses the first frame, so that the caller takes the host loop.
+    ``split``: ``--decode-split``, the decoder's ``set_split``."""
     import sys
 
     try:
-        return CompressedVideo(jpeg_files(path))
+        return CompressedVideo(jpeg_files(path), MjpegDecoder(split=split))
     except OpenGlottalHipError as e:
         if mode != "auto":
             raise

@@ -1652,6 +1652,7 @@ static void bgr2gray_host_loop(const uint8_t* __restrict__ bgr, long long n, uin
         gray[i] = (uint8_t)((bgr[3 * i] * 3735 + bgr[3 * i + 1] * 19235 + bgr[3 * i + 2] * 9798 + (1 << 14)) >> 15);
 }
 
+#include "og_stream.inc"
 #include "og_yolo.inc"
 #include "og_crops.inc"
 #include "og_classic.inc"
@@ -2786,13 +2787,7 @@ int og_unet_plan(const int* features, int n_levels, int B, int H, int W, int lan
     }
     og_unet_destroy(h);
     if (rc) return rc;
-    std::string txt;
-    for (auto& r : plan.recs)
-        txt += r.kernel + "|" + std::to_string(r.gx) + "|" + std::to_string(r.gy) + "|" + std::to_string(r.gz) + "|" + std::to_string(r.block) + "|" +
-               std::to_string(r.lds) + "|" + std::to_string(r.partial_bytes) + "|" + std::to_string(r.counters) + "\n";
-    if (txt.size() + 1 > cap) return fail(OG_EINVAL, "plan text does not fit the buffer");
-    memcpy(out, txt.c_str(), txt.size() + 1);
-    return (int)plan.recs.size();
+    return og_plan_text(plan, kPlanNoLast, out, cap);
 }
 
 int og_unet_plan_resized(const int* features, int n_levels, int B, int H, int W, int channels, int net_h, int net_w, int lanes,
@@ -2835,14 +2830,7 @@ int og_unet_plan_resized(const int* features, int n_levels, int B, int H, int W,
     }
     og_unet_destroy(h);
     if (rc) return rc;
-    std::string txt;
-    for (auto& r : plan.recs)
-        txt += r.kernel + "|" + std::to_string(r.gx) + "|" + std::to_string(r.gy) + "|" + std::to_string(r.gz) + "|" + std::to_string(r.block) + "|" +
-               std::to_string(r.lds) + "|" + std::to_string(r.partial_bytes) + "|" + std::to_string(r.counters) + "|" +
-               (r.writes.empty() ? "-" : r.writes) + "\n";
-    if (txt.size() + 1 > cap) return fail(OG_EINVAL, "plan text does not fit the buffer");
-    memcpy(out, txt.c_str(), txt.size() + 1);
-    return (int)plan.recs.size();
+    return og_plan_text(plan, kPlanWrites, out, cap);
 }
 
 long long og_workspace_limit(int which) { return which == 0 ? (long long)kPartialBytes : which == 1 ? kTileCounters : which == 2 ? 65535 : 160 * 1024; }

@@ -9,15 +9,12 @@
 #include "../../include/openglottal_hip_classic.h"
 #include "../../include/openglottal_hip_classic_tiled.h"
 
-struct og_classic {
-    int device = -1;
-    bool ready = false;   // stream and state word exist
-    hipStream_t stream = nullptr;
+struct og_classic : OgStreamHandle {
     double beta = 0.7, percentile = 30.0;
-    int n_comp = 2, chunk = 128;
+    int n_comp = 2;
     int tiled = 0;   // og_classic_set_tiled: 0 off, 1 auto, 2 always
     bool seeded = false;
-    double* d_state = nullptr;   // the running threshold
+    double* d_state = nullptr;   // the running threshold: made with the stream (classic_ready)
     // workspace of one micro-batch
     size_t cap_nb = 0, cap_px = 0, cap_in = 0;   // frames; pixels and source bytes of the whole micro-batch
     bool cap_mask = false, cap_sel = false;
@@ -39,11 +36,10 @@ struct og_classic {
         int32_t* h_area = nullptr;
         int32_t* h_T = nullptr;
         double* h_thresh = nullptr;
-        hipEvent_t ev_out = nullptr;
+        hipEvent_t ev = nullptr;
         int b0 = -1, nb = 0;
     } slots[2];
 };
-inline bool og_skip_device(const og_classic* h) { return !h || !h->ready; }
 
 namespace {
 
@@ -82,32 +78,23 @@ int check_classic(og_classic* h, int B, int H, int W, int ch) {
 }
 
 int classic_ready(og_classic* h) {
-    if (h->ready) return OG_OK;
-    HIPCHK(hipGetDevice(&h->device));
-    HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    if (h->d_state) return OG_OK;
+    const int rc = og_stream_ready(h);
+    if (rc) return rc;
     HIPCHK(hipMalloc((void**)&h->d_state, sizeof(double)));
-    h->ready = true;
     return OG_OK;
 }
 
 void classic_free_ws(og_classic* h) {
-    void* dev[] = {h->d_in, h->d_mask, h->d_la, h->d_lb, h->d_hist, h->d_boxes, h->d_thresh, h->d_cut, h->d_T, h->d_area, h->d_sel};
-    for (void* p : dev)
-        if (p) (void)hipFree(p);
-    h->d_in = h->d_mask = nullptr;
-    h->d_la = h->d_lb = nullptr;
-    h->d_hist = nullptr;
-    h->d_boxes = h->d_cut = h->d_T = h->d_area = h->d_sel = nullptr;
-    h->d_thresh = nullptr;
+    auto drop = [](bool pinned, auto*&... p) {   // free and forget: each pointer is listed once
+        ((void)(!p ? hipSuccess : pinned ? hipHostFree(p) : hipFree(p)), ...);
+        ((p = nullptr), ...);
+    };
+    drop(false, h->d_in, h->d_mask, h->d_la, h->d_lb, h->d_hist, h->d_boxes, h->d_thresh, h->d_cut, h->d_T, h->d_area, h->d_sel);
     for (auto& s : h->slots) {
-        void* host[] = {s.h_in, s.h_mask, s.h_boxes, s.h_area, s.h_T, s.h_thresh};
-        for (void* p : host)
-            if (p) (void)hipHostFree(p);
-        s.h_in = s.h_mask = nullptr;
-        s.h_boxes = s.h_area = s.h_T = nullptr;
-        s.h_thresh = nullptr;
-        if (s.ev_out) (void)hipEventDestroy(s.ev_out);
-        s.ev_out = nullptr;
+        drop(true, s.h_in, s.h_mask, s.h_boxes, s.h_area, s.h_T, s.h_thresh);
+        if (s.ev) (void)hipEventDestroy(s.ev);
+        s.ev = nullptr;
         s.b0 = -1;
     }
     h->cap_nb = h->cap_px = h->cap_in = 0;
@@ -120,7 +107,7 @@ void classic_free_ws(og_classic* h) {
 int classic_ensure(og_classic* h, int nb, int H, int W, size_t in, bool want_mask, bool host) {
     const bool want_sel = classic_tiled(h->tiled, H, W);
     const size_t px = (size_t)nb * H * W, inb = (size_t)nb * in;
-    const bool have_host = h->slots[0].ev_out != nullptr;
+    const bool have_host = h->slots[0].ev != nullptr;
     if ((size_t)nb <= h->cap_nb && px <= h->cap_px && inb <= h->cap_in && (!want_mask || h->cap_mask) && (!want_sel || h->cap_sel) &&
         (!host || have_host))
         return OG_OK;
@@ -149,7 +136,7 @@ int classic_ensure(og_classic* h, int nb, int H, int W, size_t in, bool want_mas
         if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_area, n * 4, hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_T, n * 4, hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_thresh, n * 8, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&s.ev, hipEventDisableTiming);
     }
     if (e != hipSuccess) {
         classic_free_ws(h);
@@ -251,14 +238,6 @@ int classic_otsu_batch(hipStream_t st, const ClassicWs& ws, int ch, const uint8_
     return OG_OK;
 }
 
-// after a failed call: wait for everything in flight, keep the message
-void classic_drain(og_classic* h) {
-    const std::string err = g_err;
-    if (h->ready) (void)hipStreamSynchronize(h->stream);
-    for (auto& s : h->slots) s.b0 = -1;
-    g_err = err;
-}
-
 // the host entries of both passes: micro-batches through the two pinned slots.  otsu: T instead of thresh, no state.
 int classic_stream_impl(og_classic* h, bool otsu, const uint8_t* frames, const uint8_t* const* frame_ptrs, int B, int H, int W, int ch,
                         const int32_t* boxes, uint8_t* mask, int32_t* area, double* thresh, int32_t* T) {
@@ -288,7 +267,7 @@ int classic_stream_impl(og_classic* h, bool otsu, const uint8_t* frames, const u
         if (s.b0 < 0) return OG_OK;
         const int b0 = s.b0, nb = s.nb;
         s.b0 = -1;
-        HIPCHK(hipEventSynchronize(s.ev_out));
+        HIPCHK(hipEventSynchronize(s.ev));
         memcpy(area + b0, s.h_area, (size_t)nb * 4);
         if (mask) memcpy(mask + b0 * HW, s.h_mask, nb * HW);
         if (thresh) memcpy(thresh + b0, s.h_thresh, (size_t)nb * 8);
@@ -311,24 +290,13 @@ int classic_stream_impl(og_classic* h, bool otsu, const uint8_t* frames, const u
         if (mask) HIPCHK(hipMemcpyAsync(s.h_mask, h->d_mask, nb * HW, hipMemcpyDeviceToHost, st));
         if (thresh) HIPCHK(hipMemcpyAsync(s.h_thresh, h->d_thresh, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
         if (T) HIPCHK(hipMemcpyAsync(s.h_T, h->d_T, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipEventRecord(s.ev_out, st));
+        HIPCHK(hipEventRecord(s.ev, st));
         s.b0 = b0;
         s.nb = nb;
         return OG_OK;
     };
 
-    int k = 0;
-    for (int b0 = 0; b0 < B && !rc; b0 += chunk, ++k) {
-        og_classic::Slot& s = h->slots[k & 1];
-        if ((rc = retire(s))) break;   // micro-batch k - 2 is complete and delivered: its pinned buffers are free
-        rc = fill(s, b0, (B - b0 < chunk) ? B - b0 : chunk);
-    }
-    for (int i = 0; i < 2; ++i) {   // in age order; on an error still wait for what is in flight
-        const int rc2 = retire(h->slots[(k + i) & 1]);
-        if (!rc) rc = rc2;
-    }
-    if (rc) classic_drain(h);
-    return rc;
+    return og_two_slot(B, chunk, h->slots, retire, fill, [h] { og_stream_drain(h); });
 }
 
 int classic_dev_impl(og_classic* h, bool otsu, const uint8_t* src, int B, int H, int W, int ch, const int32_t* boxes, uint8_t* mask,
@@ -357,7 +325,7 @@ int classic_dev_impl(og_classic* h, bool otsu, const uint8_t* src, int B, int H,
         if (!rc && thresh) HIPCHK(hipMemcpyAsync(thresh + b0, h->d_thresh, (size_t)nb * 8, hipMemcpyDeviceToDevice, h->stream));
         if (!rc && T) HIPCHK(hipMemcpyAsync(T + b0, h->d_T, (size_t)nb * 4, hipMemcpyDeviceToDevice, h->stream));
     }
-    if (rc) classic_drain(h);
+    if (rc) og_stream_drain(h);
     return rc;
 }
 
@@ -510,31 +478,15 @@ int og_classic_set_tiled(og_classic* h, int mode) {
 og_classic* og_classic_create(void) { return new og_classic(); }
 
 void og_classic_destroy(og_classic* h) {
-    if (!h) return;
-    DeviceGuard dg_(h->device, og_skip_device(h));
-    if (h->ready) {
-        (void)hipStreamSynchronize(h->stream);
+    og_stream_destroy(h, [h] {
         classic_free_ws(h);
         (void)hipFree(h->d_state);
-        (void)hipStreamDestroy(h->stream);
-    }
-    delete h;
+    });
 }
 
-int og_classic_sync(og_classic* h) {
-    if (!h) return fail(OG_EINVAL, "null handle");
-    if (!h->ready) return OG_OK;
-    OG_SCOPE(h);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return OG_OK;
-}
+int og_classic_sync(og_classic* h) { return og_stream_sync(h); }
 
-int og_classic_set_chunk(og_classic* h, int chunk) {
-    if (!h) return fail(OG_EINVAL, "null handle");
-    if (chunk < 1 || chunk > kClassicMaxChunk) return fail(OG_EINVAL, "chunk must be 1.." + std::to_string(kClassicMaxChunk));
-    h->chunk = chunk;
-    return OG_OK;
-}
+int og_classic_set_chunk(og_classic* h, int chunk) { return og_stream_set_chunk(h, chunk, kClassicMaxChunk); }
 
 int og_vft_guided_reset(og_classic* h, double beta, double percentile, int n_components) {
     if (!h) return fail(OG_EINVAL, "null handle");
@@ -641,7 +593,7 @@ int classic_plan_impl(int B, int H, int W, int channels, int chunk, int mode, ch
     tmp.tiled = mode;
     int rc = check_classic(&tmp, B, H, W, channels);
     if (rc) return rc;
-    if (chunk < 1 || chunk > kClassicMaxChunk) return fail(OG_EINVAL, "chunk must be 1.." + std::to_string(kClassicMaxChunk));
+    if ((rc = og_check_chunk(chunk, kClassicMaxChunk))) return rc;
     const int mb = classic_chunk(chunk, H, W, channels), cb = mb < B ? mb : B;
     if (workspace_bytes) *workspace_bytes = (long long)cb * classic_frame_bytes(H, W, channels, true, true, classic_tiled(mode, H, W)) + 8;
     const uintptr_t gap = (uintptr_t)1 << 40;   // placeholder bases: nothing dereferences them in a dry run
@@ -657,14 +609,7 @@ int classic_plan_impl(int B, int H, int W, int channels, int chunk, int mode, ch
                                (const int32_t*)(11 * gap), mask, area);
     g_plan = nullptr;
     if (rc) return rc;
-    std::string txt;
-    for (auto& r : plan.recs)
-        txt += r.kernel + "|" + std::to_string(r.gx) + "|" + std::to_string(r.gy) + "|" + std::to_string(r.gz) + "|" + std::to_string(r.block) + "|" +
-               std::to_string(r.lds) + "|" + std::to_string(r.partial_bytes) + "|" + std::to_string(r.counters) + "|" +
-               (r.writes.empty() ? "-" : r.writes) + "\n";
-    if (txt.size() + 1 > cap) return fail(OG_EINVAL, "plan text does not fit the buffer");
-    memcpy(out, txt.c_str(), txt.size() + 1);
-    return (int)plan.recs.size();
+    return og_plan_text(plan, kPlanWrites, out, cap);
 }
 }  // namespace
 

@@ -301,14 +301,7 @@ int og_unet_plan_crops(const int* features, int n_levels, int B, int H, int W, i
     }
     og_unet_destroy(h);
     if (rc) return rc;
-    std::string txt;
-    for (auto& r : plan.recs)
-        txt += r.kernel + "|" + std::to_string(r.gx) + "|" + std::to_string(r.gy) + "|" + std::to_string(r.gz) + "|" + std::to_string(r.block) + "|" +
-               std::to_string(r.lds) + "|" + std::to_string(r.partial_bytes) + "|" + std::to_string(r.counters) + "|" +
-               (r.writes.empty() ? "-" : r.writes) + "\n";
-    if (txt.size() + 1 > cap) return fail(OG_EINVAL, "plan text does not fit the buffer");
-    memcpy(out, txt.c_str(), txt.size() + 1);
-    return (int)plan.recs.size();
+    return og_plan_text(plan, kPlanWrites, out, cap);
 }
 
 }  // extern "C"

@@ -199,7 +199,8 @@ int gated_stream_impl(og_gated* g, const uint8_t* frames, const uint8_t* const* 
         if (mask) memcpy(mask + b0 * HW, s.h_mask, nb * HW);
         return OG_OK;
     };
-    auto fill = [&](og_gated::Slot& s, og_gated::Gate& k, int b0, int nb) -> int {
+    auto fill = [&](og_gated::Slot& s, int b0, int nb) -> int {
+        og_gated::Gate& k = g->gate[&s - g->slots];   // the slot's own dense buffers
         const uint8_t* src = frames ? frames + (size_t)b0 * fb : s.h_in;
         if (frame_ptrs) {
             for (int j = 0; j < nb; ++j) memcpy(s.h_in + (size_t)j * fb, frame_ptrs[b0 + j], fb);
@@ -248,16 +249,7 @@ int gated_stream_impl(og_gated* g, const uint8_t* frames, const uint8_t* const* 
         return OG_OK;
     };
 
-    int k = 0;
-    for (int b0 = 0; b0 < B && !rc; b0 += chunk, ++k) {
-        og_gated::Slot& s = g->slots[k & 1];
-        if ((rc = retire(s))) break;   // micro-batch k - 2 is complete and delivered: the slot's buffers are free
-        rc = fill(s, g->gate[k & 1], b0, (B - b0 < chunk) ? B - b0 : chunk);
-    }
-    for (int i = 0; i < 2; ++i) {   // in age order; on an error still wait for what is in flight
-        const int rc2 = retire(g->slots[(k + i) & 1]);
-        if (!rc) rc = rc2;
-    }
+    rc = og_two_slot(B, chunk, g->slots, retire, fill, [] {});
     gated_drain(g);   // a caller-pinned source may still be read by a copy whose micro-batch failed later; cheap when all is done
     if (rc) return rc;
     if (n_kept) *n_kept = (int32_t)total_kept;

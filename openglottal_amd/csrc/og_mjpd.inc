@@ -29,7 +29,6 @@ bool og_misaligned(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) !=
             return fail(OG_EINVAL, std::string(#ptr) + " must be aligned to " + std::to_string(alignof(decltype(*(ptr)))) + " bytes"); \
     } while (0)
 constexpr long long kMjpegMaxPixels = 1ll << 24;
-constexpr int kMjpegMaxChunk = 1024;
 constexpr long long kMjpegBatchBytes = 256ll << 20;
 #include "og_jpeg_annexk.inc"
 }  // namespace
@@ -37,6 +36,7 @@ extern "C" const char* og_last_error(void) { return g_err.c_str(); }
 #endif
 
 constexpr long long kMjpdMaxFile = 1ll << 30;
+constexpr int kMjpdMaxChunk = 1024;   // as the encoder's
 constexpr int kMjpdStatusMax = 7;
 
 // what the kernels read beside the bytes: one per distinct (DQT, DHT, component selectors) of a call, built on the host
@@ -436,31 +436,22 @@ __global__ void k_mjps_entropy(const uint8_t* __restrict__ blob, const long long
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
 #ifndef OG_MJPD_HOST_ONLY
-struct og_mjpd {
-    int device = -1;
-    bool ready = false;   // the stream exists
-    hipStream_t stream = nullptr;
-    int chunk = 128;
+struct og_mjpd : OgStreamHandle {
     int split = 0, sub = 0;   // og_mjps_set_split (og_mjps.inc): 1 sends calls with Ri == 0 through k_mjps_entropy; sub 0 is the default
-    MjpdTab* d_tabs = nullptr;
-    size_t cap_tabs = 0;
+    OgBuf<MjpdTab> d_tabs;
     int nsets = 0, sampling = -1, Ri = 0;   // what d_tabs holds, and the form of the resident calls
-    // per buffer the bytes of the largest micro-batch run so far
-    uint8_t* d_ws = nullptr;    // coefficients, planes, intervals
-    uint8_t* d_in = nullptr;    // streamed entry: offsets, records, bytes
-    uint8_t* d_out = nullptr;   // streamed entry: frames, unless the caller's device buffer takes them
-    uint8_t* d_status = nullptr;
-    size_t cap_ws = 0, cap_in = 0, cap_out = 0, cap_status = 0;
+    // each buffer holds the bytes of the largest micro-batch run so far
+    OgBuf<uint8_t> d_ws;    // coefficients, planes, intervals
+    OgBuf<uint8_t> d_in;    // streamed entry: offsets, records, bytes
+    OgBuf<uint8_t> d_out;   // streamed entry: frames, unless the caller's device buffer takes them
+    OgBuf<int32_t> d_status;
     struct Slot {
-        uint8_t* h_in = nullptr;
-        uint8_t* h_out = nullptr;
-        uint8_t* h_status = nullptr;
-        size_t cap_in = 0, cap_out = 0, cap_status = 0;
+        OgBuf<uint8_t> h_in{true}, h_out{true};
+        OgBuf<int32_t> h_status{true};
         hipEvent_t ev = nullptr;
         int b0 = -1, nb = 0;
     } slots[2];
 };
-inline bool og_skip_device(const og_mjpd* h) { return !h || !h->ready; }
 #endif
 
 namespace {
@@ -833,55 +824,18 @@ int check_mjpd_shape(int H, int W) {
 int mjps_lds_bytes();
 int mjps_sub_of(int mode, int sub, int Ri);
 
-int mjpd_ready(og_mjpd* h) {
-    if (h->ready) return OG_OK;
-    HIPCHK(hipGetDevice(&h->device));
-    HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    h->ready = true;
-    return OG_OK;
-}
-
-// grow one buffer to `need` bytes (never shrink); what it held is dropped, so the stream is drained first
-template <class T>
-int mjpd_grow(og_mjpd* h, T** p, size_t* cap, size_t need, bool pinned) {
-    if (need <= *cap && *p) return OG_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (*p) (void)(pinned ? hipHostFree(*p) : hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const size_t bytes = need ? need : 1;
-    const hipError_t e = pinned ? hipHostMalloc((void**)p, bytes, hipHostMallocDefault) : hipMalloc((void**)p, bytes);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        return fail(e == hipErrorOutOfMemory ? OG_ENOMEM : OG_EHIP, std::string("mjpd workspace: ") + hipGetErrorString(e));
-    }
-    *cap = bytes;
-    return OG_OK;
-}
-
 void mjpd_free(og_mjpd* h) {
-    void* dev[] = {h->d_tabs, h->d_ws, h->d_in, h->d_out, h->d_status};
-    for (void* p : dev)
-        if (p) (void)hipFree(p);
+    og_release(h->d_tabs, h->d_ws, h->d_in, h->d_out, h->d_status);
     for (auto& s : h->slots) {
-        void* host[] = {s.h_in, s.h_out, s.h_status};
-        for (void* p : host)
-            if (p) (void)hipHostFree(p);
+        og_release(s.h_in, s.h_out, s.h_status);
         if (s.ev) (void)hipEventDestroy(s.ev);
     }
-}
-
-void mjpd_drain(og_mjpd* h) {
-    const std::string err = g_err;
-    if (h->ready) (void)hipStreamSynchronize(h->stream);
-    for (auto& s : h->slots) s.b0 = -1;
-    g_err = err;
 }
 
 int mjpd_upload_tabs(og_mjpd* h, const MjpdTab* tabs, int nsets, int sampling, int Ri) {
     h->nsets = 0;
     h->sampling = -1;
-    int rc = mjpd_grow(h, &h->d_tabs, &h->cap_tabs, (size_t)(nsets ? nsets : 1) * sizeof(MjpdTab), false);
+    int rc = h->d_tabs.grow(h, (size_t)(nsets ? nsets : 1) * sizeof(MjpdTab), "mjpd");
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));   // (launches in flight read the old sets; the pageable source must outlive the copy)
     if (nsets) HIPCHK(hipMemcpy(h->d_tabs, tabs, (size_t)nsets * sizeof(MjpdTab), hipMemcpyHostToDevice));
@@ -931,7 +885,7 @@ extern "C" {
 long long og_mjpd_limit(int which) {
     switch (which) {
         case 0: return kMjpegMaxPixels;
-        case 1: return kMjpegMaxChunk;
+        case 1: return kMjpdMaxChunk;
         case 2: return (long long)sizeof(og_mjpd_rec);
         case 3: return (long long)sizeof(MjpdTab);
         case 4: return kMjpdStatusMax;
@@ -1014,30 +968,12 @@ int og_jpegd_records_host(const uint8_t* blob, const int64_t* offsets, int B, og
 og_mjpd* og_mjpd_create(void) { return new og_mjpd(); }
 
 void og_mjpd_destroy(og_mjpd* h) {
-    if (!h) return;
-    DeviceGuard dg_(h->device, og_skip_device(h));
-    if (h->ready) {
-        (void)hipStreamSynchronize(h->stream);
-        mjpd_free(h);
-        (void)hipStreamDestroy(h->stream);
-    }
-    delete h;
+    og_stream_destroy(h, [h] { mjpd_free(h); });
 }
 
-int og_mjpd_sync(og_mjpd* h) {
-    if (!h) return fail(OG_EINVAL, "null handle");
-    if (!h->ready) return OG_OK;
-    OG_SCOPE(h);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return OG_OK;
-}
+int og_mjpd_sync(og_mjpd* h) { return og_stream_sync(h); }
 
-int og_mjpd_set_chunk(og_mjpd* h, int chunk) {
-    if (!h) return fail(OG_EINVAL, "null handle");
-    if (chunk < 1 || chunk > kMjpegMaxChunk) return fail(OG_EINVAL, "chunk must be 1.." + std::to_string(kMjpegMaxChunk));
-    h->chunk = chunk;
-    return OG_OK;
-}
+int og_mjpd_set_chunk(og_mjpd* h, int chunk) { return og_stream_set_chunk(h, chunk, kMjpdMaxChunk); }
 
 int og_mjpd_set_tables(og_mjpd* h, const uint8_t* tabs, int nsets, int sampling, int Ri) {
     if (!h) return fail(OG_EINVAL, "null handle");
@@ -1045,7 +981,7 @@ int og_mjpd_set_tables(og_mjpd* h, const uint8_t* tabs, int nsets, int sampling,
     if (sampling < 0 || sampling > 3) return fail(OG_EINVAL, "sampling must be 0..3");
     if (Ri < 0 || Ri > 65535) return fail(OG_EINVAL, "Ri must be 0..65535");
     OG_ALIGN((const uint32_t*)tabs);
-    int rc = mjpd_ready(h);
+    int rc = og_stream_ready(h);
     if (rc) return rc;
     OG_SCOPE(h);
     return mjpd_upload_tabs(h, (const MjpdTab*)tabs, nsets, sampling, Ri);
@@ -1065,19 +1001,19 @@ int og_mjpd_decode_u8_dev(og_mjpd* h, const uint8_t* blob_dev, const int64_t* of
     if (B == 0) return OG_OK;
     if (!blob_dev || !offsets_dev || !recs_dev || !frames_dev || !status_dev) return fail(OG_EINVAL, "null buffer");
     if (h->sampling < 0 || h->nsets < 1) return fail(OG_ESTATE, "og_mjpd_set_tables has not been called");
-    if ((rc = mjpd_ready(h))) return rc;
+    if ((rc = og_stream_ready(h))) return rc;
     OG_SCOPE(h);
     MjpdForm g;
     mjpd_form(H, W, h->sampling, &g);
     const int nI = mjpd_intervals(g, h->Ri), chunk = mjpd_chunk(h->chunk, g, nI), cb = chunk < B ? chunk : B;
-    if ((rc = mjpd_grow(h, &h->d_ws, &h->cap_ws, (size_t)cb * mjpd_frame_ws(g, nI), false))) return rc;
+    if ((rc = h->d_ws.grow(h, (size_t)cb * mjpd_frame_ws(g, nI), "mjpd"))) return rc;
     const size_t fb = (size_t)H * W * 3;
     for (int b0 = 0; b0 < B && !rc; b0 += chunk) {
         const int nb = (B - b0 < chunk) ? B - b0 : chunk;
         rc = mjpd_batch(h->stream, h->d_ws, h->d_tabs, h->nsets, blob_dev, (const long long*)offsets_dev + b0, recs_dev + b0, nb, g, h->Ri,
                         mjps_sub_of(h->split, h->sub, h->Ri), frames_dev + b0 * fb, status_dev + b0);
     }
-    if (rc) mjpd_drain(h);
+    if (rc) og_stream_drain(h);
     return rc;
 }
 
@@ -1108,7 +1044,7 @@ int og_mjpd_decode_stream(og_mjpd* h, const uint8_t* blob, const int64_t* offset
     const int Hh = call.H, Ww = call.W;
     if ((unsigned long long)cap < (unsigned long long)B * Hh * Ww * 3)
         return fail(OG_EINVAL, "cap is below B * H * W * 3 = " + std::to_string((unsigned long long)B * Hh * Ww * 3) + " bytes");
-    if ((rc = mjpd_ready(h))) return rc;
+    if ((rc = og_stream_ready(h))) return rc;
     OG_SCOPE(h);
     std::vector<MjpdTab> tabs(call.specs.size());
     for (size_t i = 0; i < tabs.size(); ++i) mjpd_build_tab(call.specs[i], &tabs[i]);
@@ -1123,14 +1059,14 @@ int og_mjpd_decode_stream(og_mjpd* h, const uint8_t* blob, const int64_t* offset
         in_max = std::max(in_max, (size_t)(nb + 1) * 8 + (size_t)nb * sizeof(og_mjpd_rec) + (size_t)(offsets[b0 + nb] - offsets[b0]));
     }
     const bool to_host = frames_out_host_or_null != nullptr, own_out = !frames_out_dev_or_null;
-    if ((rc = mjpd_grow(h, &h->d_ws, &h->cap_ws, (size_t)cb * mjpd_frame_ws(g, nI), false))) return rc;
-    if ((rc = mjpd_grow(h, &h->d_in, &h->cap_in, in_max, false))) return rc;
-    if (own_out && (rc = mjpd_grow(h, &h->d_out, &h->cap_out, cb * fb, false))) return rc;
-    if ((rc = mjpd_grow(h, &h->d_status, &h->cap_status, (size_t)cb * 4, false))) return rc;
+    if ((rc = h->d_ws.grow(h, (size_t)cb * mjpd_frame_ws(g, nI), "mjpd"))) return rc;
+    if ((rc = h->d_in.grow(h, in_max, "mjpd"))) return rc;
+    if (own_out && (rc = h->d_out.grow(h, cb * fb, "mjpd"))) return rc;
+    if ((rc = h->d_status.grow(h, (size_t)cb * 4, "mjpd"))) return rc;
     for (auto& s : h->slots) {
-        if ((rc = mjpd_grow(h, &s.h_in, &s.cap_in, in_max, true))) return rc;
-        if (to_host && (rc = mjpd_grow(h, &s.h_out, &s.cap_out, cb * fb, true))) return rc;
-        if ((rc = mjpd_grow(h, &s.h_status, &s.cap_status, (size_t)cb * 4, true))) return rc;
+        if ((rc = s.h_in.grow(h, in_max, "mjpd"))) return rc;
+        if (to_host && (rc = s.h_out.grow(h, cb * fb, "mjpd"))) return rc;
+        if ((rc = s.h_status.grow(h, (size_t)cb * 4, "mjpd"))) return rc;
         if (!s.ev) HIPCHK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
     }
     const hipStream_t st = h->stream;
@@ -1145,7 +1081,7 @@ int og_mjpd_decode_stream(og_mjpd* h, const uint8_t* blob, const int64_t* offset
         return OG_OK;
     };
     auto fill = [&](og_mjpd::Slot& s, int b0, int nb) -> int {
-        long long* off = (long long*)s.h_in;
+        long long* off = (long long*)s.h_in.p;
         og_mjpd_rec* recs = (og_mjpd_rec*)(s.h_in + (size_t)(nb + 1) * 8);
         uint8_t* bytes = (uint8_t*)(recs + nb);
         const size_t nbytes = (size_t)(offsets[b0 + nb] - offsets[b0]), head = (size_t)(bytes - s.h_in);
@@ -1154,9 +1090,9 @@ int og_mjpd_decode_stream(og_mjpd* h, const uint8_t* blob, const int64_t* offset
         memcpy(bytes, blob + offsets[b0], nbytes);
         HIPCHK(hipMemcpyAsync(h->d_in, s.h_in, head + nbytes, hipMemcpyHostToDevice, st));
         uint8_t* dst = own_out ? h->d_out : frames_out_dev_or_null + (size_t)b0 * fb;
-        const int rc2 = mjpd_batch(st, h->d_ws, h->d_tabs, h->nsets, h->d_in + head, (const long long*)h->d_in,
+        const int rc2 = mjpd_batch(st, h->d_ws, h->d_tabs, h->nsets, h->d_in + head, (const long long*)h->d_in.p,
                                    (const og_mjpd_rec*)(h->d_in + (size_t)(nb + 1) * 8), nb, g, call.Ri, mjps_sub_of(h->split, h->sub, call.Ri), dst,
-                                   (int32_t*)h->d_status);
+                                   h->d_status);
         if (rc2) return rc2;
         if (to_host) HIPCHK(hipMemcpyAsync(s.h_out, dst, (size_t)nb * fb, hipMemcpyDeviceToHost, st));
         HIPCHK(hipMemcpyAsync(s.h_status, h->d_status, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
@@ -1166,20 +1102,7 @@ int og_mjpd_decode_stream(og_mjpd* h, const uint8_t* blob, const int64_t* offset
         return OG_OK;
     };
 
-    int k = 0;
-    for (int b0 = 0; b0 < B && !rc; b0 += chunk, ++k) {
-        og_mjpd::Slot& s = h->slots[k & 1];
-        if ((rc = retire(s))) break;   // micro-batch k - 2 is complete and delivered: its pinned buffers are free
-        rc = fill(s, b0, (B - b0 < chunk) ? B - b0 : chunk);
-    }
-    for (int i = 0; i < 2; ++i) {   // in age order; on an error still wait for what is in flight
-        const int rc2 = retire(h->slots[(k + i) & 1]);
-        if (!rc) rc = rc2;
-    }
-    if (rc) {
-        mjpd_drain(h);
-        return rc;
-    }
+    if ((rc = og_two_slot(B, chunk, h->slots, retire, fill, [h] { og_stream_drain(h); }))) return rc;
     *H = Hh;
     *W = Ww;
     if (!call.first_refusal.empty()) g_err = call.first_refusal;
@@ -1196,7 +1119,7 @@ int mjpd_plan_text(int B, int H, int W, int sampling, int Ri, int chunk, int sub
     if (rc) return rc;
     if (sampling < 0 || sampling > 3) return fail(OG_EINVAL, "sampling must be 0..3");
     if (Ri < 0 || Ri > 65535) return fail(OG_EINVAL, "Ri must be 0..65535");
-    if (chunk < 1 || chunk > kMjpegMaxChunk) return fail(OG_EINVAL, "chunk must be 1.." + std::to_string(kMjpegMaxChunk));
+    if ((rc = og_check_chunk(chunk, kMjpdMaxChunk))) return rc;
     MjpdForm g;
     mjpd_form(H, W, sampling, &g);
     const int nI = mjpd_intervals(g, Ri), mb = mjpd_chunk(chunk, g, nI), cb = mb < B ? mb : B;
@@ -1217,14 +1140,7 @@ int mjpd_plan_text(int B, int H, int W, int sampling, int Ri, int chunk, int sub
     }
     g_plan = nullptr;
     if (rc) return rc;
-    std::string txt;
-    for (auto& r : plan.recs)
-        txt += r.kernel + "|" + std::to_string(r.gx) + "|" + std::to_string(r.gy) + "|" + std::to_string(r.gz) + "|" + std::to_string(r.block) + "|" +
-               std::to_string(r.lds) + "|" + std::to_string(r.partial_bytes) + "|" + std::to_string(r.counters) + "|" +
-               (r.writes.empty() ? "-" : r.writes) + "\n";
-    if (txt.size() + 1 > cap) return fail(OG_EINVAL, "plan text does not fit the buffer");
-    memcpy(out, txt.c_str(), txt.size() + 1);
-    return (int)plan.recs.size();
+    return og_plan_text(plan, kPlanWrites, out, cap);
 }
 }  // namespace
 

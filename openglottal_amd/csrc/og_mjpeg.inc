@@ -321,30 +321,21 @@ __global__ __launch_bounds__(256) void k_mjpeg_place(const uint8_t* __restrict__
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
-struct og_mjpeg {
-    int device = -1;
-    bool ready = false;   // the stream exists
-    hipStream_t stream = nullptr;
-    int chunk = 128, quality = 75;
+struct og_mjpeg : OgStreamHandle {
+    int quality = 75;
     MjpegTab* d_tab = nullptr;
     int tab_q = 0, tab_H = 0, tab_W = 0;   // what d_tab holds
-    // per buffer the bytes of the largest micro-batch run so far
-    uint8_t* d_ws = nullptr;   // coefficients, slots, lengths, offsets
-    uint8_t* d_in = nullptr;
-    uint8_t* d_out = nullptr;
-    uint8_t* d_meta = nullptr;   // streamed entry: total (8 bytes), then the sizes
-    size_t cap_ws = 0, cap_in = 0, cap_out = 0, cap_meta = 0;
+    // each buffer holds the bytes of the largest micro-batch run so far
+    OgBuf<uint8_t> d_ws;   // coefficients, slots, lengths, offsets
+    OgBuf<uint8_t> d_in, d_out;
+    OgBuf<uint8_t> d_meta;   // streamed entry: total (8 bytes), then the sizes
     struct Slot {
-        uint8_t* h_in = nullptr;
-        uint8_t* h_out = nullptr;
-        uint8_t* h_meta = nullptr;
-        size_t cap_in = 0, cap_out = 0, cap_meta = 0;
+        OgBuf<uint8_t> h_in{true}, h_out{true}, h_meta{true};
         hipEvent_t ev = nullptr;
         int b0 = -1, nb = 0;
         long long at = 0, bytes = 0;   // where in the caller's out, how many
     } slots[2];
 };
-inline bool og_skip_device(const og_mjpeg* h) { return !h || !h->ready; }
 
 namespace {
 
@@ -478,32 +469,6 @@ uint8_t* mjpeg_scan_host(const int16_t* coefs, const MjpegGeom& g, const MjpegTa
     return p;
 }
 
-int mjpeg_ready(og_mjpeg* h) {
-    if (h->ready) return OG_OK;
-    HIPCHK(hipGetDevice(&h->device));
-    HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    h->ready = true;
-    return OG_OK;
-}
-
-// grow one buffer to `need` bytes (never shrink); what it held is dropped, so the stream is drained first
-template <class T>
-int mjpeg_grow(og_mjpeg* h, T** p, size_t* cap, size_t need, bool pinned) {
-    if (need <= *cap && *p) return OG_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (*p) (void)(pinned ? hipHostFree(*p) : hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const size_t bytes = need ? need : 1;
-    const hipError_t e = pinned ? hipHostMalloc((void**)p, bytes, hipHostMallocDefault) : hipMalloc((void**)p, bytes);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        return fail(e == hipErrorOutOfMemory ? OG_ENOMEM : OG_EHIP, std::string("mjpeg workspace: ") + hipGetErrorString(e));
-    }
-    *cap = bytes;
-    return OG_OK;
-}
-
 // the tables and the header of (quality, H, W) on the device
 int mjpeg_ensure_tab(og_mjpeg* h, int H, int W) {
     if (h->d_tab && h->tab_q == h->quality && h->tab_H == H && h->tab_W == W) return OG_OK;
@@ -520,13 +485,10 @@ int mjpeg_ensure_tab(og_mjpeg* h, int H, int W) {
 }
 
 void mjpeg_free(og_mjpeg* h) {
-    void* dev[] = {h->d_tab, h->d_ws, h->d_in, h->d_out, h->d_meta};
-    for (void* p : dev)
-        if (p) (void)hipFree(p);
+    if (h->d_tab) (void)hipFree(h->d_tab);
+    og_release(h->d_ws, h->d_in, h->d_out, h->d_meta);
     for (auto& s : h->slots) {
-        void* host[] = {s.h_in, s.h_out, s.h_meta};
-        for (void* p : host)
-            if (p) (void)hipHostFree(p);
+        og_release(s.h_in, s.h_out, s.h_meta);
         if (s.ev) (void)hipEventDestroy(s.ev);
     }
 }
@@ -564,13 +526,6 @@ int check_mjpeg(og_mjpeg* h, int B, int H, int W, size_t cap) {
     if ((unsigned long long)cap < (unsigned long long)B * (unsigned long long)mjpeg_bound(H, W))
         return fail(OG_EINVAL, "cap is below B * og_jpeg_bound(H, W) = " + std::to_string((long long)B * mjpeg_bound(H, W)) + " bytes");
     return OG_OK;
-}
-
-void mjpeg_drain(og_mjpeg* h) {
-    const std::string err = g_err;
-    if (h->ready) (void)hipStreamSynchronize(h->stream);
-    for (auto& s : h->slots) s.b0 = -1;
-    g_err = err;
 }
 
 }  // namespace
@@ -648,30 +603,12 @@ int og_jpeg_encode_host(const uint8_t* frame, int H, int W, int quality, uint8_t
 og_mjpeg* og_mjpeg_create(void) { return new og_mjpeg(); }
 
 void og_mjpeg_destroy(og_mjpeg* h) {
-    if (!h) return;
-    DeviceGuard dg_(h->device, og_skip_device(h));
-    if (h->ready) {
-        (void)hipStreamSynchronize(h->stream);
-        mjpeg_free(h);
-        (void)hipStreamDestroy(h->stream);
-    }
-    delete h;
+    og_stream_destroy(h, [h] { mjpeg_free(h); });
 }
 
-int og_mjpeg_sync(og_mjpeg* h) {
-    if (!h) return fail(OG_EINVAL, "null handle");
-    if (!h->ready) return OG_OK;
-    OG_SCOPE(h);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return OG_OK;
-}
+int og_mjpeg_sync(og_mjpeg* h) { return og_stream_sync(h); }
 
-int og_mjpeg_set_chunk(og_mjpeg* h, int chunk) {
-    if (!h) return fail(OG_EINVAL, "null handle");
-    if (chunk < 1 || chunk > kMjpegMaxChunk) return fail(OG_EINVAL, "chunk must be 1.." + std::to_string(kMjpegMaxChunk));
-    h->chunk = chunk;
-    return OG_OK;
-}
+int og_mjpeg_set_chunk(og_mjpeg* h, int chunk) { return og_stream_set_chunk(h, chunk, kMjpegMaxChunk); }
 
 int og_mjpeg_set_quality(og_mjpeg* h, int quality) {
     if (!h) return fail(OG_EINVAL, "null handle");
@@ -689,18 +626,18 @@ int og_mjpeg_encode_u8_dev(og_mjpeg* h, const uint8_t* frames_dev, int B, int H,
     OG_ALIGN(total_dev);
     if (B == 0) return OG_OK;
     if (!frames_dev || !out_dev || !sizes_dev || !total_dev) return fail(OG_EINVAL, "null buffer");
-    if ((rc = mjpeg_ready(h))) return rc;
+    if ((rc = og_stream_ready(h))) return rc;
     OG_SCOPE(h);
     const MjpegGeom g = mjpeg_geom(H, W);
     const int chunk = mjpeg_chunk(h->chunk, g), cb = chunk < B ? chunk : B;
     if ((rc = mjpeg_ensure_tab(h, H, W))) return rc;
-    if ((rc = mjpeg_grow(h, &h->d_ws, &h->cap_ws, (size_t)cb * mjpeg_frame_ws(g) + 8, false))) return rc;
+    if ((rc = h->d_ws.grow(h, (size_t)cb * mjpeg_frame_ws(g) + 8, "mjpeg"))) return rc;
     const size_t fb = (size_t)H * W * 3;
     for (int b0 = 0; b0 < B && !rc; b0 += chunk) {
         const int nb = (B - b0 < chunk) ? B - b0 : chunk;
         rc = mjpeg_batch(h->stream, h->d_ws, h->d_tab, frames_dev + b0 * fb, nb, H, W, out_dev, sizes_dev + b0, total_dev, b0 == 0, 0);
     }
-    if (rc) mjpeg_drain(h);
+    if (rc) og_stream_drain(h);
     return rc;
 }
 
@@ -716,19 +653,19 @@ int og_mjpeg_encode_stream_u8(og_mjpeg* h, const uint8_t* frames, int B, int H, 
         *total = 0;
         return OG_OK;
     }
-    if ((rc = mjpeg_ready(h))) return rc;
+    if ((rc = og_stream_ready(h))) return rc;
     OG_SCOPE(h);
     const MjpegGeom g = mjpeg_geom(H, W);
     const int chunk = mjpeg_chunk(h->chunk, g), cb = chunk < B ? chunk : B;
     const size_t fb = (size_t)H * W * 3, meta = 8 + (size_t)cb * 4;
     if ((rc = mjpeg_ensure_tab(h, H, W))) return rc;
-    if ((rc = mjpeg_grow(h, &h->d_ws, &h->cap_ws, (size_t)cb * mjpeg_frame_ws(g) + 8, false))) return rc;
-    if ((rc = mjpeg_grow(h, &h->d_in, &h->cap_in, cb * fb, false))) return rc;
-    if ((rc = mjpeg_grow(h, &h->d_out, &h->cap_out, (size_t)cb * mjpeg_bound(H, W), false))) return rc;
-    if ((rc = mjpeg_grow(h, &h->d_meta, &h->cap_meta, meta, false))) return rc;
+    if ((rc = h->d_ws.grow(h, (size_t)cb * mjpeg_frame_ws(g) + 8, "mjpeg"))) return rc;
+    if ((rc = h->d_in.grow(h, cb * fb, "mjpeg"))) return rc;
+    if ((rc = h->d_out.grow(h, (size_t)cb * mjpeg_bound(H, W), "mjpeg"))) return rc;
+    if ((rc = h->d_meta.grow(h, meta, "mjpeg"))) return rc;
     for (auto& s : h->slots) {
-        if ((rc = mjpeg_grow(h, &s.h_in, &s.cap_in, cb * fb, true))) return rc;
-        if ((rc = mjpeg_grow(h, &s.h_meta, &s.cap_meta, meta, true))) return rc;
+        if ((rc = s.h_in.grow(h, cb * fb, "mjpeg"))) return rc;
+        if ((rc = s.h_meta.grow(h, meta, "mjpeg"))) return rc;
         if (!s.ev) HIPCHK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
     }
     const hipStream_t st = h->stream;
@@ -744,16 +681,16 @@ int og_mjpeg_encode_stream_u8(og_mjpeg* h, const uint8_t* frames, int B, int H, 
     auto fill = [&](og_mjpeg::Slot& s, int b0, int nb) -> int {
         memcpy(s.h_in, frames + (size_t)b0 * fb, nb * fb);
         HIPCHK(hipMemcpyAsync(h->d_in, s.h_in, nb * fb, hipMemcpyHostToDevice, st));
-        const int rc2 = mjpeg_batch(st, h->d_ws, h->d_tab, h->d_in, nb, H, W, h->d_out, (int32_t*)(h->d_meta + 8), (long long*)h->d_meta, true, 0);
+        const int rc2 = mjpeg_batch(st, h->d_ws, h->d_tab, h->d_in, nb, H, W, h->d_out, (int32_t*)(h->d_meta + 8), (long long*)h->d_meta.p, true, 0);
         if (rc2) return rc2;
         HIPCHK(hipMemcpyAsync(s.h_meta, h->d_meta, 8 + (size_t)nb * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipEventRecord(s.ev, st));
         HIPCHK(hipEventSynchronize(s.ev));   // the micro-batch's one number: its bytes
-        const long long bytes = *(const long long*)s.h_meta;
+        const long long bytes = *(const long long*)s.h_meta.p;
         if (bytes < 0 || bytes > (long long)nb * mjpeg_bound(H, W)) return fail(OG_EHIP, "the device reported an impossible size");
         memcpy(sizes + b0, s.h_meta + 8, (size_t)nb * 4);
-        if ((size_t)bytes > s.cap_out || !s.h_out) {   // (grows drain the stream: nothing of this slot is in flight)
-            const int rc3 = mjpeg_grow(h, &s.h_out, &s.cap_out, ((size_t)bytes + (1u << 20)) & ~(size_t)((1u << 20) - 1), true);
+        if ((size_t)bytes > s.h_out.cap || !s.h_out) {   // (grows drain the stream: nothing of this slot is in flight)
+            const int rc3 = s.h_out.grow(h, ((size_t)bytes + (1u << 20)) & ~(size_t)((1u << 20) - 1), "mjpeg");
             if (rc3) return rc3;
         }
         HIPCHK(hipMemcpyAsync(s.h_out, h->d_out, (size_t)bytes, hipMemcpyDeviceToHost, st));
@@ -766,18 +703,8 @@ int og_mjpeg_encode_stream_u8(og_mjpeg* h, const uint8_t* frames, int B, int H, 
         return OG_OK;
     };
 
-    int k = 0;
-    for (int b0 = 0; b0 < B && !rc; b0 += chunk, ++k) {
-        og_mjpeg::Slot& s = h->slots[k & 1];
-        if ((rc = retire(s))) break;   // micro-batch k - 2 is complete and delivered: its pinned buffers are free
-        rc = fill(s, b0, (B - b0 < chunk) ? B - b0 : chunk);
-    }
-    for (int i = 0; i < 2; ++i) {   // in age order; on an error still wait for what is in flight
-        const int rc2 = retire(h->slots[(k + i) & 1]);
-        if (!rc) rc = rc2;
-    }
-    if (rc) mjpeg_drain(h);
-    else *total = at;
+    rc = og_two_slot(B, chunk, h->slots, retire, fill, [h] { og_stream_drain(h); });
+    if (!rc) *total = at;
     return rc;
 }
 
@@ -785,7 +712,7 @@ int og_mjpeg_plan(int B, int H, int W, int chunk, char* out, size_t cap, long lo
     if (!out || cap == 0 || B < 1) return fail(OG_EINVAL, "bad argument");
     int rc = check_jpeg_shape(H, W);
     if (rc) return rc;
-    if (chunk < 1 || chunk > kMjpegMaxChunk) return fail(OG_EINVAL, "chunk must be 1.." + std::to_string(kMjpegMaxChunk));
+    if ((rc = og_check_chunk(chunk, kMjpegMaxChunk))) return rc;
     const MjpegGeom g = mjpeg_geom(H, W);
     const int mb = mjpeg_chunk(chunk, g), cb = mb < B ? mb : B;
     const long long bound = mjpeg_bound(H, W);
@@ -806,14 +733,7 @@ int og_mjpeg_plan(int B, int H, int W, int chunk, char* out, size_t cap, long lo
     }
     g_plan = nullptr;
     if (rc) return rc;
-    std::string txt;
-    for (auto& r : plan.recs)
-        txt += r.kernel + "|" + std::to_string(r.gx) + "|" + std::to_string(r.gy) + "|" + std::to_string(r.gz) + "|" + std::to_string(r.block) + "|" +
-               std::to_string(r.lds) + "|" + std::to_string(r.partial_bytes) + "|" + std::to_string(r.counters) + "|" +
-               (r.writes.empty() ? "-" : r.writes) + "\n";
-    if (txt.size() + 1 > cap) return fail(OG_EINVAL, "plan text does not fit the buffer");
-    memcpy(out, txt.c_str(), txt.size() + 1);
-    return (int)plan.recs.size();
+    return og_plan_text(plan, kPlanWrites, out, cap);
 }
 
 }  // extern "C"

@@ -7,33 +7,20 @@
 // call to call.
 #include "../../include/openglottal_hip_overlay.h"
 
-struct og_overlay {
-    int device = -1;
-    bool ready = false;   // the stream exists
-    hipStream_t stream = nullptr;
-    int chunk = 128;
-    // per buffer the bytes of the largest micro-batch run so far
-    int* d_la = nullptr;
-    size_t cap_la = 0;
-    int32_t* d_wbox = nullptr;   // {0, 0, W, H} per frame of the micro-batch: the labelling's windows
-    size_t cap_wbox = 0;         // bytes: 16 per frame
+struct og_overlay : OgStreamHandle {
+    // each buffer holds the bytes of the largest micro-batch run so far
+    OgBuf<int> d_la;
+    OgBuf<int32_t> d_wbox;   // {0, 0, W, H} per frame of the micro-batch, 16 bytes: the labelling's windows
     int wbox_H = 0, wbox_W = 0;
-    uint8_t* d_in = nullptr;
-    uint8_t* d_mask = nullptr;
-    uint8_t* d_out = nullptr;
-    int32_t* d_boxes = nullptr;
-    size_t cap_in = 0, cap_mask = 0, cap_out = 0, cap_boxes = 0;
+    OgBuf<uint8_t> d_in, d_mask, d_out;
+    OgBuf<int32_t> d_boxes;
     struct Slot {
-        uint8_t* h_in = nullptr;
-        uint8_t* h_mask = nullptr;
-        uint8_t* h_out = nullptr;
-        int32_t* h_boxes = nullptr;
-        size_t cap_in = 0, cap_mask = 0, cap_out = 0, cap_boxes = 0;
-        hipEvent_t ev_out = nullptr;
+        OgBuf<uint8_t> h_in{true}, h_mask{true}, h_out{true};
+        OgBuf<int32_t> h_boxes{true};
+        hipEvent_t ev = nullptr;
         int b0 = -1, nb = 0;
     } slots[2];
 };
-inline bool og_skip_device(const og_overlay* h) { return !h || !h->ready; }
 
 namespace {
 
@@ -60,40 +47,14 @@ int check_overlay(og_overlay* h, int B, int H, int W, int ch, int style) {
     return OG_OK;
 }
 
-int overlay_ready(og_overlay* h) {
-    if (h->ready) return OG_OK;
-    HIPCHK(hipGetDevice(&h->device));
-    HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    h->ready = true;
-    return OG_OK;
-}
-
-// grow one buffer to `need` bytes (never shrink); what it held is dropped, so the stream is drained first
-template <class T>
-int overlay_grow(og_overlay* h, T** p, size_t* cap, size_t need, bool pinned) {
-    if (need <= *cap && *p) return OG_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (*p) (void)(pinned ? hipHostFree(*p) : hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const size_t bytes = need ? need : 1;
-    const hipError_t e = pinned ? hipHostMalloc((void**)p, bytes, hipHostMallocDefault) : hipMalloc((void**)p, bytes);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        return fail(e == hipErrorOutOfMemory ? OG_ENOMEM : OG_EHIP, std::string("overlay workspace: ") + hipGetErrorString(e));
-    }
-    *cap = bytes;
-    return OG_OK;
-}
-
 // the label array and the whole-frame windows of a micro-batch of nb frames
 int overlay_ensure_labels(og_overlay* h, int nb, int H, int W) {
-    int rc = overlay_grow(h, &h->d_la, &h->cap_la, (size_t)nb * H * W * 4, false);
+    int rc = h->d_la.grow(h, (size_t)nb * H * W * 4, "overlay");
     if (rc) return rc;
-    if ((size_t)nb * 16 <= h->cap_wbox && h->wbox_H == H && h->wbox_W == W) return OG_OK;
-    const size_t n = std::max((size_t)nb, h->cap_wbox / 16);
+    if ((size_t)nb * 16 <= h->d_wbox.cap && h->wbox_H == H && h->wbox_W == W) return OG_OK;
+    const size_t n = std::max((size_t)nb, h->d_wbox.cap / 16);
     h->wbox_H = h->wbox_W = 0;
-    if ((rc = overlay_grow(h, &h->d_wbox, &h->cap_wbox, n * 16, false))) return rc;
+    if ((rc = h->d_wbox.grow(h, n * 16, "overlay"))) return rc;
     std::vector<int32_t> whole(n * 4);
     for (size_t i = 0; i < n; ++i) {
         whole[4 * i] = whole[4 * i + 1] = 0;
@@ -108,14 +69,10 @@ int overlay_ensure_labels(og_overlay* h, int nb, int H, int W) {
 }
 
 void overlay_free(og_overlay* h) {
-    void* dev[] = {h->d_la, h->d_wbox, h->d_in, h->d_mask, h->d_out, h->d_boxes};
-    for (void* p : dev)
-        if (p) (void)hipFree(p);
+    og_release(h->d_la, h->d_wbox, h->d_in, h->d_mask, h->d_out, h->d_boxes);
     for (auto& s : h->slots) {
-        void* host[] = {s.h_in, s.h_mask, s.h_out, s.h_boxes};
-        for (void* p : host)
-            if (p) (void)hipHostFree(p);
-        if (s.ev_out) (void)hipEventDestroy(s.ev_out);
+        og_release(s.h_in, s.h_mask, s.h_out, s.h_boxes);
+        if (s.ev) (void)hipEventDestroy(s.ev);
     }
 }
 
@@ -144,13 +101,6 @@ int overlay_batch(hipStream_t st, int* la, const int32_t* wbox, int ch, const ui
     return OG_OK;
 }
 
-void overlay_drain(og_overlay* h) {
-    const std::string err = g_err;
-    if (h->ready) (void)hipStreamSynchronize(h->stream);
-    for (auto& s : h->slots) s.b0 = -1;
-    g_err = err;
-}
-
 int overlay_stream_impl(og_overlay* h, const uint8_t* frames, const uint8_t* const* frame_ptrs, int B, int H, int W, int ch,
                         const uint8_t* masks, const int32_t* boxes, int style, uint8_t* out) {
     int rc = check_overlay(h, B, H, W, ch, style);
@@ -163,22 +113,22 @@ int overlay_stream_impl(og_overlay* h, const uint8_t* frames, const uint8_t* con
     if (frame_ptrs)
         for (int i = 0; i < B; ++i)
             if (!frame_ptrs[i]) return fail(OG_EINVAL, "frame_ptrs[" + std::to_string(i) + "] is null");
-    if ((rc = overlay_ready(h))) return rc;
+    if ((rc = og_stream_ready(h))) return rc;
     OG_SCOPE(h);
     const size_t HW = (size_t)H * W, fb = HW * ch;
     const int chunk = overlay_chunk(h->chunk, H, W), cb = chunk < B ? chunk : B;
     const bool outlined = overlay_outlined(style, masks);
     if (outlined && (rc = overlay_ensure_labels(h, cb, H, W))) return rc;
-    if ((rc = overlay_grow(h, &h->d_in, &h->cap_in, cb * fb, false))) return rc;
-    if ((rc = overlay_grow(h, &h->d_out, &h->cap_out, cb * HW * 3, false))) return rc;
-    if (masks && (rc = overlay_grow(h, &h->d_mask, &h->cap_mask, cb * HW, false))) return rc;
-    if (boxes && (rc = overlay_grow(h, &h->d_boxes, &h->cap_boxes, (size_t)cb * 16, false))) return rc;
+    if ((rc = h->d_in.grow(h, cb * fb, "overlay"))) return rc;
+    if ((rc = h->d_out.grow(h, cb * HW * 3, "overlay"))) return rc;
+    if (masks && (rc = h->d_mask.grow(h, cb * HW, "overlay"))) return rc;
+    if (boxes && (rc = h->d_boxes.grow(h, (size_t)cb * 16, "overlay"))) return rc;
     for (auto& s : h->slots) {
-        if ((rc = overlay_grow(h, &s.h_in, &s.cap_in, cb * fb, true))) return rc;
-        if ((rc = overlay_grow(h, &s.h_out, &s.cap_out, cb * HW * 3, true))) return rc;
-        if (masks && (rc = overlay_grow(h, &s.h_mask, &s.cap_mask, cb * HW, true))) return rc;
-        if (boxes && (rc = overlay_grow(h, &s.h_boxes, &s.cap_boxes, (size_t)cb * 16, true))) return rc;
-        if (!s.ev_out) HIPCHK(hipEventCreateWithFlags(&s.ev_out, hipEventDisableTiming));
+        if ((rc = s.h_in.grow(h, cb * fb, "overlay"))) return rc;
+        if ((rc = s.h_out.grow(h, cb * HW * 3, "overlay"))) return rc;
+        if (masks && (rc = s.h_mask.grow(h, cb * HW, "overlay"))) return rc;
+        if (boxes && (rc = s.h_boxes.grow(h, (size_t)cb * 16, "overlay"))) return rc;
+        if (!s.ev) HIPCHK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
     }
     const hipStream_t st = h->stream;
 
@@ -186,7 +136,7 @@ int overlay_stream_impl(og_overlay* h, const uint8_t* frames, const uint8_t* con
         if (s.b0 < 0) return OG_OK;
         const int b0 = s.b0, nb = s.nb;
         s.b0 = -1;
-        HIPCHK(hipEventSynchronize(s.ev_out));
+        HIPCHK(hipEventSynchronize(s.ev));
         memcpy(out + b0 * HW * 3, s.h_out, nb * HW * 3);
         return OG_OK;
     };
@@ -208,24 +158,13 @@ int overlay_stream_impl(og_overlay* h, const uint8_t* frames, const uint8_t* con
                                       style, h->d_out);
         if (rc2) return rc2;
         HIPCHK(hipMemcpyAsync(s.h_out, h->d_out, nb * HW * 3, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipEventRecord(s.ev_out, st));
+        HIPCHK(hipEventRecord(s.ev, st));
         s.b0 = b0;
         s.nb = nb;
         return OG_OK;
     };
 
-    int k = 0;
-    for (int b0 = 0; b0 < B && !rc; b0 += chunk, ++k) {
-        og_overlay::Slot& s = h->slots[k & 1];
-        if ((rc = retire(s))) break;   // micro-batch k - 2 is complete and delivered: its pinned buffers are free
-        rc = fill(s, b0, (B - b0 < chunk) ? B - b0 : chunk);
-    }
-    for (int i = 0; i < 2; ++i) {   // in age order; on an error still wait for what is in flight
-        const int rc2 = retire(h->slots[(k + i) & 1]);
-        if (!rc) rc = rc2;
-    }
-    if (rc) overlay_drain(h);
-    return rc;
+    return og_two_slot(B, chunk, h->slots, retire, fill, [h] { og_stream_drain(h); });
 }
 
 // the sequential labelling of the host twins: outside[p] = 1 where p is background of a component that touches the frame's edge
@@ -291,30 +230,12 @@ int og_overlay_host(const uint8_t* frame, int H, int W, int channels, const uint
 og_overlay* og_overlay_create(void) { return new og_overlay(); }
 
 void og_overlay_destroy(og_overlay* h) {
-    if (!h) return;
-    DeviceGuard dg_(h->device, og_skip_device(h));
-    if (h->ready) {
-        (void)hipStreamSynchronize(h->stream);
-        overlay_free(h);
-        (void)hipStreamDestroy(h->stream);
-    }
-    delete h;
+    og_stream_destroy(h, [h] { overlay_free(h); });
 }
 
-int og_overlay_sync(og_overlay* h) {
-    if (!h) return fail(OG_EINVAL, "null handle");
-    if (!h->ready) return OG_OK;
-    OG_SCOPE(h);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return OG_OK;
-}
+int og_overlay_sync(og_overlay* h) { return og_stream_sync(h); }
 
-int og_overlay_set_chunk(og_overlay* h, int chunk) {
-    if (!h) return fail(OG_EINVAL, "null handle");
-    if (chunk < 1 || chunk > kOverlayMaxChunk) return fail(OG_EINVAL, "chunk must be 1.." + std::to_string(kOverlayMaxChunk));
-    h->chunk = chunk;
-    return OG_OK;
-}
+int og_overlay_set_chunk(og_overlay* h, int chunk) { return og_stream_set_chunk(h, chunk, kOverlayMaxChunk); }
 
 int og_overlay_u8_dev(og_overlay* h, const uint8_t* frames_dev, int B, int H, int W, int channels, const uint8_t* masks_dev_or_null,
                       const int32_t* boxes_dev_or_null, int style, uint8_t* out_dev) {
@@ -323,7 +244,7 @@ int og_overlay_u8_dev(og_overlay* h, const uint8_t* frames_dev, int B, int H, in
     OG_ALIGN(boxes_dev_or_null);
     if (B == 0) return OG_OK;
     if (!frames_dev || !out_dev) return fail(OG_EINVAL, "null buffer");
-    if ((rc = overlay_ready(h))) return rc;
+    if ((rc = og_stream_ready(h))) return rc;
     OG_SCOPE(h);
     const size_t HW = (size_t)H * W;
     const int chunk = overlay_chunk(h->chunk, H, W), cb = chunk < B ? chunk : B;
@@ -334,7 +255,7 @@ int og_overlay_u8_dev(og_overlay* h, const uint8_t* frames_dev, int B, int H, in
                            masks_dev_or_null ? masks_dev_or_null + b0 * HW : nullptr, boxes_dev_or_null ? boxes_dev_or_null + 4 * (size_t)b0 : nullptr,
                            nb, H, W, style, out_dev + b0 * HW * 3);
     }
-    if (rc) overlay_drain(h);
+    if (rc) og_stream_drain(h);
     return rc;
 }
 
@@ -354,7 +275,7 @@ int og_overlay_plan(int B, int H, int W, int channels, int chunk, int style, cha
     og_overlay tmp;
     int rc = check_overlay(&tmp, B, H, W, channels, style);
     if (rc) return rc;
-    if (chunk < 1 || chunk > kOverlayMaxChunk) return fail(OG_EINVAL, "chunk must be 1.." + std::to_string(kOverlayMaxChunk));
+    if ((rc = og_check_chunk(chunk, kOverlayMaxChunk))) return rc;
     const int mb = overlay_chunk(chunk, H, W), cb = mb < B ? mb : B;
     if (workspace_bytes) *workspace_bytes = (long long)cb * overlay_frame_bytes(H, W, channels, style);
     const uintptr_t gap = (uintptr_t)1 << 40;   // placeholder bases: nothing dereferences them in a dry run
@@ -368,14 +289,7 @@ int og_overlay_plan(int B, int H, int W, int channels, int chunk, int style, cha
                            (const int32_t*)(6 * gap), (B - b0 < mb) ? B - b0 : mb, H, W, style, dst + b0 * HW * 3);
     g_plan = nullptr;
     if (rc) return rc;
-    std::string txt;
-    for (auto& r : plan.recs)
-        txt += r.kernel + "|" + std::to_string(r.gx) + "|" + std::to_string(r.gy) + "|" + std::to_string(r.gz) + "|" + std::to_string(r.block) + "|" +
-               std::to_string(r.lds) + "|" + std::to_string(r.partial_bytes) + "|" + std::to_string(r.counters) + "|" +
-               (r.writes.empty() ? "-" : r.writes) + "\n";
-    if (txt.size() + 1 > cap) return fail(OG_EINVAL, "plan text does not fit the buffer");
-    memcpy(out, txt.c_str(), txt.size() + 1);
-    return (int)plan.recs.size();
+    return og_plan_text(plan, kPlanWrites, out, cap);
 }
 
 }  // extern "C"

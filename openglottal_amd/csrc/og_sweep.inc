@@ -182,23 +182,18 @@ __global__ __launch_bounds__(256) void k_sweep_lookup(const uint2* __restrict__ 
     }
 }
 
-struct og_sweep {
-    int device = -1;
-    bool ready = false;   // the stream, the states and the grid's device rows exist
-    hipStream_t stream = nullptr;
-    int chunk = 0;        // 0: the default for the shape
+struct og_sweep : OgStreamHandle {   // ready: the stream, the states and the grid's device rows exist
+    og_sweep() { chunk = 0; }   // 0: the default for the shape
     std::vector<double> thr;      // the grid of the last call; a call with another one resets the states
     std::vector<int32_t> hold;
     double* d_thr = nullptr;
     int32_t* d_hold = nullptr;
     OgTrackState* d_state = nullptr;
-    // per buffer the bytes of the largest micro-batch run so far
-    uint2* d_tab = nullptr;
-    int32_t* d_box = nullptr;
-    uint8_t* d_stage = nullptr;
-    size_t cap_tab = 0, cap_box = 0, cap_stage = 0;
+    // each buffer holds the bytes of the largest micro-batch run so far
+    OgBuf<uint2> d_tab;
+    OgBuf<int32_t> d_box;
+    OgBuf<uint8_t> d_stage;
 };
-inline bool og_skip_device(const og_sweep* h) { return !h || !h->ready; }
 
 namespace {
 
@@ -234,9 +229,9 @@ int check_sweep(int N, int H, int W, const double* conf_thres, int n_conf, const
 
 int sweep_ready(og_sweep* h) {
     if (h->ready) return OG_OK;
-    HIPCHK(hipGetDevice(&h->device));
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_thr, kSweepMaxConf * sizeof(double));
+    const int rc = og_stream_ready(h);
+    if (rc) return rc;
+    hipError_t e = hipMalloc((void**)&h->d_thr, kSweepMaxConf * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_hold, kSweepMaxHold * sizeof(int32_t));
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_state, (size_t)kSweepMaxConf * kSweepMaxHold * sizeof(OgTrackState));
     // (on the handle's stream: a non-blocking stream is not ordered after the null stream's work)
@@ -245,32 +240,14 @@ int sweep_ready(og_sweep* h) {
         if (h->d_thr) (void)hipFree(h->d_thr);
         if (h->d_hold) (void)hipFree(h->d_hold);
         if (h->d_state) (void)hipFree(h->d_state);
-        if (h->stream) (void)hipStreamDestroy(h->stream);
+        (void)hipStreamDestroy(h->stream);
         h->d_thr = nullptr;
         h->d_hold = nullptr;
         h->d_state = nullptr;
         h->stream = nullptr;
+        h->ready = false;
         return fail(e == hipErrorOutOfMemory ? OG_ENOMEM : OG_EHIP, std::string("og_sweep: ") + hipGetErrorString(e));
     }
-    h->ready = true;
-    return OG_OK;
-}
-
-// grow one device buffer to `need` bytes (never shrink); what it held is dropped, so the stream is drained first
-template <class T>
-int sweep_grow(og_sweep* h, T** p, size_t* cap, size_t need) {
-    if (need <= *cap && *p) return OG_OK;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const size_t bytes = need ? need : 1;
-    const hipError_t e = hipMalloc((void**)p, bytes);
-    if (e != hipSuccess) {
-        *p = nullptr;
-        return fail(e == hipErrorOutOfMemory ? OG_ENOMEM : OG_EHIP, std::string("sweep workspace: ") + hipGetErrorString(e));
-    }
-    *cap = bytes;
     return OG_OK;
 }
 
@@ -308,19 +285,13 @@ int sweep_batch(og_sweep* h, const uint8_t* pred, const uint8_t* gt, const float
     return OG_OK;
 }
 
-void sweep_drain(og_sweep* h) {
-    const std::string err = g_err;
-    if (h->ready) (void)hipStreamSynchronize(h->stream);
-    g_err = err;
-}
-
 // device set-up shared by the two entries: the stream, the grid, the workspace of one micro-batch of cb frames
 int sweep_prepare(og_sweep* h, int cb, int H, int W, const double* conf_thres, int n_conf, const int32_t* max_hold, int n_hold) {
     int rc = sweep_set_grid(h, conf_thres, n_conf, max_hold, n_hold);
     if (rc) return rc;
     const int C = n_conf * n_hold;
-    if ((rc = sweep_grow(h, &h->d_tab, &h->cap_tab, (size_t)cb * 8 * (size_t)og_sweep_table_elems(H, W)))) return rc;
-    return sweep_grow(h, &h->d_box, &h->cap_box, (size_t)cb * 16 * C);
+    if ((rc = h->d_tab.grow(h, (size_t)cb * 8 * (size_t)og_sweep_table_elems(H, W), "sweep"))) return rc;
+    return h->d_box.grow(h, (size_t)cb * 16 * C, "sweep");
 }
 
 inline size_t sweep_up256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -396,32 +367,17 @@ int og_sweep_host(const uint8_t* pred, const uint8_t* gt, const float* best, con
 og_sweep* og_sweep_create(void) { return new og_sweep(); }
 
 void og_sweep_destroy(og_sweep* h) {
-    if (!h) return;
-    DeviceGuard dg_(h->device, og_skip_device(h));
-    if (h->ready) {
-        (void)hipStreamSynchronize(h->stream);
-        void* dev[] = {h->d_thr, h->d_hold, h->d_state, h->d_tab, h->d_box, h->d_stage};
-        for (void* p : dev)
-            if (p) (void)hipFree(p);
-        (void)hipStreamDestroy(h->stream);
-    }
-    delete h;
+    og_stream_destroy(h, [h] {
+        (void)hipFree(h->d_thr);   // (the three of sweep_ready exist together)
+        (void)hipFree(h->d_hold);
+        (void)hipFree(h->d_state);
+        og_release(h->d_tab, h->d_box, h->d_stage);
+    });
 }
 
-int og_sweep_sync(og_sweep* h) {
-    if (!h) return fail(OG_EINVAL, "null handle");
-    if (!h->ready) return OG_OK;
-    OG_SCOPE(h);
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return OG_OK;
-}
+int og_sweep_sync(og_sweep* h) { return og_stream_sync(h); }
 
-int og_sweep_set_chunk(og_sweep* h, int chunk) {
-    if (!h) return fail(OG_EINVAL, "null handle");
-    if (chunk < 0 || chunk > kSweepMaxChunk) return fail(OG_EINVAL, "chunk must be 1.." + std::to_string(kSweepMaxChunk) + ", or 0 for the default");
-    h->chunk = chunk;
-    return OG_OK;
-}
+int og_sweep_set_chunk(og_sweep* h, int chunk) { return og_stream_set_chunk(h, chunk, kSweepMaxChunk, true); }
 
 int og_sweep_reset(og_sweep* h) {
     if (!h) return fail(OG_EINVAL, "null handle");
@@ -465,7 +421,7 @@ int og_sweep_counts_u8_dev(og_sweep* h, const uint8_t* pred_dev, const uint8_t* 
         rc = sweep_batch(h, pred_dev + b0 * HW, gt_dev + b0 * HW, best_dev + 5 * (size_t)b0, resets_dev_or_null ? resets_dev_or_null + b0 : nullptr,
                          nb, H, W, n_hold, C, max_shift_px, padding, inclusive, N, b0, frame_counts_dev, counts_dev, boxes_dev_or_null);
     }
-    if (rc) sweep_drain(h);
+    if (rc) og_stream_drain(h);
     return rc;
 }
 
@@ -492,7 +448,7 @@ int og_sweep_counts_u8(og_sweep* h, const uint8_t* pred, const uint8_t* gt, cons
                  o_res = sweep_up256(o_best + (size_t)cb * 20), o_fc = sweep_up256(o_res + (size_t)cb),
                  o_cnt = sweep_up256(o_fc + (size_t)cb * 12), o_box = sweep_up256(o_cnt + (size_t)C * cb * 12),
                  total = o_box + (size_t)C * cb * 16;
-    if ((rc = sweep_grow(h, &h->d_stage, &h->cap_stage, total))) return rc;
+    if ((rc = h->d_stage.grow(h, total, "sweep"))) return rc;
     uint8_t* s = h->d_stage;
     const hipStream_t st = h->stream;
     std::vector<int32_t> h_cnt((size_t)C * cb * 3), h_box(boxes_or_null ? (size_t)C * cb * 4 : 0);
@@ -517,7 +473,7 @@ int og_sweep_counts_u8(og_sweep* h, const uint8_t* pred, const uint8_t* gt, cons
         return OG_OK;
     };
     for (int b0 = 0; b0 < N && !rc; b0 += chunk) rc = run(b0, (N - b0 < chunk) ? N - b0 : chunk);
-    if (rc) sweep_drain(h);
+    if (rc) og_stream_drain(h);
     return rc;
 }
 
@@ -528,7 +484,8 @@ int og_sweep_plan(int N, int H, int W, int n_conf, int n_hold, int chunk, char* 
     if ((long long)H * W > kSweepMaxPixels) return fail(OG_EINVAL, "H*W above " + std::to_string(kSweepMaxPixels) + " pixels");
     if (n_conf < 1 || n_conf > kSweepMaxConf) return fail(OG_EINVAL, "n_conf must be 1.." + std::to_string(kSweepMaxConf));
     if (n_hold < 1 || n_hold > kSweepMaxHold) return fail(OG_EINVAL, "n_hold must be 1.." + std::to_string(kSweepMaxHold));
-    if (chunk < 0 || chunk > kSweepMaxChunk) return fail(OG_EINVAL, "chunk must be 1.." + std::to_string(kSweepMaxChunk) + ", or 0 for the default");
+    const int rc = og_check_chunk(chunk, kSweepMaxChunk, true);
+    if (rc) return rc;
     const int mb = chunk ? chunk : sweep_default_chunk(H, W), cb = mb < N ? mb : N;
     std::string txt;
     int n = 0;

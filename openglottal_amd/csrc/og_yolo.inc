@@ -1060,19 +1060,7 @@ int og_yolo_plan(og_yolo* h, int B, int H, int W, int n_cu, const char* options,
     }
     c->arena = nullptr;
     if (rc) return rc;
-    std::string txt;
-    txt.reserve(plan.recs.size() * 96);
-    for (auto& r : plan.recs) {
-        char num[112];
-        snprintf(num, sizeof num, "|%u|%u|%u|%u|%u|%lld|%lld|", r.gx, r.gy, r.gz, r.block, r.lds, r.partial_bytes, r.counters);
-        txt += r.kernel;
-        txt += num;
-        txt += r.mod;
-        txt += '\n';
-    }
-    if (txt.size() + 1 > cap) return fail(OG_EINVAL, "plan text does not fit the buffer");
-    memcpy(out, txt.c_str(), txt.size() + 1);
-    return (int)plan.recs.size();
+    return og_plan_text(plan, kPlanMod, out, cap);
 }
 
 int og_yolo_last_launches(og_yolo* h, char* out, size_t cap) {

@@ -1,6 +1,8 @@
 """-m gpu: k_mjps_entropy (include/split/openglottal_hip_mjps.h), the split entropy pass of files without restart markers.  Device bytes
 and statuses = the split twin's = the sequential twin's = the same handle's with the mode off, in the smallest shapes where each
-mechanism can go wrong: several windows at sub 4, every form, damaged frames beside an intact one under guard zones."""
+mechanism can go wrong: several windows at sub 4, every form, damaged frames beside an intact one under guard zones; and the window
+machinery that only the kernel has (staging, data-end search, lane masks) on real windows at every sub, on bytes placed at window
+edges, on errors behind window 0 and at the four source alignments."""
 import numpy as np
 import pytest
 import torch
@@ -84,6 +86,131 @@ def test_damaged_frames_beside_an_intact_one_under_guard_zones():
             assert np.array_equal(frames[i], f), (sub, i)
         got, st = d.decode(files, statuses=True)                              # the streamed entry
         assert st.tolist() == [0, 1, 2, 4, 3, 0] and all(np.array_equal(got[i], want[i][0]) for i in range(B))
+
+
+# ── the kernel's windows: staging, the data-end search and the lane masks exist only on the device ─────────────────────────────────
+# Every case: device = the sequential twin = the split twin at the kernel's lanes per window, statuses and bytes.  The files and
+# their firing checks (the case holds what it is named for) are tests/mjps_cases.py's, held to the twins on the CPU by
+# tests/test_mjps_host.py.
+def _judge(files, sub, frames, status, what):
+    assert len(frames) == len(status) == len(files)
+    for i, j in enumerate(files):
+        ref, st = DC.twin(j)
+        out, st2, _ = SC.kernel_twin(j, sub)
+        assert int(status[i]) == st == st2, (what, sub, i, int(status[i]), st, st2)
+        assert np.array_equal(frames[i], ref) and np.array_equal(frames[i], out), (what, sub, i)
+
+
+def _guarded(d, blob, offsets, recs, B, H, W, label):
+    """The raw entry inside guard zones (buffer_guard.run_guarded: three runs, the slack 0x00 and 0xFF): `(frames, status)`."""
+    out = G.run_guarded("og_mjpd_decode_u8_dev", label,
+                        lambda p: lib().og_mjpd_decode_u8_dev(d._h, p["blob"], p["offsets"], p["recs"], B, H, W, p["frames"], B * H * W * 3, p["status"]),
+                        {"blob": blob, "offsets": offsets, "recs": recs}, {"frames": B * H * W * 3, "status": 4 * B}, kind="device", sync=d.sync)
+    return out["frames"].reshape(B, H, W, 3), out["status"].view(np.int32)
+
+
+def _three_entries(d, files, sub, what):
+    """The streamed entry, decode_resident and the raw og_mjpd_decode_u8_dev call."""
+    got, st = d.decode(files, statuses=True)
+    _judge(files, sub, got, st, what + ": streamed")
+    res, st = d.decode_resident(files, statuses=True)
+    assert res.is_cuda
+    _judge(files, sub, res.cpu().numpy(), st, what + ": decode_resident")
+    frames, st = _resident(d, files)
+    _judge(files, sub, frames, st, what + ": decode_dev")
+
+
+@pytest.mark.parametrize("name,sub", [(n, s) for n, v in SC.REAL.items() for s in v[3]], ids=lambda v: str(v))
+def test_real_windows_at_every_sub(name, sub):
+    """Pillow noise at quality 100 without DRI: 67 KB (128 x 128, three windows at the large subs) and 101 KB (128 x 192) in 4:4:4,
+    and the larger shape in 4:2:0 and gray, whose base and predictors carry over MCUs of six blocks and of one.  At sub 256, 512
+    and 1024 a full window has 128, 64 and 32 lanes: the rest of the workgroup is idle."""
+    j = SC.real_fires(name)
+    d = MJ.MjpegDecoder(split="auto", sub=sub)
+    _three_entries(d, [j], sub, name)
+    d.set_split("off")                                                        # the same handle, the lane per interval
+    got, st = d.decode([j], statuses=True)
+    assert not st.any() and np.array_equal(got[0], DC.twin(j)[0])
+
+
+@pytest.mark.parametrize("sub", [256, 4])
+def test_frames_of_different_window_counts_in_one_launch(sub):
+    """chunk 3, five frames: each workgroup leaves its window loop on its own -- after three windows, after one short one, at an
+    error in its second."""
+    files = list(SC.mixed_fires(sub))
+    d = MJ.MjpegDecoder(chunk=3, split="auto", sub=sub)
+    got, st = d.decode(files, statuses=True)
+    _judge(files, sub, got, st, "mixed: streamed")
+    res, st = d.decode_resident(files, statuses=True)
+    _judge(files, sub, res.cpu().numpy(), st, "mixed: decode_resident")
+    assert st.tolist() == [0, 0, 0, 0, 1]
+
+
+@pytest.mark.parametrize("sub", [4, 8])
+def test_bytes_placed_at_window_edges(sub):
+    """Hand-made gray scans, windows of 1024 and 2048 bytes: a stuffed pair across Wn and across 2 Wn, one whose FF is the last
+    staged byte of window 0, one on a dword edge of the end search, a lane of window 1 that starts on the 00; the data end at Wn - 1,
+    Wn, Wn + 1, Wn + K - 1, Wn + K and Wn + K + 1 in a complete frame (the FF has to be found; behind Wn a second window of one to
+    five lanes), the same six lengths as truncated scans that end without any FF, and a truncated scan of exactly Wn bytes whose last
+    symbol ends with its last bit: there only the open end of window 0's last lane finds the missing bits."""
+    d = MJ.MjpegDecoder(split="auto", sub=sub)
+    _three_entries(d, [SC.edge_fires(n, sub) for n in SC.EDGES], sub, "edges")
+    for part in (SC.ENDS[:3], SC.ENDS[3:]):
+        _three_entries(d, [SC.end_fires(n, sub) for n in part], sub, f"ends {part}")
+        _three_entries(d, [SC.cut_fires(n, sub) for n in part], sub, f"cuts {part}")
+    _three_entries(d, [SC.symbol_edge_fires(sub)], sub, "a scan of exactly Wn bytes that ends on a symbol's last bit")
+
+
+def test_a_hand_made_scan_of_three_windows_at_sub_1024():
+    """384 blocks of 63 ten-bit AC values, 77 KB: every lane of 1024 bytes holds five blocks."""
+    j = SC.three_windows_at_1024()
+    assert SC.kernel_twin(j, 1024)[2]["windows"] >= 3
+    for sub in (1024, 512):
+        _three_entries(MJ.MjpegDecoder(split="auto", sub=sub), [j], sub, "three windows at 1024")
+
+
+@pytest.mark.parametrize("built_for", [4, 8])
+def test_errors_behind_window_0_under_guard_zones(built_for):
+    """64 x 128 gray: a truncation, a ZRL past 63 and a DC prediction out of range in window 1, an invalid code in window 2, an
+    intact neighbour on each side; base, pred0 and the carry are not 0 where the error key is made and the erase pass runs.  The files
+    built for the windows of one sub also run at the other."""
+    for name in SC.late_errors(built_for):
+        SC.late_fires(name, built_for)
+    for sub in (4, 8):
+        d = MJ.MjpegDecoder(split="auto", sub=sub)
+        for names in SC.LATE_BATCHES:
+            cases = [SC.late_errors(built_for)[n] for n in names]
+            files = [j for j, _, _ in cases]
+            blob, offsets, recs, tabs, form = MJ.records_host(files)
+            assert (form["H"], form["W"], form["Ri"]) == (64, 128, 0)
+            d.set_tables(tabs, form["sampling"], form["Ri"])
+            frames, st = _guarded(d, blob, offsets, recs, len(files), 64, 128, f"late errors of sub {built_for} at sub {sub}")
+            assert st.tolist() == [claim for _, claim, _ in cases]
+            _judge(files, sub, frames, st, f"late {names}")
+            got, st = d.decode(files, statuses=True)
+            _judge(files, sub, got, st, f"late {names}: streamed")
+
+
+@pytest.mark.parametrize("which", ["hand-made, sub 4", "pillow, sub 256"])
+def test_the_four_source_alignments(which):
+    """The caller owns `offsets`: the same file at four consecutive bytes of the blob, so that the staging's `a` (the scan's address
+    modulo 4) takes every value; the bytes around the file are 0x00 in one guarded run and 0xFF in the other."""
+    sub = 4 if which.startswith("hand") else 256
+    j = SC.edge_fires("pair-across-Wn", 4) if sub == 4 else SC.real_fires("444-128x128")
+    assert SC.kernel_twin(j, sub)[2]["windows"] >= 3
+    info = MJ.parse(j)
+    H, W = info["H"], info["W"]
+    _, offsets, recs, tabs, form = MJ.records_host([j])
+    d = MJ.MjpegDecoder(split="auto", sub=sub)
+    d.set_tables(tabs, form["sampling"], form["Ri"])
+    seen = set()
+    for o in range(64, 68):
+        shifted = offsets + o
+        seen.add(int(shifted[0] + recs[0, 0]) & 3)
+        blob = lambda fill, o=o: np.concatenate([np.full(o, fill, np.uint8), np.frombuffer(j, np.uint8), np.full(61, fill, np.uint8)])
+        frames, st = _guarded(d, blob, shifted, recs, 1, H, W, f"{which}, file at byte {o}")
+        _judge([j], sub, frames, st, f"file at byte {o}")
+    assert recs[0, 0] == info["scan_offset"] and seen == {0, 1, 2, 3}
 
 
 def test_files_with_restart_markers_take_the_old_kernel():

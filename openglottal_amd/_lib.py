@@ -1,7 +1,8 @@
 """ctypes binding of ``libopenglottal_hip.so`` (include/openglottal_hip.h, include/openglottal_hip_crops.h,
 include/openglottal_hip_classic.h, include/openglottal_hip_gated.h, include/openglottal_hip_classic_tiled.h,
 include/openglottal_hip_overlay.h, include/openglottal_hip_sweep.h, include/openglottal_hip_gate.h,
-include/openglottal_hip_mjpeg.h, include/decode/openglottal_hip_mjpd.h, include/split/openglottal_hip_mjps.h).
+include/openglottal_hip_mjpeg.h, include/decode/openglottal_hip_mjpd.h, include/split/openglottal_hip_mjps.h,
+include_ext/openglottal_hip_png.h).
 
 cffi is not installed in the build image, so the thin C-ABI layer
 the north-star asks for is bound with ctypes; the declarations below are the
@@ -272,6 +273,26 @@ MJPS_PROTOTYPES = {
     "og_jpegs_decode_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); the complete export list of include_ext/openglottal_hip_png.h (PNG files decoded on the device)
+PNG_PROTOTYPES = {
+    "og_png_limit": (C.c_longlong, [C.c_int]),
+    "og_pngd_parse_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "og_pngd_inflate_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "og_pngd_decode_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "og_pngd_records_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                       C.c_int, C.c_void_p, C.c_void_p]),
+    "og_png_create": (C.c_void_p, []),
+    "og_png_destroy": (None, [C.c_void_p]),
+    "og_png_sync": (C.c_int, [C.c_void_p]),
+    "og_png_set_chunk": (C.c_int, [C.c_void_p, C.c_int]),
+    "og_png_set_palettes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "og_png_decode_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]),
+    "og_png_decode_stream": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "og_png_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
+}
+
 
 def lib() -> C.CDLL:
     """Load the HIP library once; fail loudly if it is not built."""
@@ -296,7 +317,7 @@ def lib() -> C.CDLL:
         for name, (res, args) in (list(PROTOTYPES.items()) + list(CROP_PROTOTYPES.items()) + list(CLASSIC_PROTOTYPES.items())
                                   + list(GATED_PROTOTYPES.items()) + list(TILED_PROTOTYPES.items()) + list(OVERLAY_PROTOTYPES.items())
                                   + list(SWEEP_PROTOTYPES.items()) + list(GATE_PROTOTYPES.items()) + list(MJPEG_PROTOTYPES.items())
-                                  + list(MJPD_PROTOTYPES.items()) + list(MJPS_PROTOTYPES.items())):
+                                  + list(MJPD_PROTOTYPES.items()) + list(MJPS_PROTOTYPES.items()) + list(PNG_PROTOTYPES.items())):
             fn = getattr(l, name)  # AttributeError if a symbol is missing: also loud
             fn.restype = res
             fn.argtypes = args

@@ -62,7 +62,8 @@ def add_infer_parser(sub):
 def _decode_flag(r) -> None:
     r.add_argument("--decode", choices=["host", "device", "auto"], default="host",
                    help="host (default): videos are decoded on the host, as until now; device: an MJPG .avi (or a directory of .jpg "
-                        "frames of one size) goes to the device compressed and is decoded there (baseline JPEG only); auto: device, "
+                        "frames of one size) goes to the device compressed and is decoded there (baseline JPEG only), and so does a "
+                        "directory of .png frames of one size (8-bit, not interlaced); auto: device, "
                         "and the host loop, with one line on stderr, when the decoder refuses the first frame")
     r.add_argument("--decode-split", choices=["off", "auto"], default="off",
                    help="with --decode device or auto.  off (default): a lane per restart interval, so a file without restart markers "
@@ -91,6 +92,10 @@ def _infer_jobs(a):
             video = None
             if all(p.lower().endswith((".jpg", ".jpeg")) for p in paths):
                 video = open_compressed(a.input, a.decode, a.decode_split)
+            elif all(p.lower().endswith(".png") for p in paths):   # PNG frames of one size: inflate and unfilter on the device
+                from .png import open_compressed as open_png
+
+                video = open_png(a.input, a.decode)
             elif a.decode == "auto":
                 print(f"--decode auto: {a.input} is decoded on the host: it holds images that are no .jpg files", file=sys.stderr)
             else:
@@ -362,7 +367,14 @@ def _decoded_on_device(a):
 
     if str(a.video).endswith((".npy", ".npz")):
         raise SystemExit(f"--decode {a.decode} is for compressed input (an MJPG .avi or a directory of .jpg frames), not {a.video}")
-    video = open_compressed(str(a.video), a.decode, a.decode_split)
+    exts = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff")
+    names = [n for n in os.listdir(str(a.video)) if n.lower().endswith(exts)] if os.path.isdir(str(a.video)) else []
+    if names and all(n.lower().endswith(".png") for n in names):   # a directory of .png frames only
+        from .png import open_compressed as open_png
+
+        video = open_png(str(a.video), a.decode)
+    else:
+        video = open_compressed(str(a.video), a.decode, a.decode_split)
     return a.video if video is None else video.frames_host()
 
 

@@ -1,7 +1,9 @@
 """Cases of the PNG decoder tests (tests/test_png_*.py, tests/test_gpu_png*.py): a token-level deflate WRITER (stored, fixed and
 dynamic blocks from explicit literal / (length, distance) tokens and explicit code lengths), a PNG assembler (filter type per row,
 IDAT split at any byte, CRCs from zlib.crc32), an independent numpy decoder over zlib.decompress, the valid set and the hostile corpus.
-Every stream meant to be valid is checked with zlib.decompress where it is made, every stream meant to be invalid must make zlib raise."""
+Every stream meant to be valid is checked with zlib.decompress where it is made, every stream meant to be invalid must make zlib raise.
+The ring files (ring_files, deep_errors) put matches, stored blocks and errors on the seams of the decoder's 32 KiB window; lz_expand,
+match_facts, token_spans and writers give the plain meaning of their tokens, from which tests/test_png_host.py asserts each seam."""
 import functools
 import heapq
 import io
@@ -429,6 +431,233 @@ def far_match_file():
     return gray_file(H, W, lambda w: fixed(w, toks, True), bytes(raw))
 
 
+# ── the ring files: matches and stored blocks on the seams of k_png_inflate's 32 KiB window ────────────────────────────────────────────
+WINDOW = 32768
+
+
+def lz_expand(tokens):
+    """the plain LZ77 meaning of a token list, byte by byte and with no ring: a literal (int), a stored run ("S", bytes), a match
+    (length, distance)"""
+    out = bytearray()
+    for t in tokens:
+        if isinstance(t, int):
+            out.append(t)
+        elif t[0] == "S":
+            out += t[1]
+        else:
+            for _ in range(t[0]):
+                out.append(out[len(out) - t[1]])
+    return bytes(out)
+
+
+def token_spans(tokens):
+    """[(pos, length)] of every token"""
+    pos, out = 0, []
+    for t in tokens:
+        n = 1 if isinstance(t, int) else len(t[1]) if t[0] == "S" else t[0]
+        out.append((pos, n))
+        pos += n
+    return out
+
+
+def match_facts(tokens):
+    """[(pos, len, dist)] of every match"""
+    return [(p, t[0], t[1]) for t, (p, _) in zip(tokens, token_spans(tokens)) if not isinstance(t, int) and t[0] != "S"]
+
+
+def writers(tokens):
+    """the index of the token that wrote each output byte"""
+    return np.concatenate([np.full(n, i, np.int64) for i, (_, n) in enumerate(token_spans(tokens))])
+
+
+def ring_ft(r):
+    return (0, 2, 0, 2, 1, 0, 2, 3, 0, 2, 4)[r % 11]                  # (mostly the two types the numpy unfilter does a row at a time)
+
+
+def ring_fill(shape, H, W, seed, force=None):
+    """shape: blocks ("stored", n) | ("fixed", items) | ("dynamic", items), items ("lit", n) | (length, distance) -> the same blocks with
+    bytes in them and the H * (1 + W) raw bytes they mean.  Every byte is seeded random except the row starts (ring_ft) and the bytes
+    a match copies onto a row start, which take that row's filter type; force {pos: value} sets the origin of a byte after that."""
+    stride, N = 1 + W, H * (1 + W)
+    origin, pos = np.arange(N), 0
+    for b in shape:
+        for it in ([("lit", b[1])] if b[0] == "stored" else b[1]):
+            if it[0] == "lit":
+                pos += it[1]
+            else:
+                for _ in range(it[0]):
+                    origin[pos] = origin[pos - it[1]]
+                    pos += 1
+    assert pos == N, (pos, N)
+    base = np.random.default_rng(seed).integers(0, 256, N).astype(np.uint8)
+    for r in range(H):
+        base[origin[r * stride]] = ring_ft(r)
+    for p, v in (force or {}).items():
+        base[origin[p]] = v
+    raw = base[origin].tobytes()
+    blocks, pos = [], 0
+    for b in shape:
+        if b[0] == "stored":
+            blocks.append(("stored", raw[pos:pos + b[1]]))
+            pos += b[1]
+            continue
+        toks = []
+        for it in b[1]:
+            if it[0] == "lit":
+                toks += list(raw[pos:pos + it[1]])
+                pos += it[1]
+            else:
+                toks.append(it)
+                pos += it[0]
+        blocks.append((b[0], toks))
+    assert lz_expand(block_tokens(blocks)) == raw
+    return blocks, raw
+
+
+def block_tokens(blocks):
+    return [t for b in blocks for t in ([("S", b[1])] if b[0] == "stored" else b[1])]
+
+
+def write_blocks(w, blocks, final=True, kw=None, marks=None):
+    """the blocks in order, the last one final; kw {block index: arguments of `dynamic`}; marks, a list, receives per block
+    (bit position of its header, byte position of a stored block's data or None)"""
+    for i, b in enumerate(blocks):
+        last, at = final and i == len(blocks) - 1, w.bitpos()
+        if b[0] == "stored":
+            stored(w, b[1], last)
+        elif b[0] == "fixed":
+            fixed(w, b[1], last)
+        else:
+            dynamic(w, b[1], last, **(kw or {}).get(i, {}))
+        if marks is not None:
+            marks.append((at, len(w.out) - len(b[1]) if b[0] == "stored" else None))
+
+
+def token_bitpos(blocks, bi, ti):
+    """the bit of the deflate data at which token ti of the fixed block bi starts"""
+    w = Bits()
+    write_blocks(w, blocks[:bi], final=False)
+    fixed(w, blocks[bi][1][:ti], False, eob=False)
+    return w.bitpos()
+
+
+class Ring:
+    def __init__(self, name, H, W, blocks, raw):
+        self.name, self.H, self.W, self.blocks, self.raw, self.marks = name, H, W, blocks, raw, []
+        self.tokens = block_tokens(blocks)
+        self.file = gray_file(H, W, lambda w: write_blocks(w, blocks, marks=self.marks), raw)
+        self.z = stream_of(self.file)
+
+    def block_pos(self, bi):
+        return sum(n for _, n in token_spans(block_tokens(self.blocks[:bi])))
+
+
+R4_GAPS = (1, 63, 64, 65, 100, 257)
+R5_DISTS = (1, 2, 3, 63, 64, 65, 127, 128, 129, 257)
+
+
+def _pad(shape, N):
+    used = sum(b[1] if b[0] == "stored" else sum(it[1] if it[0] == "lit" else it[0] for it in b[1]) for b in shape)
+    return shape + [("stored", N - used)]
+
+
+@functools.lru_cache(None)
+def ring_files():
+    """{name: Ring}: 8-bit gray files from the token writer, bulk in stored blocks, each holding the seams its name states
+    (tests/test_png_host.py asserts from the tokens that it does)"""
+    lit, out = (lambda n: ("lit", n)), {}
+
+    def add(name, H, W, shape, seed):
+        out[name] = Ring(name, H, W, *ring_fill(_pad(shape, H * (1 + W)) if shape[-1][0] != "dynamic" else shape, H, W, seed))
+
+    # R1: a match out of a stored block in the first window; a stored block across the wrap point and a match out of both its sides
+    add("ring-stored-match", 172, 199, [("stored", 600), ("fixed", [(258, 300), lit(10)]), ("stored", 31000), ("stored", 2000),
+                                        ("fixed", [(258, 1200), lit(6)])], 31)
+    # R2, R3: 258 bytes written across the wrap at dist > len (32 768) and dist < len (65 536); a source across the wrap
+    add("ring-wrap-258", 254, 259, [("stored", 32600), ("fixed", [lit(68), (258, 1000), lit(1074), (258, 1400), lit(4)]), ("stored", 31174),
+                                    ("fixed", [lit(4), (258, 7), lit(3)])], 32)
+    # R2, R3: 3 bytes, two before the wrap and one after it, at dist > len and dist < len; a source of 5 bytes across the wrap, repeated
+    add("ring-wrap-3", 254, 259, [("stored", 32700), ("fixed", [lit(66), (3, 1000), lit(2), (258, 5), lit(3)]), ("stored", 32400),
+                                  ("fixed", [lit(102), (3, 2), lit(3)])], 33)
+    # R4: 258 bytes at 32 768 - dist = 1 .. 257 overwrite the slots they have yet to read, in the second window and beyond 65 536
+    add("ring-self-overwrite", 272, 249, [("stored", 33000), ("fixed", [it for k in R4_GAPS for it in ((258, WINDOW - k), lit(5))]), ("stored", 31500),
+                                          ("fixed", [it for k in (0,) + R4_GAPS for it in ((258, WINDOW - k), lit(5))])], 34)
+    # R5, R6: short distances against the turn of 64 lanes; a literal read at once, the second time out of slot 32 767
+    add("ring-short-dist", 111, 299, [("fixed", [lit(300)] + [it for d in R5_DISTS for it in ((258, d), lit(3))] +
+                                       [(64, 1), lit(3), (65, 1), lit(3), lit(1), (20, 1)]), ("stored", 29634), ("fixed", [lit(68), (258, 1), lit(4)])], 35)
+    # R7: dynamic (286 / many distance codes) -> dynamic (258 / one) -> fixed -> stored -> dynamic
+    d3 = [lit(300), (258, 1000), lit(2), (40, 2900), lit(2), (7, 3)]
+    add("ring-tables", 15, 249, [("dynamic", [lit(2100), (258, 2000), lit(3), (3, 1), lit(2), (10, 30), lit(2), (50, 500), lit(2), (100, 1500), lit(2),
+                                             (20, 7), lit(5)]), ("dynamic", [lit(12), (3, 1), lit(5), (3, 1), lit(3), (3, 1)]),
+                                 ("fixed", [lit(20), (30, 100), lit(4)]), ("stored", 300), ("dynamic", d3 + [lit(3750 - 2940 - 609)])], 36)
+    # R8: Adler-32 where N - i passes through multiples of 65 521
+    row = bytes([255]) * 65520
+    raw1, raw2 = b"\x01" + row, b"\x01" + row + b"\x02" + row
+    out["adler-65521"] = Ring("adler-65521", 1, 65520, [("stored", raw1[:40000]), ("stored", raw1[40000:])], raw1)
+    out["adler-131042"] = Ring("adler-131042", 2, 65520, [("stored", raw2[:50000]), ("stored", raw2[50000:100000]), ("stored", raw2[100000:])], raw2)
+    return out
+
+
+def more_valid_files():
+    return [("wide-gray-1", simple(3, 1025, 0, 1, None, 41)), ("wide-pal-2", simple(3, 1023, 3, 2, None, 42)), ("wide-gray-4", simple(3, 1023, 0, 4, None, 43)),
+            ("paeth-rgba-65x600", simple(65, 600, 6, 8, [4] * 65, 44)),           # rb 2 400: lane 63 runs 63 steps behind across a long row
+            ("average-paeth-1000x3", simple(1000, 3, 0, 8, [3, 4] * 500, 45))]     # sixteen bands
+
+
+# ── errors beyond the first window: the ring files, damaged ─────────────────────────────────────────────────────────────────────────
+def _refused(z):
+    try:
+        zlib.decompress(z)
+    except zlib.error:
+        return z
+    raise AssertionError("zlib accepts a stream meant to be invalid")
+
+
+@functools.lru_cache(None)
+def deep_errors():
+    """[(name, file, expected status, raw position at which the decoder meets the error)]"""
+    R = ring_files()
+    out = []
+
+    def put(name, ring, z, status, pos):
+        out.append((name, assemble(ring.H, ring.W, 0, 8, z), status, pos))
+
+    def surplus(ring, blocks, extra):
+        return zstream(lambda w: write_blocks(w, blocks), ring.raw[:len(ring.raw) - extra[0]] + extra[1])
+
+    a = R["ring-stored-match"]                                                 # block 3: the stored block of 2 000 bytes from 31 868
+    put("deep-cut-in-stored", a, _refused(a.z[:2 + a.marks[3][1] + 1000]), 1, a.block_pos(3) + 1000)
+    b = R["ring-self-overwrite"]                                               # block 3, token 0: (258, 32 768) at 66 078; 8 + 5 bits, then 13 extra
+    at = token_bitpos(b.blocks, 3, 0) + 13
+    put("deep-cut-in-distance-extra", b, _refused(b.z[:2 + at // 8 + 1]), 1, b.block_pos(3))
+    c = R["ring-tables"]
+    f = [0] * 286
+    for s in token_syms(c.blocks[4][1])[0]:
+        f[s] += 1
+    over = huffman_lengths(f)
+    over[over.index(max(over))] -= 1                                           # a complete set with one code shortened
+    put("deep-third-header-over-subscribed", c, zbad(lambda w: write_blocks(w, c.blocks, kw={4: {"lit_lens": over}}), c.raw), 2, c.block_pos(4))
+    d = R["ring-wrap-258"]
+    bad = d.blocks[:1] + [("fixed", d.blocks[1][1] + [("L", 286)])] + d.blocks[2:]
+    put("deep-litlen-286", d, zbad(lambda w: write_blocks(w, bad), d.raw), 2, d.block_pos(2))
+    far = bytes(np.random.default_rng(8).integers(0, 256, 32767).astype(np.uint8))
+    out.append(("distance-32768-at-32767", assemble(182, 183, 0, 8, zbad(lambda w: (stored(w, far), fixed(w, [(258, 32768)], True)))), 3, 32767))
+    e = R["ring-wrap-3"]                                                       # cap 66 040; the last block is 500 stored bytes from 65 540
+    tail = e.blocks[-1][1]
+    put("deep-overflow-literal", b, surplus(b, b.blocks + [("fixed", [7])], (0, b"\x07")), 4, len(b.raw))
+    put("deep-overflow-match", e, surplus(e, e.blocks[:-1] + [("stored", tail[:243]), ("fixed", [(258, 9)])], (257, (tail[234:243] * 29)[:258])), 4,
+        len(e.raw) - 257)
+    put("deep-overflow-stored", e, surplus(e, e.blocks[:-1] + [("stored", tail + b"x")], (0, b"x")), 4, len(e.raw) - 500)
+    flip = bytearray(b.z)                                                      # block 2: the stored block of 31 500 bytes from 34 578
+    flip[2 + b.marks[2][1] + 65600 - b.block_pos(2)] ^= 0x40
+    put("deep-adler-flip", b, _refused(bytes(flip)), 5, 65600)
+    # a match that copies a 5 onto the start of row 65: valid deflate, the right Adler-32
+    blocks, raw = ring_fill(_pad([("stored", 6450), ("fixed", [("lit", 40), (20, 55), ("lit", 5)])], 7000), 70, 99, 37, force={6500: 5})
+    assert match_facts(block_tokens(blocks)) == [(6490, 20, 55)] and raw[6500] == 5 and all(raw[r * 100] <= 4 for r in range(70) if r != 65)
+    out.append(("deep-filter-5-by-match", assemble(70, 99, 0, 8, zstream(lambda w: write_blocks(w, blocks), raw)), 7, 6500))
+    return out
+
+
 @functools.lru_cache(None)
 def valid_cases():
     """[(name, file)]: every one decodes with status 0"""
@@ -484,6 +713,7 @@ def valid_cases():
     big = bytes([0]) + bytes(np.random.default_rng(9).integers(0, 256, 65534).astype(np.uint8))
     out.append(("stored-65535", assemble(1, 65534, 0, 8, zstream(lambda w: (stored(w, big), stored(w, b"", True)), big))))
     out.append(("far-match-32768", far_match_file()))
+    out += [(n, r.file) for n, r in ring_files().items()] + more_valid_files()
     return out
 
 
@@ -508,7 +738,8 @@ def stream_of(png):
 
 @functools.lru_cache(None)
 def hand_made_invalid():
-    """[(name, file, expected status or None)]: 17 x 9 RGB files around streams zlib refuses, and files the parser refuses"""
+    """[(name, file, expected status or None)]: 17 x 9 RGB files around streams zlib refuses, files the parser refuses, and the ring
+    files damaged beyond the first window (deep_errors)"""
     H, W = 9, 17
     rows = rng_rows(H, W, 2, 8, 11)
     raw = filter_rows(rows, [r % 5 for r in range(H)], 3)
@@ -588,6 +819,7 @@ def hand_made_invalid():
               ("ihdr-of-12-bytes", SIG + chunk(b"IHDR", ihdr()[:12]) + ok[33:]), ("empty", b""), ("signature-only", SIG),
               ("critical-unknown", ok[:33] + chunk(b"ABCD", b"xy") + ok[33:])]
     out += [(n, f, 6) for n, f in refuse]
+    out += [(n, f, s) for n, f, s, _ in deep_errors()]
     return out
 
 
@@ -604,7 +836,7 @@ def _mutants(png):
 
 @functools.lru_cache(None)
 def hostile_corpus():
-    """[file]: the mutants of a 17 x 9 RGB file and of its 4-bit palette twin, then the hand-made files"""
+    """[file]: the mutants of a 17 x 9 RGB file and of its 4-bit palette twin, then the hand-made files (the deep errors last)"""
     H, W = 9, 17
     rgb = simple(H, W, 2, 8, None, 21, smooth=True)
     pal = simple(H, W, 3, 4, None, 22, plte=palette(11, 3))

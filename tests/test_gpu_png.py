@@ -1,7 +1,9 @@
 """-m gpu: PNG files decoded on the device (include_ext/openglottal_hip_png.h).  The device gives the host twin's bytes AND statuses on
 the whole valid set and the whole hostile corpus of tests/png_cases.py (one call each, mixed sizes, chunk 3, so that micro-batches
-and pinned slots turn over), on the shapes that sit on the kernels' seams, resident and streamed, at C = 3 and C = 1; `read_pairs`
-feeds `evaluate_device`, and `cli infer --mode images --decode device` writes what `--decode host` writes."""
+and pinned slots turn over), on the shapes that sit on the kernels' seams, resident and streamed, at C = 3 and C = 1; the ring
+files and the errors beyond the first window are judged by the independent numpy decoder as well, and k_png_expand walks files larger
+than its grid; `read_pairs` feeds `evaluate_device`, and `cli infer --mode images --decode device` writes what `--decode host` writes."""
+import functools
 import io
 import os
 
@@ -86,6 +88,82 @@ def test_one_match_at_distance_32768(decoder):
     f = dict(PC.valid_cases())["far-match-32768"]
     got, st = hold_to_twin(decoder, [f])
     assert not st.any() and np.array_equal(got[0], PC.pillow(f))
+
+
+@functools.lru_cache(None)
+def judge(f, C):
+    """the independent decoder (zlib.decompress and the numpy unfilter), once per file and C: a change to the inline functions moves
+    device and twin together, this one stays"""
+    return PC.reference(f, C)
+
+
+def ring_call():
+    """the ring files and the other late files of the valid set, a small file of an odd number of raw bytes in front of each"""
+    late = [f for _, f in PC.valid_cases()[75:]]
+    files = [g for i, f in enumerate(late) for g in (PC.simple(1, 2 + 2 * i, 0, 8, None, i), f)]
+    at = P.records_host(files)["recs"]["raw_offset"][1::2]
+    assert len(late) == len(PC.ring_files()) + 5 and (at % 2).any() and len(set((at % 4).tolist())) > 2        # raw offsets off every alignment
+    return files
+
+
+@pytest.mark.parametrize("C", [3, 1])
+def test_the_ring_files_in_one_call(decoder, C):
+    """k_png_inflate's window -- stored blocks into the ring, copies across the wrap point, matches that overwrite their own source,
+    short distances against the 64-lane turn, tables rebuilt in LDS (tests/test_png_host.py asserts that each file holds its seam) --
+    streamed at chunk 3 and resident, against the twin and against the independent decoder"""
+    files = ring_call()
+    for resident in (False, True):
+        got, st = hold_to_twin(decoder, files, C, resident)
+        assert not st.any()
+        for i, (g, f) in enumerate(zip(got, files)):
+            assert np.array_equal(g, judge(f, C)), i
+
+
+@pytest.mark.parametrize("C", [3, 1])
+def test_errors_beyond_the_first_window_beside_valid_files(decoder, C):
+    deep = PC.deep_errors()
+    good = [PC.ring_files()["ring-tables"].file, PC.simple(9, 17, 2, 8, None, 1), PC.ring_files()["ring-stored-match"].file]
+    files = [g for i, (_, f, _, _) in enumerate(deep) for g in (f, good[i % 3])]
+    for resident in (False, True):
+        got, st = hold_to_twin(decoder, files, C, resident)
+        assert st.tolist() == [s for _, _, want, _ in deep for s in (want, 0)]
+        for i, (g, f) in enumerate(zip(got, files)):
+            assert (not g.any() and g.size) if i % 2 == 0 else np.array_equal(g, judge(f, C)), i
+
+
+STRIDED = (1, 255, 256, 257, 437, 4355)
+
+
+@pytest.mark.parametrize("C", [3, 1])
+def test_expand_walks_files_larger_than_its_grid(decoder, C):
+    """k_png_expand with max_pixels below the largest H * W: a grid of one or two workgroups per file walks every file in strides and
+    gives the bytes of the true max_pixels, nothing outside the records' ranges"""
+    pillow = dict(PC.valid_cases())
+    files = [PC.simple(1, 1, 0, 8, None, 1), PC.simple(15, 17, 2, 8, None, 2), PC.simple(16, 16, 6, 8, None, 3), PC.simple(1, 257, 4, 8, None, 4),
+             pillow["pillow-3-4-l6"], pillow["pillow-0-1-l6"], PC.simple(67, 65, 3, 8, None, 5)]
+    B, gap, edge = len(files), 5, 64
+    r = P.records_host(files, C)
+    recs = r["recs"].copy()
+    assert sorted({int(h) * int(w) for h, w in zip(recs["H"], recs["W"])}) == list(STRIDED) == sorted(STRIDED) and r["max_pixels"] == 4355
+    assert {3} <= set(recs["ctype"].tolist()) and 1 in recs["depth"].tolist()
+    recs["out_offset"] += gap * np.arange(B)
+    cap = r["out_bytes"] + gap * B
+    want = np.full(cap, 0x5A, np.uint8)
+    for f, rec in zip(files, recs):
+        px = judge(f, C).reshape(-1)
+        want[rec["out_offset"]:rec["out_offset"] + px.size] = px
+    decoder.set_palettes(r["pals"])
+    dev = [torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).cuda() for a in (r["zblob"], r["zoffsets"], recs)]
+    for max_pixels in (r["max_pixels"], 1, 256, 257):
+        whole = torch.full((edge + cap + edge,), 0x5A, dtype=torch.uint8, device="cuda")
+        out = whole[edge:edge + cap]
+        status = torch.full((B,), -1, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        decoder.decode_dev(*dev, B, C, r["raw_bytes"], max_pixels, out, cap, status)
+        decoder.sync()
+        assert status.cpu().tolist() == [0] * B, max_pixels
+        got = whole.cpu().numpy()
+        assert (got[:edge] == 0x5A).all() and (got[edge + cap:] == 0x5A).all() and np.array_equal(got[edge:edge + cap], want), max_pixels
 
 
 def realistic():

@@ -1,6 +1,7 @@
 """The host twin of the device PNG decoder (og_pngd_*_host, include_ext/openglottal_hip_png.h) against two other decoders: an
 independent numpy unfilter over zlib.decompress (tests/png_cases.py) and Pillow.  Valid files: status 0 and the same bytes as both.
-The hostile corpus: every status occurs, status 0 => Pillow's bytes, a non-zero status => every output byte 0.  No GPU."""
+The hostile corpus: every status occurs, status 0 => Pillow's bytes, a non-zero status => every output byte 0.  The ring files and
+the errors beyond the first window: each seam asserted from the file's tokens.  No GPU."""
 import collections
 import io
 import os
@@ -45,6 +46,107 @@ def test_the_valid_set_holds_what_it_claims():
     # zlib's own block types at levels 0 and 6: stored and dynamic
     first = lambda n: (PC.stream_of(dict(VALID)[n])[2] >> 1) & 3   # noqa: E731
     assert first("pillow-2-8-l0") == 0 and first("pillow-2-8-l6") == 2 and first("fixed") == 1
+
+
+def slot(p):
+    return p & (PC.WINDOW - 1)
+
+
+def wraps(p, n):
+    """n bytes from p run past the end of the 32 KiB ring"""
+    return slot(p) + n > PC.WINDOW
+
+
+@pytest.mark.parametrize("name", list(PC.ring_files()))
+def test_the_ring_files_hold_what_they_claim(name):
+    """the firing checks: every seam a ring file is named for, computed from its tokens.  A file that stops reaching its seam fails
+    here instead of going quiet."""
+    r = PC.ring_files()[name]
+    toks, stride = r.tokens, 1 + r.W
+    m, w, spans = PC.match_facts(toks), PC.writers(toks), PC.token_spans(toks)
+    info = P.parse(r.file)
+    assert (info["ctype"], info["depth"], info["raw_bytes"]) == (0, 8, len(r.raw)) and len(r.raw) <= 131042
+    assert PC.lz_expand(toks) == r.raw == zlib.decompress(r.z) and all(r.raw[y * stride] <= 4 for y in range(r.H))
+    is_stored = lambda i: not isinstance(toks[i], int) and toks[i][0] == "S"   # noqa: E731
+    src = lambda p, n, d: range(p - d, p - d + min(n, d))   # noqa: E731
+    if name == "ring-stored-match":                                           # R1
+        (p0, n0, d0), (p1, n1, d1) = m
+        assert p0 + n0 <= PC.WINDOW and {w[q] for q in src(p0, n0, d0)} == {0} and is_stored(0)
+        by, = {w[q] for q in src(p1, n1, d1)}
+        assert is_stored(by) and wraps(*spans[by]) and p1 - spans[by][0] - spans[by][1] == 0 and p1 < 2 * PC.WINDOW
+        assert p1 - d1 < PC.WINDOW < p1 - d1 + n1                             # the source spans the wrap point the stored block crossed
+    elif name in ("ring-wrap-258", "ring-wrap-3"):                            # R2, R3
+        n = 258 if name == "ring-wrap-258" else 3
+        across = [(p, ln, d) for p, ln, d in m if wraps(p, ln) and ln == n]
+        assert sorted(d > ln for _, ln, d in across) == [False, True] and len({p >> 15 for p, _, _ in across}) == 2
+        assert n != 3 or all(slot(p) == PC.WINDOW - 2 for p, _, _ in across)  # two bytes before the wrap, one behind it
+        assert any(wraps(p - d, min(ln, d)) and (d > ln) == (n == 258) for p, ln, d in m)
+    elif name == "ring-self-overwrite":                                       # R4
+        own = {(PC.WINDOW - d, min(p >> 15, 2)) for p, ln, d in m if ln == 258 and d + ln > PC.WINDOW}
+        assert own == {(k, 1) for k in PC.R4_GAPS} | {(k, 2) for k in (0,) + PC.R4_GAPS} and (66078, 258, PC.WINDOW) in m
+        assert {1, 63} <= set(PC.R4_GAPS) and {64, 65, 100, 257} <= set(PC.R4_GAPS)   # the same turn, the next turn's same lane, later turns
+    elif name == "ring-short-dist":                                           # R5, R6
+        assert {(ln, d) for p, ln, d in m if p + ln <= PC.WINDOW} >= {(258, d) for d in (1, 2, 3, 63, 64, 65, 127, 128, 129, 257)} | {(64, 1), (65, 1)}
+        at_once = [spans[i][0] for i in range(1, len(toks)) if isinstance(toks[i - 1], int) and not isinstance(toks[i], int) and toks[i][1] == 1]
+        assert any(slot(p) == 0 and p for p in at_once) and any(0 < p < PC.WINDOW for p in at_once)
+    elif name == "ring-tables":                                               # R7
+        assert [b[0] for b in r.blocks] == ["dynamic", "dynamic", "fixed", "stored", "dynamic"] and (r.z[2] >> 1) & 3 == 2
+        (l0, d0), (l1, d1), (l4, d4) = (PC.token_syms(r.blocks[i][1]) for i in (0, 1, 4))
+        assert max(l0) + 1 == 286 and max(l1) + 1 == 258 and len(set(l1)) < len(set(l0)) // 4    # HLIT; lsym keeps the old symbols behind the new
+        assert max(d0) + 1 > 20 and len(set(d0)) > 5 and set(d1) == {0} and len(set(d4)) > 2      # HDIST 1, one distance code
+        assert all(r.marks[i][0] % 8 for i in (1, 2, 3))                      # headers off the byte grid
+    else:                                                                     # R8
+        assert len(r.raw) in (65521, 131042) and len(r.raw) % 65521 == 0 and all(b[0] == "stored" for b in r.blocks)
+        assert set(r.raw[1:stride]) == {255} and set(r.raw[-r.W:]) == {255} and r.raw.count(255) == r.H * r.W
+
+
+def test_the_other_new_files_hold_what_they_claim():
+    files = dict(VALID)
+    for n, depth in (("wide-gray-1", 1), ("wide-pal-2", 2), ("wide-gray-4", 4)):
+        i = P.parse(files[n])
+        assert i["depth"] == depth and i["W"] > 1000 and (i["W"] * depth) % 8 and i["rb"] == (i["W"] * depth + 7) // 8
+    i = P.parse(files["paeth-rgba-65x600"])
+    assert (i["H"], i["rb"], i["bpp"]) == (65, 2400, 4) and set(zlib.decompress(PC.stream_of(files["paeth-rgba-65x600"]))[::2401]) == {4}
+    i = P.parse(files["average-paeth-1000x3"])
+    assert (i["H"], i["W"], (i["H"] + 63) // 64) == (1000, 3, 16) and zlib.decompress(PC.stream_of(files["average-paeth-1000x3"]))[:12:4] == bytes([3, 4, 3])
+    assert [n for n, _ in VALID[:75]][-1] == "far-match-32768" and len(VALID) == 75 + len(PC.ring_files()) + 5
+
+
+def test_errors_beyond_the_first_window():
+    """every deep-error file meets its error where its name says (from the tokens), gives its status and zeros; zlib refuses it,
+    or accepts it with another size (4) or with a row start of 5 (7)"""
+    cases = {n: (f, s, pos) for n, f, s, pos in PC.deep_errors()}
+    assert sorted(s for _, s, _ in cases.values()) == [1, 1, 2, 2, 3, 4, 4, 4, 5, 7]
+    for name, (f, want, pos) in cases.items():
+        px, st = P.decode_host(f, 3, statuses=True)
+        assert st == want and px is not None and not px.any() and not P.decode_host(f, 1, statuses=True)[0].any(), (name, st)
+        cap, z = P.parse(f)["raw_bytes"], PC.stream_of(f)
+        if want in (4, 7):
+            raw = zlib.decompress(z)
+            assert (len(raw) > cap) if want == 4 else (len(raw) == cap and raw[pos] == 5), name
+        else:
+            with pytest.raises(zlib.error):
+                zlib.decompress(z)
+        assert P.inflate_host(z, cap)[1] == (0 if want == 7 else want), name
+    at = {n: pos for n, (_, _, pos) in cases.items()}
+    cap = lambda n: P.parse(cases[n][0])["raw_bytes"]   # noqa: E731
+    assert PC.WINDOW < at["deep-cut-in-stored"] and 2 * PC.WINDOW <= at["deep-cut-in-distance-extra"] and PC.WINDOW < at["deep-litlen-286"]
+    tables = PC.ring_files()["ring-tables"]
+    assert at["deep-third-header-over-subscribed"] == tables.block_pos(4) and [b[0] for b in tables.blocks[:5]].count("dynamic") == 3
+    for n, length in (("deep-overflow-literal", 1), ("deep-overflow-match", 258), ("deep-overflow-stored", 501)):
+        assert cap(n) > 65536 and at[n] + length == cap(n) + 1 and at[n] >> 15 == cap(n) >> 15 == 2, n
+    assert at["deep-adler-flip"] > 65521 and at["deep-adler-flip"] % 250 and cap("deep-adler-flip") == 272 * 250
+    assert at["deep-filter-5-by-match"] % 100 == 0 and at["deep-filter-5-by-match"] // 100 >= 64
+
+
+def test_distance_32768_is_refused_at_32767_and_taken_at_32768():
+    bad = {n: f for n, f, _, _ in PC.deep_errors()}["distance-32768-at-32767"]
+    good = dict(VALID)["far-match-32768"]
+    assert P.decode_host(bad, statuses=True)[1] == 3 and P.decode_host(good, statuses=True)[1] == 0
+    assert P.parse(bad)["raw_bytes"] == P.parse(good)["raw_bytes"]
+    # the valid file's stream: 32 768 literals of the fixed code, then length 258 at distance 32 768; the refused one: one byte fewer
+    raw = zlib.decompress(PC.stream_of(good))
+    assert raw[32768:32768 + 258] == raw[:258] and raw[32768 + 258] != raw[258]
 
 
 def test_hand_made_invalid_streams_and_refusals():

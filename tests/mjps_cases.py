@@ -1,6 +1,6 @@
 """Inputs of the split entropy decoder's tests (helper module beside tests/mjpd_cases.py, whose Pillow files and hostile corpus it
-reuses): the (sub, lanes) pairs of the issue, a second hostile corpus from a 37x50 4:2:0 file without DRI, and a small Annex-K scan
-writer for hand-made gray files -- coefficient blocks and raw bits in, bytes out -- whose claimed statuses the sequential twin
+reuses): the (sub, lanes) pairs of the issue, a second hostile corpus from a 37x50 4:2:0 file without DRI, and hand-made gray files
+from mjpd_cases' Annex-K scan writer -- coefficient blocks and raw bits in, bytes out -- whose claimed statuses the sequential twin
 confirms; and the files of the kernel's windows -- Pillow noise of two and three real 32 768-byte windows, hand-made scans whose bytes
 a seeded search places on window edges, errors behind window 0 -- each with the firing check that the tests assert.  Everything is
 cached."""
@@ -10,6 +10,7 @@ import time
 import numpy as np
 
 import mjpd_cases as DC
+from mjpd_cases import Scan, _dht, pack_bits      # noqa: F401  (the writer lives beside the Pillow files; the restart-scan writer there builds on it)
 from openglottal_amd import mjpeg as MJ
 
 PAIRS = ((4, 2), (4, 256), (8, 3), (64, 256), (1024, 256))      # (sub, lanes per window)
@@ -62,100 +63,7 @@ def hostile():
     return first + corpus_of(base37(), "b37")
 
 
-# ── the scan writer ──────────────────────────────────────────────────────────────────────────────────────────────────────────────────
-def _dht(jpeg):
-    """`{(class, id): {symbol: (code, length)}}` of a file's DHT segments."""
-    tabs, at = {}, 2
-    while jpeg[at + 1] != 0xDA:
-        n = 2 + ((jpeg[at + 2] << 8) | jpeg[at + 3])
-        if jpeg[at + 1] == 0xC4:
-            s, i = jpeg[at + 4:at + n], 0
-            while i < len(s):
-                tc, th = s[i] >> 4, s[i] & 15
-                counts = s[i + 1:i + 17]
-                vals = s[i + 17:i + 17 + sum(counts)]
-                code, k, t = 0, 0, {}
-                for length in range(1, 17):
-                    for _ in range(counts[length - 1]):
-                        t[vals[k]] = (code, length)
-                        code += 1
-                        k += 1
-                    code <<= 1
-                tabs[(tc, th)] = t
-                i += 17 + sum(counts)
-        at += n
-    return tabs
-
-
-def pack_bits(bits):
-    """Bits -> the bytes of a scan: padded with 1-bits to a whole byte, a 00 stuffed behind every FF."""
-    a = np.asarray(bits, np.uint8)
-    a = np.concatenate([a, np.ones(-a.size % 8, np.uint8)])
-    return np.packbits(a).tobytes().replace(b"\xff", b"\xff\x00")
-
-
-class Scan:
-    """A gray scan bit by bit, in the Annex K luminance tables (taken from a Pillow file, which carries them)."""
-
-    def __init__(self, H, W):
-        self.H, self.W = H, W
-        self.head = DC.pillow_jpeg(H, W, "gray", 75, 0)
-        self.dc_tab, self.ac_tab = _dht(self.head)[(0, 0)], _dht(self.head)[(1, 0)]
-        self.blocks = ((H + 7) // 8) * ((W + 7) // 8)
-        self.bits = []
-
-    def raw(self, bits):
-        self.bits += [int(b) for b in bits]
-        return self
-
-    def _code(self, table, sym):
-        code, length = table[sym]
-        return self.raw(format(code, f"0{length}b"))
-
-    def _value(self, v):
-        size = int(abs(v)).bit_length()
-        if size:
-            self.raw(format(v if v > 0 else v + (1 << size) - 1, f"0{size}b"))
-        return size
-
-    def dc(self, diff):
-        self._code(self.dc_tab, int(abs(diff)).bit_length())
-        self._value(diff)
-        return self
-
-    def ac(self, run, v):
-        self._code(self.ac_tab, (run << 4) | int(abs(v)).bit_length())
-        self._value(v)
-        return self
-
-    def zrl(self):
-        return self._code(self.ac_tab, 0xF0)
-
-    def eob(self):
-        return self._code(self.ac_tab, 0x00)
-
-    def block(self, diff, ac=()):
-        """One block from its DC difference and `{zigzag index: value}`."""
-        self.dc(diff)
-        ac = dict(ac)
-        at = 1
-        for k in sorted(ac):
-            run = k - at
-            while run > 15:
-                self.zrl()
-                run -= 16
-            self.ac(run, ac[k])
-            at = k + 1
-        return self.eob() if at < 64 else self
-
-    def scan_bytes(self):
-        return pack_bits(self.bits)
-
-    def file(self, tail=b""):
-        lo, _ = DC.scan_span(self.head)
-        return self.head[:lo] + self.scan_bytes() + tail + b"\xff\xd9"
-
-
+# ── hand-made scans (the writer is mjpd_cases.Scan) ──────────────────────────────────────────────────────────────────────────────────
 @functools.lru_cache(maxsize=None)
 def handmade(H=8, W=64):
     """`{name: (file, claimed status)}` of gray H x W files (at least 8 blocks)."""

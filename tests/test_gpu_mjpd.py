@@ -33,8 +33,11 @@ def test_device_bytes_are_the_twins(decoder, H, W, form, restart):
     assert st == 0
     got = decoder.decode([j])
     assert got.shape == (1, H, W, 3) and np.array_equal(got[0], want)
-    res = decoder.decode_resident([j, j])
-    assert res.is_cuda and np.array_equal(res.cpu().numpy(), np.stack([want, want]))
+    j2 = DC.pillow_jpeg(H, W, form, 75, restart, False, 1)       # a second seed: two frames exchanged, or one decoded twice, would show
+    want2, st2 = DC.twin(j2)
+    assert st2 == 0 and not np.array_equal(want2, want)
+    res = decoder.decode_resident([j, j2])
+    assert res.is_cuda and np.array_equal(res.cpu().numpy(), np.stack([want, want2]))
 
 
 def test_per_frame_tables_and_a_ragged_last_micro_batch():
@@ -175,3 +178,200 @@ def test_iter_avi_blocks_and_the_resident_python_entry(tmp_path, decoder):
     decoder.decode_dev(*dev, 10, 24, 40, out, out.numel(), status)
     decoder.sync()
     assert not status.any() and np.array_equal(out.cpu().numpy(), want)
+
+
+# ── what the twin does not share with the device: k_mjpd_markers' strides and ballots, k_mjpd_entropy's lane map ───────────────────────
+# The files and the predicates that make each of them the case it is named for are tests/mjpd_cases.py's (asserted by every builder,
+# and again in tests/test_mjpd_host.py, where the valid ones are held to Pillow).
+def _wanted(files):
+    """The twins' `(frames, statuses)`; a frame the twin refuses is all zero."""
+    H, W = next(f.shape[:2] for f, _ in map(DC.twin, files) if f is not None)
+    frames = np.stack([DC.twin(j)[0] if DC.twin(j)[0] is not None else np.zeros((H, W, 3), np.uint8) for j in files])
+    return frames, [DC.twin(j)[1] for j in files]
+
+
+def _first_difference(got, want, labels=None):
+    bad = [i for i in range(len(want)) if not np.array_equal(got[i], want[i])]
+    return [(i, labels[i] if labels else None) for i in bad[:8]]
+
+
+def _dev_call(d, files, H, W):
+    """`decode_dev` after `set_tables`: frames and statuses, pre-filled with values no decode leaves."""
+    blob, offsets, recs, tabs, form = MJ.records_host(files)
+    d.set_tables(tabs, form["sampling"], form["Ri"])
+    dev = [torch.from_numpy(a).cuda() for a in (blob, offsets, recs)]
+    B = len(files)
+    out = torch.full((B, H, W, 3), 7, dtype=torch.uint8, device="cuda")
+    status = torch.full((B,), -1, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    d.decode_dev(*dev, B, H, W, out, out.numel(), status)
+    d.sync()
+    return out.cpu().numpy(), status.cpu().numpy()
+
+
+def _every_entry(files, H, W, chunk=128, labels=None):
+    """Device = twins, statuses and bytes, through `decode`, `decode_resident` and `decode_dev`."""
+    want, sts = _wanted(files)
+    d = MJ.MjpegDecoder(chunk=chunk)
+    got, st = d.decode(files, statuses=True)
+    assert st.tolist() == sts and not _first_difference(got, want, labels), ("decode", chunk, st.tolist(), _first_difference(got, want, labels))
+    got, st = d.decode_resident(files, statuses=True)
+    assert st.tolist() == sts and not _first_difference(got.cpu().numpy(), want, labels), ("decode_resident", chunk, st.tolist())
+    got, st = _dev_call(d, files, H, W)
+    assert st.tolist() == sts and not _first_difference(got, want, labels), ("decode_dev", chunk, st.tolist())
+    return want, sts
+
+
+def test_markers_many_to_a_wave_and_the_write_guard(decoder):
+    """[dense, doubled-all, dense', renumbered-late, dense, doubled-all], 8 x 2400 gray with nI = 300: up to 19 markers in one wave's
+    ballot, markers in all four waves of a stride, 299 of them (k & 7 wraps 37 times).  doubled-all has 598: without `k + 1 < nI`
+    its surplus would be written into the next frame's interval table and, from the last frame, into mstat[0..]."""
+    files = DC.guard_batch()
+    want, sts = _wanted(files)
+    assert sts == DC.GUARD_STATUS == [0, 5, 0, 5, 0, 5] and not np.array_equal(want[2], want[0])
+    frames, status = _resident_call(decoder, files, 8, 2400, "markers-guard")
+    assert status.tolist() == sts
+    assert not _first_difference(frames, want, DC.GUARD_ORDER), _first_difference(frames, want, DC.GUARD_ORDER)
+    assert np.array_equal(frames[0], frames[4]) and not np.array_equal(frames[2], frames[0]) and (frames[[1, 3, 5]] == 128).all()
+    for chunk in (2, 128):
+        got, st = MJ.MjpegDecoder(chunk=chunk).decode(files, statuses=True)
+        assert st.tolist() == sts and not _first_difference(got, want, DC.GUARD_ORDER), (chunk, st.tolist())
+
+
+def test_markers_damaged_behind_the_first_stride(decoder):
+    """Every damage of dense(0) between intact neighbours: a wrong number at marker 200, one wrong by 4 at marker 201 (right in its
+    low two bits), k % 7 from marker 8 on, the last marker
+    missing, FF D3 as the scan's last two bytes (i = n - 2), and a scan that ends in a lone FF (i = n - 1, status 0): behind it lies
+    a two-byte 'file' D0 D0 that the parser refuses, so a lane that read p[n] would find a marker there."""
+    cases = DC.damaged()
+    names = ["renumbered-late", "renumbered-by-4", "mod7", "removed-last", "end-marker", "ff-last"]
+    files, labels = [DC.dense(1)], ["dense'"]
+    for n in names:
+        files += [cases[n][0]] + ([b"\xd0\xd0"] if n == "ff-last" else []) + [DC.dense(0)]
+        labels += [n] + (["D0 D0"] if n == "ff-last" else []) + ["dense"]
+    want, sts = _wanted(files)
+    assert sts == [0, 5, 0, 5, 0, 5, 0, 5, 0, 5, 0, 0, 6, 0]
+    frames, status = _resident_call(decoder, files, 8, 2400, "markers-damaged")
+    assert status.tolist() == sts and not _first_difference(frames, want, labels), (status.tolist(), _first_difference(frames, want, labels))
+    got, st = decoder.decode(files, statuses=True)
+    assert st.tolist() == sts and not _first_difference(got, want, labels)
+
+
+def test_markers_on_stride_and_wave_edges_and_scan_lengths(decoder):
+    """8 x 96 gray, Ri = 1: a marker whose FF is byte 255, 254, 0, 63 or 64 of a stride (two seeds each), and scans of 0, 1 and 255
+    bytes mod 256 (the tail test i + 1 < n), in one call; every file is valid."""
+    files = [(f"edge-{R}-{w}", DC.edge_case(R, w)) for R in DC.EDGES for w in (0, 1)] + [(f"length-{r}", DC.length_case(r)) for r in DC.LENGTHS]
+    labels, files = [n for n, _ in files], [j for _, j in files]
+    want, sts = _wanted(files)
+    assert sts == [0] * 13 and len({f.tobytes() for f in want}) == 13
+    frames, status = _resident_call(decoder, files, 8, 96, "markers-edges")
+    assert status.tolist() == sts and not _first_difference(frames, want, labels), (status.tolist(), _first_difference(frames, want, labels))
+    got, st = MJ.MjpegDecoder(chunk=3).decode(files, statuses=True)
+    assert st.tolist() == sts and not _first_difference(got, want, labels)
+
+
+def test_markers_behind_strides_without_any(decoder):
+    """Intervals longer than a stride: `base` is carried over whole strides and wave slices that hold no marker."""
+    files = [DC.sparse(0), DC.sparse(1)]
+    H, W, _ = DC.SPARSE_SHAPE
+    assert all(DC.empty_strides(j) and DC.empty_slices(j) for j in files)
+    want, sts = _wanted(files)
+    assert sts == [0, 0] and not np.array_equal(want[0], want[1])
+    frames, status = _resident_call(decoder, files, H, W, "markers-sparse")
+    assert status.tolist() == sts and not _first_difference(frames, want)
+    assert np.array_equal(decoder.decode(files), want)
+
+
+def test_lane_map_a_workgroup_that_starts_inside_a_frame():
+    """Seven distinct 37 x 50 4:2:0 frames of seven table sets, nI = 12: 84 lanes, the second workgroup starts at frame 5, interval 4,
+    with frame 5's set in LDS and frame 6's read from global memory."""
+    files = list(DC.lane_files())
+    assert MJ.records_host(files)[3].shape[0] == 7 and 64 // MJ.parse(files[0])["nI"] == 5
+    _, sts = _every_entry(files, 37, 50)
+    assert sts == [0] * 7
+    # frame 5 damaged: the second workgroup's first frame is refused by k_mjpd_markers (set0 = -1), frame 6 decodes from global tables
+    broken = files[:5] + [DC.rst_removed(files[5])] + files[6:]
+    _, sts = _every_entry(broken, 37, 50)
+    assert sts == [0, 0, 0, 0, 0, 5, 0]
+    # frames 5 and 6 are frame 0's file: the second workgroup's LDS set is one that the first workgroup used too
+    shared = files[:5] + [files[0], files[0]]
+    assert MJ.records_host(shared)[3].shape[0] == 5 and MJ.records_host(shared)[2][:, 3].tolist() == [0, 1, 2, 3, 4, 0, 0]
+    _every_entry(shared, 37, 50)
+    # 36 lanes per micro-batch: three micro-batches through both slots
+    _every_entry(files, 37, 50, chunk=3)
+
+
+@pytest.mark.parametrize("nI", (3, 20))
+def test_lane_map_at_an_interval_count_that_does_not_divide_64(nI):
+    files, lane64 = DC.lane_batch(nI)
+    assert MJ.parse(files[0])["nI"] == nI and 64 % nI and lane64 == (64 // nI, 64 % nI) and lane64[0] < len(files)
+    _, sts = _every_entry(files, 37, 50)
+    assert sts == [0] * len(files)
+
+
+def _corpus_call(decoder, name):
+    base = DC.bases()[0 if name == "ri1" else 1]
+    files = [(f"{name}-base", base)] + [(label, j) for label, j in DC.hostile() if label.startswith(name + "-")]
+    labels, files = [n for n, _ in files], [j for _, j in files]
+    want, sts = _wanted(files)
+    got, st = decoder.decode(files, statuses=True)
+    wrong = [(labels[i], int(st[i]), sts[i]) for i in np.flatnonzero(st != np.asarray(sts))]
+    assert not wrong, wrong[:8]
+    assert not _first_difference(got, want, labels), _first_difference(got, want, labels)
+    assert not got[np.asarray(sts) == 6].any()
+    return sts
+
+
+def test_the_whole_hostile_corpus_ri1(decoder):
+    """The intact Ri = 1 base and all of its 1 285 damaged copies in one streamed call: every status and every frame the twin's."""
+    sts = _corpus_call(decoder, "ri1")
+    assert len(sts) == 1 + len(DC.bases()[0]) + 500 + 3 == 1286 and set(sts) >= {0, 1, 2, 3, 5, 6}
+
+
+def test_the_whole_hostile_corpus_nodri(decoder):
+    sts = _corpus_call(decoder, "nodri")
+    assert len(sts) == 1 + len(DC.bases()[1]) + 500 == 1275 and set(sts) >= {0, 1, 2, 3, 6}
+
+
+def test_narrow_planes_and_one_pixel_frames(decoder):
+    """Chroma of one or two columns (og_jpegd_chroma's replication branch) and of three (the first filtered one); 1 x 1 frames, where a
+    k_mjpd_idct workgroup has 8 to 24 live lanes per frame.  Three distinct seeds per call."""
+    assert {(W + 1) // 2 for _, W, form in DC.NARROW if form in ("422", "420")} == {1, 2, 3}
+    for H, W, form in DC.NARROW:
+        files = DC.narrow_files(H, W, form)
+        want, sts = _wanted(files)
+        assert sts == [0, 0, 0], (H, W, form)
+        got = decoder.decode_resident(files)
+        assert got.shape == (3, H, W, 3) and np.array_equal(got.cpu().numpy(), want), (H, W, form)
+        assert np.array_equal(decoder.decode(files), want), (H, W, form)
+
+
+def test_long_codes_from_lds_and_from_global_memory(decoder):
+    """Codes of 10..16 bits miss the 9-bit look-up; og_jpegd_symbol then walks maxcode/valoff/vals -- in the LDS copy when the frame's
+    set is the workgroup's first, in global memory otherwise.  The past-the-bound file has another table set (its DQT)."""
+    j, lengths = DC.long_codes()
+    assert lengths == tuple(DC.long_lengths(DC._dht(j)[(1, 0)])) and max(lengths) == 16 and sum(n >= 10 for n in lengths) >= 3
+    other = DC.past_the_bound()
+    for files in ([j, other, j], [other, j]):
+        assert MJ.records_host(files)[3].shape[0] == 2
+        want, sts = _wanted(files)
+        assert sts == [0] * len(files)
+        assert np.array_equal(decoder.decode(files), want)
+    c = DC.long_chroma()
+    assert max(DC.long_lengths(DC._dht(c)[(1, 1)])) > 9
+    files = [c, DC.pillow_jpeg(37, 50, "444", 95, 0, True, 4), c]
+    want, sts = _wanted(files)
+    assert sts == [0, 0, 0] and np.array_equal(decoder.decode_resident(files).cpu().numpy(), want)
+
+
+def test_past_the_bound_the_device_wraps_as_the_twin_does(decoder):
+    """Outside the header's BOUND only device = twin is claimed: uint32 wrap-around in both passes of og_jpegd_idct8."""
+    j = DC.past_the_bound()
+    want, sts = _wanted([j, j])
+    assert sts == [0, 0] and len(np.unique(want[0])) > 1
+    frames, status = _resident_call(decoder, [j, j], 8, 64, "past-the-bound")
+    assert status.tolist() == [0, 0] and np.array_equal(frames, want)
+    files = [DC._handmade_gray(dc, 255) for dc in (1023, -1023, 2047, -2047)]
+    want, sts = _wanted(files)
+    assert sts == [0] * 4
+    assert np.array_equal(decoder.decode(files), want)

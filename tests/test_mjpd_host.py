@@ -143,34 +143,19 @@ def test_hostile_input_terminates_inside_its_buffers_with_a_listed_status():
         assert DC.twin(dict(DC.hostile())[label])[1] == 5
 
 
-def _handmade_gray(dc, q):
-    """An 8x8 gray file of ONE coefficient: DC = dc, every quantisation step q."""
-    codes = {0: "00", 1: "010", 2: "011", 3: "100", 4: "101", 5: "110", 6: "1110", 7: "11110", 8: "111110", 9: "1111110", 10: "11111110",
-             11: "111111110"}                                             # Annex K.3, luminance DC
-    j = bytearray(DC.pillow_jpeg(8, 8, "gray"))
-    at = j.index(b"\xff\xdb")
-    j[at + 5:at + 69] = bytes([q]) * 64
-    lo, _ = DC.scan_span(bytes(j))
-    cat = abs(dc).bit_length()
-    bits = codes[cat] + (format(dc if dc >= 0 else dc + (1 << cat) - 1, f"0{cat}b") if cat else "") + "1010"      # EOB
-    bits += "1" * (-len(bits) % 8)
-    scan = bytes(int(bits[k:k + 8], 2) for k in range(0, len(bits), 8)).replace(b"\xff", b"\xff\x00")
-    return bytes(j[:lo]) + scan + b"\xff\xd9"
-
-
 def test_what_pillow_does_far_outside_the_sample_range():
     """libjpeg's C code limits samples through a table that wraps modulo 1024; the answer that counts is Pillow's.  Samples of
     128 + dc * q / 8: up to four times the range past either end Pillow saturates, as the twin's clamp does (the C table would give 0
     at 638 + 128).  Parity stops where Pillow's 16-bit first pass overflows (|4 * dc * q| >= 2^15); the header says so."""
     for dc, q in ((5, 255), (12, 255), (16, 255), (20, 255), (28, 255), (-5, 255), (-16, 255), (-20, 255), (-21, 255), (300, 16), (-300, 16)):
-        j = _handmade_gray(dc, q)
+        j = DC._handmade_gray(dc, q)
         assert abs(4 * dc * q) < 1 << 15
         want = DC.pillow_bgr(j)
         assert np.array_equal(MJ.decode_host(j), want), (dc, q)
         assert (want == (255 if dc > 0 else 0)).all()
     # far outside: the twin still answers, with status 0 and a clamped frame; no parity is claimed there
     for dc in (1023, -1023, 2047, -2047):
-        f, st = MJ.decode_host(_handmade_gray(dc, 255), statuses=True)
+        f, st = MJ.decode_host(DC._handmade_gray(dc, 255), statuses=True)
         assert st == 0 and f.shape == (8, 8, 3)
 
 
@@ -219,3 +204,81 @@ def test_the_int32_bound_of_the_header():
     E = 5900
     assert 31872 * E + 2 ** 10 < 2 ** 31 and 31872 * (11.32 * E + 4) + 2 ** 17 < 2 ** 31 and 4 * 8 ** 0.5 < 11.32
     assert 1024 + 255 * 8 / 2 < E                                            # any file encoded from pixels, any 8-bit table
+
+
+# ── the files of tests/test_gpu_mjpd.py's marker, lane-map, plane and code cases: what each is named for, on the CPU ───────────────────
+def _twin_is_pillows(j, label):
+    f, st = DC.twin(j)
+    assert st == 0 and np.array_equal(f, DC.pillow_bgr(j)), label
+
+
+def test_marker_placements_hold_on_the_bytes_and_the_files_are_pillows():
+    """Every valid restart-scan file: the builder asserts its placement (strides, wave slices, residues of the marker's FF and of the
+    scan's length mod 256) on the bytes it returns; the twin gives status 0 and Pillow's bytes."""
+    files = DC.valid_placements()
+    assert len(files) == 4 + 2 * len(DC.EDGES) + len(DC.LENGTHS) and len({j for _, j in files}) == len(files)
+    for label, j in files:
+        _twin_is_pillows(j, label)
+    assert not np.array_equal(DC.twin(DC.dense(0))[0], DC.twin(DC.dense(1))[0])
+    assert {R for R in DC.EDGES} == {(255,), (254,), (0,), (63, 64), (0, 255)} and set(DC.LENGTHS) == {0, 1, 255}
+    for seed in (0, 1):
+        assert DC.empty_strides(DC.sparse(seed)) and not DC.empty_strides(DC.dense(seed)) and not DC.empty_slices(DC.dense(seed))
+
+
+def test_damaged_markers_have_their_claimed_status_and_a_whole_frame():
+    """The seven damages of dense(0): the twin's status is the claimed one (5, and 0 for the scan that ends in a lone FF), and the frame
+    is written whole between its guard zones -- mid-gray for 5, since no interval is decoded."""
+    H, W = 8, 2400
+    cases = DC.damaged()
+    assert set(cases) == {"renumbered-late", "renumbered-by-4", "mod7", "removed-last", "doubled-all", "end-marker", "ff-last"}
+    for name, (j, claim) in cases.items():
+        assert MJ.parse(j)["status"] == 0 and DC.twin(j)[1] == claim == (0 if name == "ff-last" else 5), name
+        out = G.run_guarded("og_jpegd_decode_host", name, lambda p: lib().og_jpegd_decode_host(p["j"], len(j), p["out"], H * W * 3, p["st"]),
+                            {"j": np.frombuffer(j, np.uint8)}, {"out": H * W * 3, "st": 4})
+        assert out["st"].view(np.int32)[0] == claim
+        frame = out["out"].reshape(H, W, 3)
+        assert np.array_equal(frame, DC.twin(j)[0])
+        if claim == 5:
+            assert (frame == 128).all(), name
+        else:
+            assert np.array_equal(frame, DC.twin(DC.dense(0))[0])       # the missing EOI takes nothing from the last interval
+    assert [DC.twin(j)[1] for j in DC.guard_batch()] == DC.GUARD_STATUS
+
+
+def test_the_lane_map_files():
+    files = DC.lane_files()
+    for j in files:
+        _twin_is_pillows(j, "lane")
+    assert DC.twin(DC.rst_removed(files[5]))[1] == 5 and MJ.parse(DC.rst_removed(files[5]))["nI"] == 12
+    for nI, lane64 in ((3, (21, 1)), (20, (3, 4))):
+        batch, at = DC.lane_batch(nI)
+        assert at == lane64 and at[1] != 0                   # the second workgroup's first lane is not a frame's first interval
+        for j in set(batch):
+            _twin_is_pillows(j, nI)
+
+
+def test_narrow_planes_at_three_seeds():
+    assert {(W + 1) // 2 for _, W, form in DC.NARROW if form in ("422", "420")} == {1, 2, 3}     # both sides of cw <= 2
+    for H, W, form in DC.NARROW:
+        for j in DC.narrow_files(H, W, form):
+            assert (MJ.parse(j)["H"], MJ.parse(j)["W"], MJ.parse(j)["sampling"]) == (H, W, DC.SAMPLING[form])
+            _twin_is_pillows(j, (H, W, form))
+
+
+def test_long_codes_are_in_the_files_that_claim_them():
+    """The lengths come from the file's own DHT: with the Annex K luminance AC table 9, 10, 11, 12, 15 and 16 bits.  A code of 10 bits
+    or more misses the 9-bit look-up and is found by the maxcode walk."""
+    j, lengths = DC.long_codes()
+    assert lengths == tuple(DC.long_lengths(DC._dht(j)[(1, 0)])) and set(lengths) >= {9, 10, 16} and len(lengths) == 6
+    _twin_is_pillows(j, "long codes")
+    assert len(np.unique(DC.twin(j)[0])) > 8
+    _twin_is_pillows(DC.long_chroma(), "optimised chroma tables")
+
+
+def test_past_the_bound_the_twin_still_answers():
+    """Every quantisation step 255, DC at both ends of its range, every AC value +-1023: far outside the header's BOUND, where only
+    device = twin is claimed (Pillow differs in about half the bytes)."""
+    j = DC.past_the_bound()
+    assert MJ.parse(j)["status"] == 0 and (MJ.parse(j)["H"], MJ.parse(j)["W"]) == (8, 64)
+    f, st = DC.twin(j)
+    assert st == 0 and f.shape == (8, 64, 3) and len(np.unique(f)) > 1

@@ -2,7 +2,7 @@
 include/openglottal_hip_classic.h, include/openglottal_hip_gated.h, include/openglottal_hip_classic_tiled.h,
 include/openglottal_hip_overlay.h, include/openglottal_hip_sweep.h, include/openglottal_hip_gate.h,
 include/openglottal_hip_mjpeg.h, include/decode/openglottal_hip_mjpd.h, include/split/openglottal_hip_mjps.h,
-include_ext/openglottal_hip_png.h).
+include_ext/openglottal_hip_png.h, include_enc/openglottal_hip_pnge.h).
 
 cffi is not installed in the build image, so the thin C-ABI layer
 the north-star asks for is bound with ctypes; the declarations below are the
@@ -293,6 +293,27 @@ PNG_PROTOTYPES = {
     "og_png_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
 }
 
+# name -> (restype, argtypes); the complete export list of include_enc/openglottal_hip_pnge.h (PNG files encoded on the device)
+_PNGE_ENCODE = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+PNGE_PROTOTYPES = {
+    "og_pnge_limit": (C.c_longlong, [C.c_int]),
+    "og_pnge_bound": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "og_pnge_filter_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    "og_pnge_deflate_host": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "og_pnge_encode_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "og_pnge_create": (C.c_void_p, []),
+    "og_pnge_destroy": (None, [C.c_void_p]),
+    "og_pnge_sync": (C.c_int, [C.c_void_p]),
+    "og_pnge_set_chunk": (C.c_int, [C.c_void_p, C.c_int]),
+    "og_pnge_set_segment": (C.c_int, [C.c_void_p, C.c_int]),
+    "og_pnge_encode_u8_dev": (C.c_int, _PNGE_ENCODE),
+    "og_pnge_encode_stream_u8": (C.c_int, _PNGE_ENCODE),
+    "og_pnge_label_bbox_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "og_pnge_label_bbox_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "og_pnge_crop_tiles_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "og_pnge_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
+}
+
 
 def lib() -> C.CDLL:
     """Load the HIP library once; fail loudly if it is not built."""
@@ -317,7 +338,8 @@ def lib() -> C.CDLL:
         for name, (res, args) in (list(PROTOTYPES.items()) + list(CROP_PROTOTYPES.items()) + list(CLASSIC_PROTOTYPES.items())
                                   + list(GATED_PROTOTYPES.items()) + list(TILED_PROTOTYPES.items()) + list(OVERLAY_PROTOTYPES.items())
                                   + list(SWEEP_PROTOTYPES.items()) + list(GATE_PROTOTYPES.items()) + list(MJPEG_PROTOTYPES.items())
-                                  + list(MJPD_PROTOTYPES.items()) + list(MJPS_PROTOTYPES.items()) + list(PNG_PROTOTYPES.items())):
+                                  + list(MJPD_PROTOTYPES.items()) + list(MJPS_PROTOTYPES.items()) + list(PNG_PROTOTYPES.items())
+                                  + list(PNGE_PROTOTYPES.items())):
             fn = getattr(l, name)  # AttributeError if a symbol is missing: also loud
             fn.restype = res
             fn.argtypes = args

@@ -42,6 +42,10 @@ def add_infer_parser(sub):
     r.add_argument("--overlay-style", choices=["fill", "contour", "none"], default="fill")
     r.add_argument("--device", default="cuda")
     r.add_argument("--frames", choices=["npy", "png"], default="npy", help="png: additionally a directory of PNGs per video (Pillow)")
+    r.add_argument("--png", choices=["pillow", "device"], default="pillow",
+                   help="--frames png: pillow (default): the annotated frames come to the host and Pillow writes them, as until now; "
+                        "device: they are filtered, deflated and framed as PNG files on the device and only the files come back; the "
+                        "decoded pixels are the same")
     r.add_argument("--skip-unboxed", action="store_true",
                    help="--pipeline unet: run the U-Net only on the frames the detector gave a box (the same frames and areas)")
     r.add_argument("--label", action="store_true",
@@ -144,8 +148,14 @@ def _cmd_infer(ap, a) -> int:
     if a.decode != "host" and a.mode == "npy":
         ap.error("--decode device and auto are for compressed input (--mode avi, or --mode images with .jpg frames); a .npy holds "
                  "decoded frames")
-    if a.no_npy and a.frames == "png":
-        ap.error("--frames png needs the annotated frames on the host, which --no-npy leaves on the device")
+    device_png = a.png == "device"
+    if device_png and a.frames != "png":
+        ap.error("--png device goes with --frames png only: it says where those files are coded")
+    if device_png and a.label:
+        ap.error("--label draws on the host after the device pass, so it needs the annotated frames there; with --png device they are "
+                 "coded on the device before they leave it.  Drop one of the two")
+    if a.no_npy and a.frames == "png" and not device_png:
+        ap.error("--frames png needs the annotated frames on the host, which --no-npy leaves on the device; --png device codes them there")
     import numpy as np
 
     from . import TemporalDetector, UNet
@@ -173,6 +183,11 @@ def _cmd_infer(ap, a) -> int:
             import cv2
         except ImportError:
             print("OpenCV is not importable: annotated videos are written as <stem>_out.npy ([B,H,W,3] u8, BGR), not .avi")
+    png_encoder = None
+    if device_png:
+        from .png import PngEncoder
+
+        png_encoder = PngEncoder()
     os.makedirs(a.output_dir, exist_ok=True)
     rows = []
     for stem, frames in _infer_jobs(a):
@@ -185,7 +200,31 @@ def _cmd_infer(ap, a) -> int:
         w = None if a.no_npy else I.NpyWriter(out_npy, len(frames))
         avi = None
         wave, at = [], 0
-        if device_avi:
+        if device_png:
+            # the block loop of iter_pipeline with the PNG coder (and, with --avi device, the JPEG coder) behind the overlay; the frames
+            # come back only for the .npy and for OpenCV's writer
+            for files, area, jpeg, blk in I.iter_pipeline_png(frames, detector, a.pipeline, model, a.device, a.overlay_style,
+                                                              png_encoder=png_encoder, mjpeg_encoder=encoder, frames=not a.no_npy,
+                                                              skip_unboxed=a.skip_unboxed):
+                I.write_png_files(os.path.join(a.output_dir, f"{stem}_out"), at, files)
+                if device_avi:
+                    if avi is None:
+                        H, W = np.asarray(frames[0]).shape[:2]
+                        avi = AviWriter(out_avi, W, H, 25.0)
+                    avi.write(*jpeg)
+                elif cv2 is not None:
+                    if avi is None:
+                        avi = cv2.VideoWriter(out_avi, cv2.VideoWriter_fourcc(*"MJPG"), 25.0, (blk.shape[2], blk.shape[1]))
+                    for f in blk:
+                        avi.write(f)
+                if w is not None:
+                    w.write(blk)
+                wave.append(area)
+                at += len(files)
+            if avi is not None:
+                avi.close() if device_avi else avi.release()
+                print(f"  Wrote {out_avi}")
+        elif device_avi:
             # the block loop of iter_pipeline with the JPEG coder behind the overlay; the frames come back only for the .npy
             for item in I.iter_pipeline_mjpeg(frames, detector, a.pipeline, model, a.device, a.overlay_style, encoder=encoder,
                                               frames=not a.no_npy, skip_unboxed=a.skip_unboxed):
@@ -291,11 +330,55 @@ def _cmd_sweep(a) -> int:
     return 0
 
 
+def add_crop_cache_parser(sub):
+    """The pre-computation of `scripts/train_unet_crop.py` (openglottal_amd/cropcache.py)."""
+    r = sub.add_parser("crop-cache", help="the crop trainer's cache (cache/<split>/images|masks/%%06d.png and meta.json), decoded, "
+                                          "cropped and PNG-coded on the device")
+    r.add_argument("--images", required=True, help="a directory of .png images")
+    r.add_argument("--labels", required=True, help="the directory of their labels: N.png, or N<label-suffix>.png")
+    r.add_argument("--out", required=True, help="the cache directory (the trainer's --cache-dir)")
+    r.add_argument("--split", required=True)
+    r.add_argument("--roi", choices=["yolo", "gt"], default="yolo", help="yolo: the detector's best box; gt: the label's tight box")
+    r.add_argument("--yolo-weights", default=None)
+    r.add_argument("--label-suffix", default="")
+    r.add_argument("--crop-size", type=int, default=256)
+    r.add_argument("--padding", type=int, default=8)
+    r.add_argument("--conf", type=float, default=0.25)
+    r.add_argument("--max-images", type=int, default=0)
+    r.add_argument("--host", action="store_true", help="decode, crop and encode on the host: the twin the device is held to (same files)")
+    return r
+
+
+def _cmd_crop_cache(ap, a) -> int:
+    if a.roi == "yolo" and not a.yolo_weights:
+        ap.error("--yolo-weights is required for --roi yolo")
+    if a.crop_size < 1:
+        ap.error("--crop-size must be positive")
+    if a.padding < 0:
+        ap.error("--padding must not be negative")
+    from . import cropcache
+
+    names, images, labels = cropcache.list_pairs(a.images, a.labels, a.label_suffix, a.max_images)
+    if not names:
+        raise SystemExit(f"No .png images found in {a.images}")
+    detector = None
+    if a.roi == "yolo":
+        from .yolo import load_detector_backend
+
+        detector = load_detector_backend(a.yolo_weights)
+    where = "host" if a.host else "device"
+    res = cropcache.build(images, labels, a.out, a.split, roi=a.roi, detector=detector, crop_size=a.crop_size, padding=a.padding, conf=a.conf,
+                          label_suffix=a.label_suffix, names=names, decode=where, encode=where)
+    print(f"{res['n']} of {len(names)} samples kept -> {os.path.join(a.out, a.split)}")
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="openglottal_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
     add_infer_parser(sub)
     add_sweep_parser(sub)
+    add_crop_cache_parser(sub)
     r = sub.add_parser("run")
     r.add_argument("video")
     r.add_argument("--pipeline", choices=["vft", "guided-vft", "unet", "unet-only", "yolo-crop+unet"], default="unet-only")
@@ -322,6 +405,8 @@ def main(argv=None) -> int:
         return _cmd_infer(ap, a)
     if a.cmd == "sweep":
         return _cmd_sweep(a)
+    if a.cmd == "crop-cache":
+        return _cmd_crop_cache(ap, a)
     crop =a.pipeline == "yolo-crop+unet"
     if a.skip_unboxed and a.pipeline != "unet":
         ap.error("--skip-unboxed goes with --pipeline unet only: no other pipeline runs the U-Net on frames without a box")

@@ -1664,6 +1664,7 @@ static void bgr2gray_host_loop(const uint8_t* __restrict__ bgr, long long n, uin
 #include "og_mjpd.inc"
 #include "og_mjps.inc"
 #include "og_png.inc"
+#include "og_pnge.inc"
 
 extern "C" {
 

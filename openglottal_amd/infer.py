@@ -174,6 +174,26 @@ def iter_pipeline_mjpeg(frames_bgr, detector, pipeline, model, device=None, over
         yield item + (out.cpu().numpy(),) if frames else item
 
 
+def iter_pipeline_png(frames_bgr, detector, pipeline, model, device=None, overlay_style="fill", png_encoder=None, mjpeg_encoder=None,
+                      frames: bool = False, **kw):
+    """The same loop with the annotated frames coded as PNG files on the device (``png.PngEncoder``), and as JPEG files
+    too when ``mjpeg_encoder`` is given: ``(files list[bytes], area float64 [n], jpeg (blob, sizes) or None, frames or None)`` per
+    block.  The frames go from ``Overlay.annotate_dev`` into the coders and cross to the host uncompressed only if ``frames`` asks."""
+    from .png import PngEncoder
+
+    enc = png_encoder if png_encoder is not None else PngEncoder()
+    for out, area in _iter_annotated_dev(frames_bgr, detector, pipeline, model, device, overlay_style, **kw):
+        n, H, W = (int(v) for v in out.shape[:3])
+        blob, sizes, total = enc.encode_resident(out, n, H, W, 3)
+        jpeg = mjpeg_encoder.encode_resident(out) if mjpeg_encoder is not None else None
+        enc.sync()
+        sizes = sizes.cpu().numpy()
+        data = blob[:int(total[0])].cpu().numpy()
+        ends = np.cumsum(sizes.astype(np.int64))
+        files = [data[int(e - k):int(e)].tobytes() for e, k in zip(ends, sizes)]
+        yield files, area.cpu().numpy().astype(np.float64), jpeg, (out.cpu().numpy() if frames else None)
+
+
 def run_pipeline(frames_bgr, detector, pipeline, model, device=None, overlay_style="fill", **kw):
     """``_run_pipeline``: ``(annotated [B,H,W,3] u8, area_wave float64 [B])`` for u8 frames of one shape (BGR, or gray, which is
     drawn on as B = G = R).  ``vft`` is refused with the sentence the CLI uses."""
@@ -236,3 +256,11 @@ def write_pngs(directory: str, start: int, block: np.ndarray) -> None:
     os.makedirs(directory, exist_ok=True)
     for i, f in enumerate(block):
         Image.fromarray(np.ascontiguousarray(f[..., ::-1])).save(os.path.join(directory, f"{start + i:06d}.png"))   # BGR -> RGB
+
+
+def write_png_files(directory: str, start: int, files) -> None:
+    """The files of ``iter_pipeline_png`` under the names ``write_pngs`` gives: ``%06d.png`` from ``start``."""
+    os.makedirs(directory, exist_ok=True)
+    for i, f in enumerate(files):
+        with open(os.path.join(directory, f"{start + i:06d}.png"), "wb") as fh:
+            fh.write(f)

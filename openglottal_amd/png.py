@@ -5,6 +5,9 @@ expansion to B G R (or gray) run on the device.  PNG is lossless: the host twin 
 
 ``PngDecoder`` wraps one ``og_png`` handle.  The files of one call may differ in size and form; a call returns one ``[B,H,W,C]`` array
 when the sizes agree and a list of ``[H,W,C]`` arrays otherwise.
+
+PNG output is coded on the device as well (include_enc/openglottal_hip_pnge.h): ``PngEncoder`` wraps one ``og_pnge`` handle
+and turns frames of one shape into complete files; ``encode_host`` is its twin, byte for byte.
 """
 from __future__ import annotations
 
@@ -195,6 +198,166 @@ def plan(forms, channels: int = 3, chunk: int = 128):
     n = lib().og_png_plan(ptr(f), int(f.shape[0]), int(channels), int(chunk), out, len(out), C.byref(ws))
     if n < 0:
         check(n, "og_png_plan")
+    names = ("kernel", "gx", "gy", "gz", "block", "lds", "workspace", "counters", "writes")
+    recs = [{k: (v if k in ("kernel", "writes") else int(v)) for k, v in zip(names, line.split("|"))} for line in out.value.decode().splitlines()]
+    assert len(recs) == n
+    return recs, ws.value
+
+
+# ── PNG output encoded on the device (include_enc/openglottal_hip_pnge.h) ────────────────────────────────────────────────────────────
+def _frames4(frames) -> np.ndarray:
+    a = np.ascontiguousarray(frames, np.uint8)
+    if a.ndim == 3:
+        a = a[..., None]
+    if a.ndim != 4 or a.shape[3] not in (1, 3):
+        raise OpenGlottalHipError(f"frames must be [B,H,W] or [B,H,W,C] u8 with C = 1 (gray) or 3 (B G R), not {a.shape}")
+    return a
+
+
+def encode_limit(which: int) -> int:
+    return int(lib().og_pnge_limit(which))
+
+
+def encode_bound(H: int, W: int, C: int = 3, segment: int = 32768) -> int:
+    """Worst-case bytes of one encoded file: every segment stored."""
+    n = int(lib().og_pnge_bound(int(H), int(W), int(C), int(segment)))
+    if n < 0:
+        check(-1, "og_pnge_bound")
+    return n
+
+
+def filter_host(frame) -> bytes:
+    """The raw stream of one ``[H,W,C]`` frame: per row the filter type of least cost and the filtered bytes."""
+    a = _frames4(np.asarray(frame)[None])[0]
+    H, W, Cn = a.shape
+    out = np.empty(H * (1 + W * Cn), np.uint8)
+    check(lib().og_pnge_filter_host(ptr(a), H, W, Cn, ptr(out), out.size), "og_pnge_filter_host")
+    return out.tobytes()
+
+
+def deflate_host(raw, segment: int = 32768) -> bytes:
+    """Raw bytes -> the encoder's zlib stream: run-length tokens, one dynamic (or stored) block per ``segment`` bytes."""
+    a = _u8(raw)
+    out = np.empty(6 + a.size + 5 * ((a.size + int(segment) - 1) // int(segment)) + 8, np.uint8)
+    n = C.c_size_t()
+    check(lib().og_pnge_deflate_host(ptr(a), a.size, int(segment), ptr(out), out.size, C.addressof(n)), "og_pnge_deflate_host")
+    return out[:n.value].tobytes()
+
+
+def encode_host(frame, segment: int = 32768) -> bytes:
+    """One ``[H,W]`` / ``[H,W,1]`` gray or ``[H,W,3]`` B G R frame -> a complete PNG file on the CPU: the bytes the device produces."""
+    a = _frames4(np.asarray(frame)[None])[0]
+    H, W, Cn = a.shape
+    out = np.empty(encode_bound(H, W, Cn, segment), np.uint8)
+    n = C.c_int()
+    check(lib().og_pnge_encode_host(ptr(a), H, W, Cn, int(segment), ptr(out), out.size, C.addressof(n)), "og_pnge_encode_host")
+    return out[:n.value].tobytes()
+
+
+class PngEncoder:
+    """One ``og_pnge`` handle: frames of one shape in, complete PNG files out, encoded on the device."""
+
+    def __init__(self, chunk: int = 128, segment: int = 32768):
+        self._h = lib().og_pnge_create()
+        if not self._h:
+            raise OpenGlottalHipError("og_pnge_create failed")
+        self.set_chunk(chunk)
+        self.set_segment(segment)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                lib().og_pnge_destroy(h)
+            except Exception:
+                pass
+
+    def set_chunk(self, chunk: int) -> None:
+        check(lib().og_pnge_set_chunk(self._h, int(chunk)), "og_pnge_set_chunk")
+        self.chunk = int(chunk)
+
+    def set_segment(self, segment: int) -> None:
+        check(lib().og_pnge_set_segment(self._h, int(segment)), "og_pnge_set_segment")
+        self.segment = int(segment)
+
+    def sync(self) -> None:
+        check(lib().og_pnge_sync(self._h), "og_pnge_sync")
+
+    def encode(self, frames):
+        """``[B,H,W,C]`` u8 on the host -> ``(blob u8, sizes int32 [B])``: the B files back to back; only the bytes used come back."""
+        a = _frames4(frames)
+        B, H, W, Cn = a.shape
+        cap = B * encode_bound(H, W, Cn, self.segment)
+        out = np.empty(max(cap, 1), np.uint8)
+        sizes = np.zeros(B, np.int32)
+        total = C.c_longlong()
+        check(lib().og_pnge_encode_stream_u8(self._h, ptr(a), B, H, W, Cn, ptr(out), cap, ptr(sizes), C.addressof(total)), "og_pnge_encode_stream_u8")
+        return out[:total.value].copy(), sizes
+
+    def encode_resident(self, frames_ptr, B: int, H: int, W: int, C_: int = 3):
+        """Frames resident on the device (a CUDA tensor or a raw address) -> ``(blob, sizes, total)`` as CUDA tensors: u8 of
+        ``B * encode_bound`` bytes of which the first ``total[0]`` hold the files, int32 ``[B]``, int64 ``[1]``.  Asynchronous: call
+        ``sync()`` before reading them from another stream."""
+        import torch
+
+        cap = int(B) * encode_bound(H, W, C_, self.segment)
+        blob = torch.empty(max(cap, 1), dtype=torch.uint8, device="cuda")
+        sizes = torch.zeros(max(int(B), 1), dtype=torch.int32, device="cuda")
+        total = torch.zeros(1, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()   # (the handle runs on a stream of its own)
+        check(lib().og_pnge_encode_u8_dev(self._h, ptr(frames_ptr), int(B), int(H), int(W), int(C_), ptr(blob), cap, ptr(sizes), ptr(total)),
+              "og_pnge_encode_u8_dev")
+        return blob, sizes[:int(B)], total
+
+    def files_resident(self, frames_ptr, B: int, H: int, W: int, C_: int = 3) -> list[bytes]:
+        """``encode_resident`` and the files fetched: only their bytes cross the bus."""
+        blob, sizes, total = self.encode_resident(frames_ptr, B, H, W, C_)
+        self.sync()
+        sizes = sizes.cpu().numpy()
+        data = blob[:int(total[0])].cpu().numpy()
+        ends = np.cumsum(sizes.astype(np.int64))
+        return [data[int(e - n):int(e)].tobytes() for e, n in zip(ends, sizes)]
+
+    def label_bbox_dev(self, labels_dev, B: int, H: int, W: int):
+        """``[B,H,W]`` u8 labels resident on the device -> int32 ``[B,4]`` CUDA tensor: the tight box ``x0 y0 x1+1 y1+1`` of
+        ``label > 0``, ``0 0 0 0`` for an empty label (``k_label_bbox``).  Waited for."""
+        import torch
+
+        boxes = torch.zeros((max(int(B), 1), 4), dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        check(lib().og_pnge_label_bbox_u8_dev(self._h, ptr(labels_dev), int(B), int(H), int(W), ptr(boxes)), "og_pnge_label_bbox_u8_dev")
+        self.sync()
+        return boxes[:int(B)]
+
+    def crop_tiles_dev(self, frames_dev, B: int, H: int, W: int, channels: int, boxes_dev, size: int):
+        """``k_crop_tiles`` alone: ``[B,H,W,channels]`` u8 frames and int32 ``[B,4]`` boxes on the device -> ``[B,size,size]`` u8 gray
+        tiles there, ready for ``encode_resident(tiles, B, size, size, 1)``.  Waited for."""
+        import torch
+
+        tiles = torch.empty((max(int(B), 1), int(size), int(size)), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        check(lib().og_pnge_crop_tiles_u8_dev(self._h, ptr(frames_dev), int(B), int(H), int(W), int(channels), ptr(boxes_dev), int(size), ptr(tiles)),
+              "og_pnge_crop_tiles_u8_dev")
+        self.sync()
+        return tiles[:int(B)]
+
+    def files(self, frames) -> list[bytes]:
+        """The files of ``encode`` as a list of ``bytes``."""
+        blob, sizes = self.encode(frames)
+        ends = np.cumsum(sizes.astype(np.int64))
+        return [blob[int(e - n):int(e)].tobytes() for e, n in zip(ends, sizes)]
+
+    def plan(self, B: int, H: int, W: int, C_: int = 3):
+        return encode_plan(B, H, W, C_, self.segment, self.chunk)
+
+
+def encode_plan(B: int, H: int, W: int, C_: int = 3, segment: int = 32768, chunk: int = 128):
+    """Dry run of the streamed encode: ``(records, workspace_bytes)``; a record is a dict of the plan line's fields."""
+    out = C.create_string_buffer(1 << 20)
+    ws = C.c_longlong()
+    n = lib().og_pnge_plan(int(B), int(H), int(W), int(C_), int(segment), int(chunk), out, len(out), C.byref(ws))
+    if n < 0:
+        check(n, "og_pnge_plan")
     names = ("kernel", "gx", "gy", "gz", "block", "lds", "workspace", "counters", "writes")
     recs = [{k: (v if k in ("kernel", "writes") else int(v)) for k, v in zip(names, line.split("|"))} for line in out.value.decode().splitlines()]
     assert len(recs) == n

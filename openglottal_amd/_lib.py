@@ -2,7 +2,7 @@
 include/openglottal_hip_classic.h, include/openglottal_hip_gated.h, include/openglottal_hip_classic_tiled.h,
 include/openglottal_hip_overlay.h, include/openglottal_hip_sweep.h, include/openglottal_hip_gate.h,
 include/openglottal_hip_mjpeg.h, include/decode/openglottal_hip_mjpd.h, include/split/openglottal_hip_mjps.h,
-include_ext/openglottal_hip_png.h, include_enc/openglottal_hip_pnge.h).
+include_ext/openglottal_hip_png.h, include_enc/openglottal_hip_pnge.h, include_enc/openglottal_hip_aug.h).
 
 cffi is not installed in the build image, so the thin C-ABI layer
 the north-star asks for is bound with ctypes; the declarations below are the
@@ -314,6 +314,21 @@ PNGE_PROTOTYPES = {
     "og_pnge_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
 }
 
+# name -> (restype, argtypes); the complete export list of include_enc/openglottal_hip_aug.h (crop-training batches augmented on the device)
+AUG_PROTOTYPES = {
+    "og_aug_limit": (C.c_longlong, [C.c_int]),
+    "og_aug_stage_host": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "og_aug_apply_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "og_aug_noise_host": (C.c_int, [C.c_uint64, C.c_size_t, C.c_void_p]),
+    "og_aug_create": (C.c_void_p, []),
+    "og_aug_destroy": (None, [C.c_void_p]),
+    "og_aug_sync": (C.c_int, [C.c_void_p]),
+    "og_aug_set_chunk": (C.c_int, [C.c_void_p, C.c_int]),
+    "og_aug_batch_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_void_p]),
+    "og_aug_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_longlong)]),
+}
+
 
 def lib() -> C.CDLL:
     """Load the HIP library once; fail loudly if it is not built."""
@@ -339,7 +354,7 @@ def lib() -> C.CDLL:
                                   + list(GATED_PROTOTYPES.items()) + list(TILED_PROTOTYPES.items()) + list(OVERLAY_PROTOTYPES.items())
                                   + list(SWEEP_PROTOTYPES.items()) + list(GATE_PROTOTYPES.items()) + list(MJPEG_PROTOTYPES.items())
                                   + list(MJPD_PROTOTYPES.items()) + list(MJPS_PROTOTYPES.items()) + list(PNG_PROTOTYPES.items())
-                                  + list(PNGE_PROTOTYPES.items())):
+                                  + list(PNGE_PROTOTYPES.items()) + list(AUG_PROTOTYPES.items())):
             fn = getattr(l, name)  # AttributeError if a symbol is missing: also loud
             fn.restype = res
             fn.argtypes = args

@@ -373,12 +373,35 @@ def _cmd_crop_cache(ap, a) -> int:
     return 0
 
 
+def add_augment_preview_parser(sub):
+    """The trainer's augmented samples as files to look at (openglottal_amd/augment.py)."""
+    r = sub.add_parser("augment-preview", help="K augmented image / mask pairs of a crop cache, augmented and PNG-coded on the device")
+    r.add_argument("--cache", required=True, help="the cache directory `crop-cache --out` wrote")
+    r.add_argument("--split", required=True)
+    r.add_argument("--n", type=int, default=8, help="how many samples, from the first one on")
+    r.add_argument("--seed", type=int, default=0)
+    r.add_argument("--out", required=True, help="receives images/%%06d.png (round(I * 255)) and masks/%%06d.png (M * 255)")
+    r.add_argument("--host", action="store_true", help="the host twins instead of the device (same files)")
+    return r
+
+
+def _cmd_augment_preview(ap, a) -> int:
+    if a.n < 1:
+        ap.error("--n must be positive")
+    from . import augment
+
+    k = augment.preview(a.cache, a.split, a.n, a.seed, a.out, host=a.host)
+    print(f"{k} augmented pairs -> {a.out}")
+    return 0
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="openglottal_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
     add_infer_parser(sub)
     add_sweep_parser(sub)
     add_crop_cache_parser(sub)
+    add_augment_preview_parser(sub)
     r = sub.add_parser("run")
     r.add_argument("video")
     r.add_argument("--pipeline", choices=["vft", "guided-vft", "unet", "unet-only", "yolo-crop+unet"], default="unet-only")
@@ -407,6 +430,8 @@ def main(argv=None) -> int:
         return _cmd_sweep(a)
     if a.cmd == "crop-cache":
         return _cmd_crop_cache(ap, a)
+    if a.cmd == "augment-preview":
+        return _cmd_augment_preview(ap, a)
     crop =a.pipeline == "yolo-crop+unet"
     if a.skip_unboxed and a.pipeline != "unet":
         ap.error("--skip-unboxed goes with --pipeline unet only: no other pipeline runs the U-Net on frames without a box")

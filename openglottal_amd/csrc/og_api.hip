@@ -1665,6 +1665,7 @@ static void bgr2gray_host_loop(const uint8_t* __restrict__ bgr, long long n, uin
 #include "og_mjps.inc"
 #include "og_png.inc"
 #include "og_pnge.inc"
+#include "og_aug.inc"
 
 extern "C" {
 
